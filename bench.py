@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the layered ray-march render path on MI355X.  Driver contract: the LAST stdout line of rank 0 is the record,
-< 3 KB (tests/test_bench_record.py); the line before it is a digest of the detail, whose full form goes to bench_detail.json.
+< 3 KB (tests/test_bench_record.py).
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: launches its own N ranks (torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K steps of the headline leg and prints the record alone.  `--full` adds everything
+else: the other arithmetic's cross-check leg, the legs over the other BASELINE configs, the PSNR check against the reference
+fixture, the eager-GPU and CPU baselines, `--emulate-share`, and the detail (a digest line before the record, the whole of it
+in bench_detail.json); the `--no-*` switches trim a `--full` run.  `--dump-outputs DIR` writes what the last timed step
+returned as DIR/<name>.npy (float32; a fixed seeded sample of the rays when the whole 5-tuple would exceed 64 MB).
+
 A "step" = one pass of the hot path over ONE synthetic 1080p view: device ray generation (a1/a2) -> coarse sampler ->
-mask compaction -> MotionNet/SpaceNet (split-bf16 MFMA, the library default; the exact f32 MFMA arithmetic is timed as a
+mask compaction -> MotionNet/SpaceNet (split-bf16 MFMA, the library default; --full times the exact f32 MFMA arithmetic as a
 short cross-check leg of <= 5 steps) -> composite + merge -> inverse-CDF resample -> fine MotionNet/SpaceNet -> composite + merge,
 through the call surface a user of the reference calls: ``stnerf_amd.parallel.render_view`` = what ``render_pose`` runs
 (device ray generation + ``layered_batchify_ray``).
@@ -332,6 +338,53 @@ def emulate_share(model, dims, rank_counts, stripe_rows, device, steps):
             "t1_ms": t1_ms, "steps": steps, "stripe_rows": stripe_rows, "shares": out}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_HEADER_MARGIN = 1 << 16        # .npy headers of every file, and then some
+
+
+def dump_arrays(out):
+    """The reference's 5-tuple of one step -> {name: tensor whose rows are the rays}: mixed fine / coarse (color, depth, acc), the same per
+    layer, and the per-layer hit masks as 0 / 1.  Parts the step did not return (None, e.g. --gather final) are left out."""
+    mixed_fine, mixed_coarse, layer_fine, layer_coarse, masks = out
+    arrays = {}
+
+    def add(prefix, trip):
+        if trip is not None:
+            for part, t in zip(("color", "depth", "acc"), trip):
+                arrays[f"{prefix}_{part}"] = t
+    add("mixed_fine", mixed_fine)
+    add("mixed_coarse", mixed_coarse)
+    for stage, layers in (("fine", layer_fine), ("coarse", layer_coarse)):
+        for i, trip in enumerate(layers or []):
+            add(f"layer{i}_{stage}", trip)
+    for i, m in enumerate(masks or []):
+        arrays[f"layer{i}_mask"] = m
+    return arrays
+
+
+def dump_outputs(out, directory, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write what the timed path returned for its last step to directory/<name>.npy, float32.  When the whole of it would
+    exceed `limit` bytes, every array is written at the same fixed seeded sample of the rays (sorted; their indices in
+    ray_index.npy, float64), as many rays as fit: the same arguments give the same files, so two builds compare output for
+    output.  -> {name: numpy array} as written."""
+    import numpy as np
+    arrays = dump_arrays(out)
+    n = next(iter(arrays.values())).shape[0]
+    per_ray = sum(4 * a[0].numel() for a in arrays.values())
+    if n * per_ray > limit - DUMP_HEADER_MARGIN:
+        keep = (limit - DUMP_HEADER_MARGIN) // (per_ray + 8)
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+        dev_idx = idx.to(next(iter(arrays.values())).device)
+        arrays = {name: a[dev_idx] for name, a in arrays.items()}
+        arrays["ray_index"] = idx.double()
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        written[name] = a.detach().cpu().numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(directory, name + ".npy"), written[name])
+    return written
+
+
 def fail(message, code=2):
     """A run that cannot measure anything still ends with ONE parsable JSON line as the last stdout line (rank 0 only), and a
     non-zero exit status."""
@@ -344,9 +397,12 @@ def fail(message, code=2):
 
 
 def _self_launch(args):
-    """`python bench.py --gpus N` (N > 1) without torch.distributed.run's environment: become the launcher of N ranks of
-    this very command (one process per GPU, rendezvous on 127.0.0.1, a free port)."""
+    """`python bench.py --gpus N` (N > 1) without torch.distributed.run's environment: start the launcher of N ranks of
+    this very command as a child process (one process per GPU, rendezvous on 127.0.0.1, a free port) and exit with its
+    status.  A child, not an exec: this process has already asked the runtime for its device count."""
+    import signal
     import socket
+    import subprocess
     if not args.debug_single_device and torch.cuda.device_count() < args.gpus:
         fail(f"--gpus {args.gpus} but this node exposes {torch.cuda.device_count()} GPU(s): one process per GPU "
              "(check HIP_VISIBLE_DEVICES / the compute partition mode)")
@@ -355,9 +411,13 @@ def _self_launch(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: what RCCL needs on this driver
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")            # dmabuf IPC: what RCCL needs on this driver
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    child = subprocess.Popen(cmd, env=env)
+    signal.signal(signal.SIGTERM, lambda *_: child.terminate())   # a stopped launcher stops its ranks
+    rc = child.wait()
+    sys.exit(rc if rc >= 0 else 128 - rc)                         # killed by signal s: the shell's 128 + s
 
 
 PRECISION_NOTES = {
@@ -584,9 +644,7 @@ def detail_line(detail):
     return line
 
 
-def emit(detail, final, detail_path=None):
-    detail_path = detail_path or DETAIL_PATH
-    final["detail"] = os.path.basename(detail_path)
+def record_line(final):
     line = json.dumps(final)
     if len(line) >= FINAL_LINE_LIMIT:                       # never let verbosity cost the driver its record again
         for k in ("share_emulation", "psnr_vs_reference_dB", "other_precision"):
@@ -594,6 +652,19 @@ def emit(detail, final, detail_path=None):
             line = json.dumps(final)
             if len(line) < FINAL_LINE_LIMIT:
                 break
+    return line
+
+
+def emit(detail, final, detail_path=None):
+    """A --full run: the detail to its file, its digest line, then the record.  detail None (a plain run): the record alone."""
+    if detail is None:
+        final.pop("detail", None)
+        print(record_line(final))
+        sys.stdout.flush()
+        return
+    detail_path = detail_path or DETAIL_PATH
+    final["detail"] = os.path.basename(detail_path)
+    line = record_line(final)
     for path in (detail_path, os.path.join(REPO, "gpurun_out", os.path.basename(detail_path))):
         try:
             if os.path.isdir(os.path.dirname(path)):
@@ -646,11 +717,21 @@ def main():
                     help="comma list of rank counts, e.g. 2,4,8 (N = 1 only): time rank 0's interleaved-stripe share of the view for "
                          "each count on this one GPU -- an EMULATION of a rank's compute, not a scaling measurement "
                          "(profiles/r05_share_emulation.md)")
-    ap.add_argument("--detail-out", default=DETAIL_PATH, help="where the full record goes (default: bench_detail.json beside this script)")
-    ap.add_argument("--dump-outputs", default=None,
-                    help="rank 0 writes the LAST timed step's whole 5-tuple (every rank holds it after the all-gather) to this "
-                         "torch file: tests compare an N-rank run with the 1-rank run bit for bit")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg, run everything else the benchmark measures or checks: the other arithmetic's "
+                         "cross-check leg, the other BASELINE configs' legs, the PSNR check, the eager-GPU and CPU baselines, "
+                         "--emulate-share; print the detail digest and write the detail file.  The --no-* switches trim it")
+    ap.add_argument("--detail-out", default=DETAIL_PATH,
+                    help="--full: where the full record goes (default: bench_detail.json beside this script)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the LAST timed step's 5-tuple (every rank holds it after the all-gather) to DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (else a fixed seeded sample of the rays, indices in ray_index.npy): "
+                         "two builds, or an N-rank and the 1-rank run, compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        fail(f"--steps {args.steps} --warmup {args.warmup}: at least one timed step, no negative warm-up")
+    if args.emulate_share and not args.full:
+        fail("--emulate-share is part of a --full run: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _self_launch(args)                               # does not return
@@ -765,48 +846,43 @@ def main():
     H, W, L, n1, n2, st, dt = dims
     n_rays = H * W
     head = measure(model, dims, args.precision, args.steps, args.warmup)
-    second = None
-    if not args.no_second_precision:
-        # the other arithmetic as a short cross-check leg (<= 5 steps after <= 2 warm-up steps, the same first poses)
-        second = measure(model, dims, "fp32" if args.precision != "fp32" else "bf16x3", min(args.steps, 5), min(args.warmup, 2))
-    model.set_precision(args.precision)
-    config_legs = []
-    if world == 1 and not args.no_config_legs and partition == "stripes":
-        for wl, k in (("walking-1080p-L4-64+64", 2), ("single-512-64+64", 2)):
-            if wl == args.workload:
-                continue
-            m2, d2 = scene(wl)
-            leg = measure(m2, d2, args.precision, k, 1)
-            leg["workload"] = wl
-            leg.pop("out")
-            config_legs.append(leg)
-            del m2
-            torch.cuda.empty_cache()
-    psnr_check = psnr_vs_reference(args.precision, device) if (rank == 0 and not args.no_psnr_check) else None
-    share = None
-    if world == 1 and args.emulate_share:
-        share = emulate_share(model, dims, [int(x) for x in args.emulate_share.split(",")], args.stripe_rows, device,
-                              steps=min(args.steps, 3))
-
     if args.dump_outputs and rank == 0:
-        o = head["out"]
-        torch.save({"mixed_fine": [t.cpu() for t in o[0]], "mixed_coarse": [t.cpu() for t in o[1]],
-                    "layer_fine": [[t.cpu() for t in trip] for trip in o[2]],
-                    "layer_coarse": [[t.cpu() for t in trip] for trip in o[3]], "masks": [t.cpu() for t in o[4]],
-                    "world": world, "partition": partition, "precision": args.precision}, args.dump_outputs)
+        dump_outputs(head["out"], args.dump_outputs)
+    second, config_legs, psnr_check, share = None, [], None, None
+    if args.full:
+        if not args.no_second_precision:
+            # the other arithmetic as a short cross-check leg (<= 5 steps after <= 2 warm-up steps, the same first poses)
+            second = measure(model, dims, "fp32" if args.precision != "fp32" else "bf16x3", min(args.steps, 5), min(args.warmup, 2))
+        model.set_precision(args.precision)
+        if world == 1 and not args.no_config_legs and partition == "stripes":
+            for wl, k in (("walking-1080p-L4-64+64", 2), ("single-512-64+64", 2)):
+                if wl == args.workload:
+                    continue
+                m2, d2 = scene(wl)
+                leg = measure(m2, d2, args.precision, k, 1)
+                leg["workload"] = wl
+                leg.pop("out")
+                config_legs.append(leg)
+                del m2
+                torch.cuda.empty_cache()
+        psnr_check = psnr_vs_reference(args.precision, device) if (rank == 0 and not args.no_psnr_check) else None
+        if world == 1 and args.emulate_share:
+            share = emulate_share(model, dims, [int(x) for x in args.emulate_share.split(",")], args.stripe_rows, device,
+                                  steps=min(args.steps, 3))
 
     if rank == 0:
+        side = args.full and world == 1
         ctx = dict(workload=args.workload, precision=args.precision, steps=args.steps, warmup=args.warmup, world=world,
                    partition=partition, stripe_rows=args.stripe_rows, rays_per_launch=args.rays_per_launch, dims=dims,
                    device=info, psnr=psnr_check,
                    pmc=_load_profile(PMC_TRAFFIC_JSON), hbm_microbench=_load_profile(MEASURED_HBM_JSON),
                    eager=(eager_gpu_baseline(args.workload, args.eager_gpu_baseline_rays, device)
-                          if world == 1 and args.eager_gpu_baseline_rays > 0 else None),
+                          if side and args.eager_gpu_baseline_rays > 0 else None),
                    cpu=(cpu_baseline(args.workload, args.cpu_baseline_rays, args.cpu_threads)
-                        if world == 1 and args.cpu_baseline_rays > 0 else None),
+                        if side and args.cpu_baseline_rays > 0 else None),
                    share=share)
         detail, final = build_records(head, second, config_legs, ctx)
-        emit(detail, final, args.detail_out)
+        emit(detail if args.full else None, final, args.detail_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -6,6 +6,7 @@ import subprocess
 import sys
 
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -199,9 +200,9 @@ def test_more_ranks_than_devices_ends_with_one_json_error_line():
 
 @pytest.mark.gpu
 def test_bench_command_prints_a_parsable_last_line():
-    """The driver's command, short: the LAST stdout line parses, is small, and carries the contract keys."""
+    """The driver's command with --full, short: the LAST stdout line parses, is small, and carries the contract keys."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--cpu-baseline-rays", "3584", "--no-config-legs", "--emulate-share", "8"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -217,3 +218,96 @@ def test_bench_command_prints_a_parsable_last_line():
     assert rec["cpu_baseline"]["chunks"] == 1
     assert rec["value"] == pytest.approx(1080 * 1920 / (rec["ms_per_step"] * 1e-3), rel=1e-3)
     assert "8" in rec["share_emulation"]
+
+
+def test_plain_record_is_one_line_and_writes_no_side_file(capsys, tmp_path, monkeypatch):
+    """A run without --full prints the record alone: no digest line before it, no detail file; the side legs it did not run are absent."""
+    import bench
+    monkeypatch.setattr(bench, "DETAIL_PATH", str(tmp_path / "bench_detail.json"))
+    detail, final = bench.build_records(_canned_leg("bf16x3", 20, 5), None, [],
+                                        _ctx(bench, cpu=None, eager=None, share=None, psnr=None))
+    bench.emit(None, final, str(tmp_path / "bench_detail.json"))
+    lines = capsys.readouterr().out.strip().split("\n")
+    assert len(lines) == 1 and len(lines[0]) < bench.FINAL_LINE_LIMIT
+    rec = json.loads(lines[0])
+    for k in CONTRACT_KEYS:
+        assert k in rec, k
+    assert rec["ms_per_step"] == pytest.approx(3321.2345678, rel=1e-5) and rec["value"] == pytest.approx(1080 * 1920 / 3.3212345678, rel=1e-5)
+    assert rec["higher_is_better"] is True and rec["unit"] == "rays/s" and rec["steps"] == 20 and rec["warmup"] == 5
+    assert rec["cpu_baseline"] is None and "other_precision" not in rec and "detail" not in rec
+    assert not os.listdir(tmp_path)
+
+
+def _canned_tuple(n, l, gen):
+    trip = lambda: (torch.rand(n, 3, generator=gen), torch.rand(n, 1, generator=gen), torch.rand(n, 1, generator=gen))
+    return trip(), trip(), [trip() for _ in range(l)], [trip() for _ in range(l)], [torch.rand(n, generator=gen) > 0.5 for _ in range(l)]
+
+
+def _read_dir(path):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_writes_the_whole_tuple_when_it_fits(tmp_path):
+    import bench
+    gen = torch.Generator().manual_seed(1)
+    out = _canned_tuple(1000, 3, gen)
+    bench.dump_outputs(out, str(tmp_path / "d"))
+    got = _read_dir(tmp_path / "d")
+    assert "ray_index" not in got and len(got) == 2 * 3 + 3 * 2 * 3 + 3
+    assert all(a.dtype.name == "float32" and a.shape[0] == 1000 for a in got.values())
+    assert (got["mixed_fine_color"] == out[0][0].numpy()).all() and (got["mixed_coarse_depth"] == out[1][1].numpy()).all()
+    assert (got["layer2_fine_acc"] == out[2][2][2].numpy()).all() and (got["layer1_coarse_color"] == out[3][1][0].numpy()).all()
+    assert (got["layer0_mask"] == out[4][0].float().numpy()).all()
+    # parts a step does not return (--gather final: no per-layer images, no masks) are left out
+    bench.dump_outputs((out[0], out[1], None, None, None), str(tmp_path / "e"))
+    assert sorted(_read_dir(tmp_path / "e")) == sorted(f"mixed_{s}_{p}" for s in ("fine", "coarse") for p in ("color", "depth", "acc"))
+
+
+def test_dump_outputs_samples_a_fixed_set_of_rays_when_the_tuple_is_too_large(tmp_path):
+    import bench
+    gen = torch.Generator().manual_seed(2)
+    n, l = 20000, 3
+    out = _canned_tuple(n, l, gen)
+    limit = bench.DUMP_HEADER_MARGIN + 400_000                         # room for ~2300 of the 20000 rays
+    first = bench.dump_outputs(out, str(tmp_path / "a"), limit=limit)
+    second = bench.dump_outputs(out, str(tmp_path / "b"), limit=limit)
+    got = _read_dir(tmp_path / "a")
+    assert sorted(got) == sorted(first) and sorted(got) == sorted(_read_dir(tmp_path / "b"))
+    idx = got["ray_index"]
+    assert idx.dtype.name == "float64" and 1000 < len(idx) < n and (idx[1:] > idx[:-1]).all() and idx[0] >= 0 and idx[-1] < n
+    assert all((first[k] == second[k]).all() for k in first)            # the same rays every time
+    rows = torch.from_numpy(idx.astype("int64"))
+    assert (got["mixed_fine_color"] == out[0][0][rows].numpy()).all() and (got["layer2_mask"] == out[4][2][rows].float().numpy()).all()
+    assert all(a.shape[0] == len(idx) for a in got.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) <= limit
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """The plain command: ONE stdout line (the record), no side file, no side legs; --dump-outputs writes the last timed step as float
+    .npy files within 64 MB, the same files from two runs with the same arguments."""
+    import numpy as np
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    recs = []
+    for tag in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag), "--detail-out", str(tmp_path / (tag + ".json"))],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.strip().split("\n") if ln.strip()]
+        assert len(lines) == 1 and len(lines[0]) < 3072, p.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        assert not os.path.exists(tmp_path / (tag + ".json"))
+    rec = recs[0]
+    for k in CONTRACT_KEYS:
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and rec["higher_is_better"] is True
+    assert rec["value"] == pytest.approx(1080 * 1920 / (rec["ms_per_step"] * 1e-3), rel=1e-3)
+    assert rec["cpu_baseline"] is None and "other_precision" not in rec and "psnr_vs_reference_dB" not in rec
+    a, b = _read_dir(tmp_path / "a"), _read_dir(tmp_path / "b")
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    assert all(v.dtype.name in ("float32", "float64") for v in a.values())
+    assert "ray_index" in a and a["mixed_fine_color"].shape == (len(a["ray_index"]), 3) and np.isfinite(a["mixed_fine_color"]).all()
+    assert float(a["mixed_fine_color"].std()) > 0.01                                  # a picture, not zeros
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)

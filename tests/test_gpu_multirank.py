@@ -9,13 +9,14 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
-BENCH_COMMON = ["--steps", "2", "--warmup", "1", "--no-second-precision", "--no-config-legs", "--no-psnr-check",
+BENCH_COMMON = ["--full", "--steps", "2", "--warmup", "1", "--no-second-precision", "--no-config-legs", "--no-psnr-check",
                 "--cpu-baseline-rays", "0", "--eager-gpu-baseline-rays", "0"]
 
 
@@ -34,14 +35,11 @@ def _run_bench(extra, dump):
     side = json.load(open(dump + ".detail.json"))
     assert side["final"] == rec
     rec["_leg"] = side["detail"]["precision_legs"][rec["config"]["precision"]]   # the full leg record (per-rank times, counts)
-    return rec, torch.load(dump)
+    return rec, {f[:-4]: torch.from_numpy(np.load(os.path.join(dump, f))) for f in sorted(os.listdir(dump)) if f.endswith(".npy")}
 
 
 def _flat(d):
-    out = d["mixed_fine"] + d["mixed_coarse"] + d["masks"]
-    for trip in d["layer_fine"] + d["layer_coarse"]:
-        out += trip
-    return out
+    return [d[k] for k in sorted(d)]
 
 
 @pytest.mark.parametrize("workload, precision, world", [("taekwondo-192x256-32+32", "bf16x3", 2),
@@ -51,17 +49,18 @@ def _flat(d):
 def test_bench_launches_its_own_ranks_and_matches_one_rank(tmp_path, workload, precision, world):
     """`python bench.py --gpus N` (no torchrun) = N ranks of the same step function as N = 1; the gathered 5-tuple of the
     last step is the 1-rank one, bit for bit; both lines carry the same partition and scaling label."""
-    one, a = _run_bench(["--gpus", "1", "--workload", workload, "--precision", precision], str(tmp_path / "one.pt"))
+    one, a = _run_bench(["--gpus", "1", "--workload", workload, "--precision", precision], str(tmp_path / "one"))
     many, b = _run_bench(["--gpus", str(world), "--debug-single-device", "--workload", workload, "--precision", precision],
-                         str(tmp_path / "many.pt"))
-    assert one["n_gpus"] == 1 and many["n_gpus"] == world and b["world"] == world
+                         str(tmp_path / "many"))
+    assert one["n_gpus"] == 1 and many["n_gpus"] == world
+    assert sorted(a) == sorted(b) and "ray_index" not in a                          # the whole 5-tuple, no sample of it
     assert one["scaling"] == many["scaling"] == "strong"
     assert one["config"]["workload"] == many["config"]["workload"] == workload
     fa, fb = _flat(a), _flat(b)
     assert len(fa) == len(fb) and len(fa) > 10
     for x, y in zip(fa, fb):
         assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y)
-    assert float(a["mixed_fine"][0].std()) > 0.01                                  # a picture, not zeros
+    assert float(a["mixed_fine_color"].std()) > 0.01                                  # a picture, not zeros
     assert len(many["_leg"]["per_rank_compute_s"]["all"]) == world
     assert abs(many["_leg"]["ray_samples_per_step_rank0"] * world - one["_leg"]["ray_samples_per_step_rank0"]) <= 0.35 * one["_leg"]["ray_samples_per_step_rank0"]
     assert many["roofline"]["frac"] > 0 and many["cpu_baseline"] is None

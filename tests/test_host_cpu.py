@@ -12,7 +12,6 @@ from conftest import GOLDEN
 from oracle import stnerf_oracle as O
 from stnerf_amd import synthetic as syn
 
-REFERENCE = "/root/reference"
 MODEL_KEYS_READ = ["BOARDER_WEIGHT", "SAMPLE_METHOD", "SAME_SPACENET", "TKERNEL_INC_RAW", "POSE_REFINEMENT", "USE_DIR",
                    "USE_DEFORM_VIEW", "USE_DEFORM_TIME", "USE_SPACE_TIME", "BKGD_USE_DEFORM_TIME", "BKGD_USE_SPACE_TIME",
                    "DEEP_RGB", "COARSE_RAY_SAMPLING", "FINE_RAY_SAMPLING"]      # modeling/layered_rfrender.py:23-37 (+ LAYER_NUM)
@@ -42,12 +41,11 @@ def _check_cfg(cfg, want):
     assert cfg.OUTPUT_DIR == want["OUTPUT_DIR"]
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "configs")), reason="the shipped ymls live in the reference checkout")
 @pytest.mark.parametrize("yml", sorted(EXPECT))
 def test_shipped_ymls_load_with_the_values_the_model_reads(yml):
     from stnerf_amd.config import get_cfg_defaults
     cfg = get_cfg_defaults()
-    cfg.merge_from_file(os.path.join(REFERENCE, "configs", yml))
+    cfg.merge_from_file(os.path.join(GOLDEN, "configs", yml))          # the reference's shipped ymls, copied as fixtures
     cfg.freeze()
     _check_cfg(cfg, EXPECT[yml])
     with pytest.raises(AttributeError):

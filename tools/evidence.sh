@@ -12,7 +12,7 @@ timeout 1500 python -m pytest tests -q -m gpu > $out/pytest.log 2>&1; echo rc=$?
 timeout 200 python __graft_entry__.py smoke > $out/smoke.log 2>&1; echo rc=$? >> $out/smoke.log
 # ---- 2. the driver's command with the driver's step counts, socket power / shader clock sampled throughout (>= 60 s per
 #         arithmetic: 25 poses x ~3 s bf16x3, 25 x ~4.8 s f32); bf16x3 = the headline leg, fp32 = the co-equal second leg
-timeout 900 bash tools/power_trace.sh $out/power_bench.csv python bench.py --steps 20 --warmup 5 --emulate-share 2,4,8 --detail-out $out/bench_detail.json > $out/bench.json 2> $out/bench.err; echo rc=$? >> $out/bench.err
+timeout 900 bash tools/power_trace.sh $out/power_bench.csv python bench.py --steps 20 --warmup 5 --full --emulate-share 2,4,8 --detail-out $out/bench_detail.json > $out/bench.json 2> $out/bench.err; echo rc=$? >> $out/bench.err
 # ---- 3. rocprofv3 of ONE step (pose 0) of the same workload per arithmetic: kernel trace, then one PMC pass per counter set
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 CMD="python bench.py --steps 1 --warmup 0 --cpu-baseline-rays 0 --eager-gpu-baseline-rays 0 --no-psnr-check --no-second-precision --no-config-legs --detail-out /tmp/d.json"
@@ -27,7 +27,7 @@ for prec in bf16x3 fp32; do
   fi
 done
 # ---- 4. the other BASELINE configurations on the same build (one bench line each, both arithmetics)
-W="--cpu-baseline-rays 0 --eager-gpu-baseline-rays 0 --no-psnr-check --no-config-legs"
+W="--full --cpu-baseline-rays 0 --eager-gpu-baseline-rays 0 --no-psnr-check --no-config-legs"
 timeout 300 python bench.py --workload single-512-64+64 --steps 5 --warmup 1 $W --detail-out $out/bench_c2_detail.json > $out/bench_c2.json 2> $out/bench_c2.err
 timeout 300 python bench.py --workload taekwondo-1080p-90+30 --steps 3 --warmup 1 $W --detail-out $out/bench_c3_90_30_detail.json > $out/bench_c3_90_30.json 2> $out/bench_c3_90_30.err
 timeout 500 python bench.py --workload walking-1080p-L4-64+64 --steps 2 --warmup 1 --emulate-share 2,4,8 $W --detail-out $out/bench_c4_detail.json > $out/bench_c4.json 2> $out/bench_c4.err
