@@ -157,7 +157,9 @@ int stnerf_pack_transposed(const stnerf_transpose_section* sections, int count, 
 int stnerf_pack_net(int kind, const float* const* weights_host, const float* const* biases_host,
                     int n_tensors, void* dst_host, int64_t dst_bytes);
 
-/* a7 + a9: fused positional encoding + SpaceNet MLP (fp32 MFMA).  modeling/spacenet.py:101-160.
+/* a7 + a9: fused positional encoding + SpaceNet MLP (exact f32 MFMA).  modeling/spacenet.py:101-160.
+ * Exact-f32 blobs (stnerf_pack_net): the stnerf_mlp_stage kernel on a single layer (bit-identical to that layer of a stage launch
+ * without STNERF_STAGE_SIGMOID_RGB), no queue word needed.
  * Work list: ray slot s in [0, count) -> ray j = ray_list ? ray_list[s] : s, where count =
  * ray_count ? min(*ray_count, n_rays) : n_rays; every ray contributes ns samples.
  *   pos   of (j,k): xyz  + j*xyz_ray_stride  + 3k      (3 floats)
@@ -181,7 +183,8 @@ int stnerf_rgb_ray_bias(int kind, const void* packed, int64_t n_rays, const int3
                         const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride,
                         float* out, stnerf_stream_t stream);
 
-/* a7 + a8: fused positional encoding (with the fractional-time lerp) + MotionNet MLP.
+/* a7 + a8: fused positional encoding (with the fractional-time lerp) + MotionNet MLP (exact f32 MFMA: the MotionNet of
+ * stnerf_mlp_stage and of stnerf_train_motionnet_fwd, one persistent launch).
  * modeling/motion_net.py:34-71.  Same work list as above.  flow (may be NULL) gets the 3-vector at
  * flow + j*flow_ray_stride + 3k.  `add_to_xyz` is a set of STNERF_MOTION_* bits: ADD_TO_XYZ updates the
  * point in place (xyz += flow), which is what modeling/layered_rfrender.py:355-356,509-510 do; PLAIN_TIME
@@ -204,14 +207,14 @@ int stnerf_motionnet_fwd(const void* packed, int64_t n_rays, int ns, const int32
  * fp32 accumulate.  Same tensors as stnerf_pack_net; the blob = [the exact-f32 blob of stnerf_pack_net | bias vectors and
  * head weights in the kernel's LDS order | the MFMA layers' weights as bf16 triples in consumption order].  All net
  * kinds.  The device copy must be 1 KB aligned.
- * Edge semantics (tests/test_gpu_stage.py::test_bf16x3_edge_semantics, tests/test_bf16x3_pack_cpu.py):
+ * Edge semantics (tests/test_gpu_stage.py::test_stage_kernels_edge_semantics, tests/test_bf16x3_pack_cpu.py):
  *   weights / biases: STNERF_EINVAL for NaN, +-inf and |w| > 3.3895e38 (bf16's largest finite value; fp32's top 0.4 % cannot be split);
  *   fp32-subnormal weights are accepted, pieces below 2^-133 flush (absolute error < 2^-133 per weight);
  *   sample points must be FINITE (the sampler's and the resampler's are).  Neither stage kernel propagates NaN / inf the way ATen does:
  *   their ReLU is an integer max on the bit pattern (one instruction; -inf and sign-bit NaNs become 0), and the bf16 split turns what is
  *   left into zero pieces.  A sample with a NaN / inf coordinate therefore gets, in bf16x3, the FINITE outputs of a network whose first
  *   layer's activations are zero (the biases' response: the same values for every such sample) where ATen returns NaN; the exact-f32
- *   kernel returns NaN for NaN / +inf coordinates and those finite values for -inf.  Likewise activations that overflow fp32 (|x| > 3.4e38: ATen carries +-inf / NaN on) give unspecified
+ *   kernel (the stage kernel, also behind stnerf_spacenet_fwd) returns NaN for a +inf coordinate and finite values for -inf and NaN.  Likewise activations that overflow fp32 (|x| > 3.4e38: ATen carries +-inf / NaN on) give unspecified
  *   values for that sample.  In every case ONLY that sample is affected: every other sample of the launch, of the same wave included,
  *   is bit-identical to a launch without it.  Subnormal activations and products behave as in the exact-f32 kernel up to the flush. */
 int64_t stnerf_packed_bytes_bf16x3(int kind);
@@ -495,7 +498,8 @@ typedef struct stnerf_render_params {
     int32_t precision;            /* 3: bf16x3 (split-bf16, stnerf_mlp_stage with STNERF_STAGE_BF16X3; nets packed by
                                      stnerf_pack_net_bf16x3) -- what the Python boundary selects by default; 0: exact f32 MFMA, one
                                      persistent stnerf_mlp_stage launch per stage; 2: exact f32, one launch per network
-                                     (round-1 scheduling, for A/B runs).  (1 was the retired split-fp16 mode: rejected.) */
+                                     (stnerf_motionnet_fwd / stnerf_spacenet_fwd: the same arithmetic, for A/B runs of
+                                     the scheduling).  (1 was the retired split-fp16 mode: rejected.) */
     int32_t has_edits;            /* edits_* / pivot are meaningful                                          */
     int32_t bkgd_use_deform_time; /* BKGD_USE_DEFORM_TIME: nets.motion[0] warps the background samples (:358-367) */
     int32_t bkgd_use_space_time;  /* BKGD_USE_SPACE_TIME: background SpaceNets take the frame id (needs use_space_time, :382-390) */

@@ -21,7 +21,7 @@ SOURCES = [
     ("lib.hip", []),
     ("sampler.hip", ["-ffp-contract=off"]),
     ("render.hip", ["-ffp-contract=off"]),
-    ("mlp.hip", []),
+    ("pack.hip", []),
     ("mlp_raybias.hip", []),
     # (no -mllvm -amdgpu-mfma-vgpr-form=1 here: it saves the v_accvgpr_read of every ReLU (+0.3 %), but with it two of
     # three instrumented variants of this file computed wrong, run-to-run varying results on the MI355X -- hipcc 7.2)
@@ -34,7 +34,7 @@ SOURCES = [
     ("render_bwd.hip", []),
     ("train_wave.hip", []),
 ]
-EXTRA = os.environ.get("STNERF_EXTRA_FLAGS", "").split()   # e.g. -DSTNERF_PHASE_PROF (development only)
+EXTRA = os.environ.get("STNERF_EXTRA_FLAGS", "").split()   # e.g. -DSTNERF_WAVE_PROF (development only)
 # STNERF_FLAGS_<source stem> (development): extra flags for ONE source of a variant build, e.g.
 # STNERF_LIB_TAG=noslp STNERF_FLAGS_mlp_bf16x3=-fno-slp-vectorize (the A/B of profiles/retired_designs.md)
 SOURCES = [(s, f + os.environ.get("STNERF_FLAGS_" + s[:-4], "").split()) for s, f in SOURCES]

@@ -1,29 +1,10 @@
-// Pieces shared by the fused MLP kernels (mlp.hip, the stage kernels).
+// Pieces shared by the MLP kernels (the stage kernels, the training kernels) and the host packers (pack.hip).
 #pragma once
 #include "common.h"
 
 namespace stnerf {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// Optional per-phase cycle accounting (development builds: -DSTNERF_PHASE_PROF).  Thread 0 of every
-// workgroup accumulates s_memtime deltas per phase; read back with stnerf_debug_read_phases().
-#ifdef STNERF_PHASE_PROF
-static __device__ unsigned long long g_phase[16];
-#define PH_DECL unsigned long long ph_t = clock64(); unsigned long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define PH(i) do { const unsigned long long n_ = clock64(); ph_acc[i] += n_ - ph_t; ph_t = n_; } while (0)
-#define PH_FLUSH do { if (threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase[i_], ph_acc[i_]); atomicAdd(&g_phase[8], 1ull); } } while (0)
-#define PH_PARAMS , unsigned long long& ph_t, unsigned long long (&ph_acc)[8]
-#define PH_ARGS , ph_t, ph_acc
-#else
-#define PH_DECL
-#define PH(i) do { } while (0)
-#define PH_FLUSH do { } while (0)
-#define PH_PARAMS
-#define PH_ARGS
-#endif
-enum { PH_PE = 0, PH_MMA = 1, PH_BAR1 = 2, PH_EPI = 3, PH_BAR2 = 4, PH_ENC2 = 5, PH_HEAD = 6, PH_MISC = 7 };
-
 
 // ---------------------------------------------------------------------------------------------
 // Packed weight layouts (offsets in floats).  Shared by the host packer and the kernels.
@@ -128,75 +109,9 @@ __device__ __forceinline__ void sincos_pe(float x, float& sn, float& cs) {
     cs = ((q + 1) & 2) ? -cv : cv;
 }
 
-struct WorkList {
-    int64_t n_rays;
-    int ns;
-    const int32_t* ray_list;
-    const int32_t* ray_count;
-};
-
-__device__ __forceinline__ int64_t worklist_rows(const WorkList& wl) {
-    int64_t cnt = wl.n_rays;
-    if (wl.ray_count) {
-        const int64_t c = *wl.ray_count;
-        cnt = c < cnt ? c : cnt;
-    }
-    return cnt * wl.ns;
-}
-
-struct SpaceArgs {
-    const float* net;
-    WorkList wl;
-    const float* xyz;
-    int64_t xyz_ray_stride;
-    const float* dirs;
-    int64_t dirs_ray_stride;
-    const float* times;
-    int64_t times_ray_stride;
-    float* raw;
-    int64_t raw_ray_stride;
-    const float* raybias;  // exact-f32 kernels: [n_rays][128] C operands of rgb_net.1 (mlp_raybias.hip)
-};
-
 // rgb_net.1's direction / time columns once per ray (mlp_raybias.hip): out[ray][128] for the listed rays.
 int launch_ray_bias(int kind, const float* net, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
                     const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride, float* out,
                     hipStream_t stream);
-
-struct MotionArgs {
-    const float* net;
-    WorkList wl;
-    float* xyz;
-    int64_t xyz_ray_stride;
-    const float* times;
-    int64_t times_ray_stride;
-    float* flow;
-    int64_t flow_ray_stride;
-    int add_to_xyz;  // STNERF_MOTION_* flag bits
-};
-
-// Positional-encoding feature f of a tile sample lives at col[(f >> 2) * TM * 4 + (f & 3)], col = encf + s * 4.
-#define ENC_AT(col, f) (col)[((f) >> 2) * TM * 4 + ((f) & 3)]
-
-// Wave -> (feature block, sample blocks) decomposition of a layer with N outputs on a TM-sample tile, NW waves.
-//   N = 256: NW = 4 -> 64 features x all samples per wave;  NW = 8 -> 32 features x all samples;  NW = 16 -> 32 x half
-//   N = 128: NW = 4 -> 32 features x all samples;           NW = 8 -> 32 features x half the samples;  NW = 16 -> 32 x quarter
-// STNERF_WS_SQUARE (experiment): with 8 waves give a 256-wide layer 64 features x half the samples per wave
-// (2 x 2 blocks: 4 global + 4 LDS operand loads per step instead of 2 + 8).
-#ifndef STNERF_WS_SQUARE
-#define STNERF_WS_SQUARE 0
-#endif
-template <int TM, int NW, int N>
-struct WaveSplit {
-    // FS feature slices x SG sample groups = NW waves
-    static constexpr int NFB = (N == 256 && (NW == 4 || (STNERF_WS_SQUARE && NW == 8))) ? 2 : 1;
-    static constexpr int FS = N / (32 * NFB);
-    static constexpr int SG = NW / FS;
-    static constexpr int NSB = (TM / 32) / SG;
-    static_assert(FS * SG == NW && NSB >= 1 && NSB * SG * 32 == TM, "unsupported tile / wave decomposition");
-    __device__ static __forceinline__ int n0(int wave) { return (wave % FS) * NFB * 32; }
-    __device__ static __forceinline__ int sb0(int wave) { return (wave / FS) * NSB; }
-};
-
 
 }  // namespace stnerf

@@ -3,7 +3,7 @@
 // their common prologue / epilogue code is mlp_wave_common.h.  (The round-2 organisation with feature-split waves and
 // activations in LDS, mlp_stage.hip, was removed in round 3.)
 #pragma once
-#include "mlp_blocks.h"
+#include "mlp_common.h"
 
 namespace stnerf {
 
@@ -26,7 +26,7 @@ struct StageArgs {
     int64_t n_rays;
     int64_t xyz_ray_stride, raw_ray_stride, dirs_ray_stride, times_ray_stride;
     const float* dirs;
-    uint32_t* queue;           // one counter, zero at launch
+    uint32_t* queue;           // one counter, zero at launch; nullptr: workgroup b takes the items b, b + grid, ...
     int32_t sigmoid_rgb;       // store sigmoid(rgb) (layers/render_layer.py:47) instead of the raw colour output
     // development builds of mlp_wave.hip (-DSTNERF_WAVE_DEBUG): activations of queue slot 0 after stage `dbg_stage` go to
     // dbg[row][256] (tools/ab_wave.py localises a wrong layer with them); null otherwise
@@ -34,15 +34,16 @@ struct StageArgs {
     int32_t dbg_stage;
 };
 
-// rows of a layer = hit rays x samples per ray
-__device__ __forceinline__ int64_t layer_rows(const StageLayer& ly, int64_t n_rays, int ns) {
+// rows of a work list (include/stnerf.h) = hit rays x samples per ray
+__device__ __forceinline__ int64_t layer_rows(const int32_t* ray_count, int64_t n_rays, int ns) {
     int64_t cnt = n_rays;
-    if (ly.ray_count) {
-        const int64_t c = *ly.ray_count;
+    if (ray_count) {
+        const int64_t c = *ray_count;
         cnt = c < cnt ? c : cnt;
     }
     return cnt * ns;
 }
+__device__ __forceinline__ int64_t layer_rows(const StageLayer& ly, int64_t n_rays, int ns) { return layer_rows(ly.ray_count, n_rays, ns); }
 
 struct RowRef {
     int64_t ray;

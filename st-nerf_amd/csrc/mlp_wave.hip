@@ -22,11 +22,10 @@
 //   * rgb_net.1's direction / time columns come per RAY from mlp_raybias.hip as the layer's C operand.
 //   * Encodings are staged through a wave-private 11 KiB LDS window (the two lanes of a sample split the frequencies,
 //     then each lane reads its half of the feature quads back) -- ordering inside a wave only, no barrier.
-//   * Heads: a lane holds every second feature quad of its sample; the partial-sum grouping of the LDS kernels
-//     (4 parts x 4 interleaved chains) is kept, the two lanes of a sample swap their chains with v_permlane32_swap.
-// Every output accumulates the same products in the same order as in the per-network kernels of mlp.hip (same
-// instruction, same k order, bias as the C operand of the first MFMA, same head grouping): results are bit-identical to
-// them (tests/test_gpu_ops.py).
+//   * Heads: a lane holds every second feature quad of its sample; the partial sums are grouped as 4 parts x 4
+//     interleaved chains (mlp_wave_core.h: head_sigma), the two lanes of a sample swap their chains with v_permlane32_swap.
+// The op-level entries run this arithmetic too: stnerf_spacenet_fwd is this kernel on one layer without a queue
+// (stage_entry.hip), stnerf_motionnet_fwd runs motion_wave in train_motion_fwd_kernel (mlp_wave_core.h, also stage_entry.hip).
 //
 // Reference: modeling/spacenet.py:16-160, modeling/motion_net.py:7-71, modeling/layered_rfrender.py:340-418,495-576.
 #include "mlp_wave_core.h"
@@ -156,10 +155,11 @@ __global__ __launch_bounds__(WV_THREADS, 1) void mlp_wave_stage_kernel(StageArgs
         }
     };
 
-    // ---- prime the pipeline: two items popped, the first one's inputs loaded
+    // ---- prime the pipeline: two items popped, the first one's inputs loaded.  Without a queue (the op-level entry
+    // stnerf_spacenet_fwd has no counter to give) workgroup b takes the items b, b + grid, ... in turn.
     if (tid == 0) {
-        qslot[0] = atomicAdd(a.queue, 1u);
-        qslot[1] = atomicAdd(a.queue, 1u);
+        qslot[0] = a.queue ? atomicAdd(a.queue, 1u) : blockIdx.x;
+        qslot[1] = a.queue ? atomicAdd(a.queue, 1u) : blockIdx.x + gridDim.x;
     }
     __syncthreads();
     uint32_t it0 = __builtin_amdgcn_readfirstlane(qslot[0]);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(WV_THREADS, 1) void mlp_wave_stage_kernel(StageArgs
     while (it0 < total) {
         // the item after next (consumed at the end of this one) and the ray index of the next item's sample
         uint32_t pending = 0;
-        if (tid == 0) pending = atomicAdd(a.queue, 1u);
+        if (tid == 0) pending = a.queue ? atomicAdd(a.queue, 1u) : it1 + gridDim.x;
         RowRef rr_next;
         row_of(it1, rr_next);
         const StageLayer& ly = a.layer[slot_of(it0)];

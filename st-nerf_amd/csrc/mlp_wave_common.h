@@ -2,9 +2,23 @@
 // mlp_bf16x3.hip (split-bf16 MFMA): the wave-private encoding window in LDS, the positional encodings, the lane-pair
 // reduction of the heads, a work item's inputs.
 #pragma once
+#include <type_traits>
+
 #include "mlp_stage.h"
 
 namespace stnerf {
+
+// Weight loads are BUFFER loads: resource descriptor of the packed blob (4 SGPRs) + wave-uniform byte offset (soffset,
+// advanced on the scalar ALU) + per-lane byte offset in a VGPR.  With a per-lane 64-bit pointer (global_load) every load
+// costs 64-bit VALU adds, and on gfx950 every VALU instruction displaces f32 MFMA work (profiles/r01_dual_issue_microbench.md).
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t weight_rsrc(const float* blob) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(blob), 0, 0x7fffffff, 0x00020000);
+}
+__device__ __forceinline__ float4 load_weight(__amdgpu_buffer_rsrc_t rsrc, uint32_t lane_bytes, uint32_t wave_bytes) {
+    const i32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_bytes, wave_bytes, 0);
+    return make_float4(__int_as_float(r.x), __int_as_float(r.y), __int_as_float(r.z), __int_as_float(r.w));
+}
 
 constexpr int WV_ROWS = 32;                       // samples per wave
 constexpr int WV_NW = 4;                          // waves per workgroup: one per SIMD
@@ -139,7 +153,7 @@ __device__ __forceinline__ void encode_motion(float* encw, int lane, const float
 // (ca + partner's ca) + (cb + partner's cb), partner = the other lane of this sample (lane ^ 32), in every lane: two
 // v_permlane32_swap (upper half of the first operand <-> lower half of the second) instead of two ds_bpermute round
 // trips.  After swap(ca, cb) the lower lanes hold {own ca, partner's ca}, the upper lanes {partner's cb, own cb}; the
-// second swap hands both half sums to both halves.  Same additions, same order as in the LDS kernels' reduction.
+// second swap hands both half sums to both halves.
 __device__ __forceinline__ float pair_sum(float ca, float cb) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(ca), __float_as_uint(cb), false, false);
     const float t = __uint_as_float(r[0]) + __uint_as_float(r[1]);

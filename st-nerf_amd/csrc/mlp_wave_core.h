@@ -107,7 +107,14 @@ __device__ __forceinline__ void load_bias(f32x16 (&acc)[8], __amdgpu_buffer_rsrc
 // STEPS K steps whose B operands are blk[s >> 2][4 (s & 3) + kk].  The A operands ping-pong between wa and wb: step s
 // reads buffer (s + PAR) & 1, which holds its weights on entry of the step; the loads of step s + 1 -- for the last
 // step: NFB_NEXT blocks at (next_wlane, next_soff), the first step of whatever runs next -- are issued in front of the
-// MFMAs of step s, one behind each of the first MFMAs (see mma_segment in mlp_blocks.h for the scheduling notes).
+// MFMAs of step s, one behind each of the first MFMAs.  Two things are pinned: sched_barrier(0) fences keep the loads in
+// the step they were written in (left alone, the machine scheduler sinks each load to just before its first use and
+// exposes the L2 latency), and sched_group_barrier interleaves them ONE per MFMA (issued as a clump they take more issue
+// cycles than one MFMA's shadow and the matrix pipe idles).
+// Summation order of an output feature n: the bias is the C operand of the layer's first MFMA; then K step s = 0, 1, ...
+// (k = 8 s .. 8 s + 7), inside a step kk = 0..3 with lane half h supplying k = 8 s + 4 h + kk -- one v_mfma_f32_32x32x2_f32
+// adds the products of k = 8 s + kk and 8 s + 4 + kk.  stage2.0's PE(pos) segment continues the same chain after its 256
+// backbone inputs.
 // The 4 * NFB MFMAs of one K step (B operands b0..b3 = the four k of this lane half), with the NL operand loads the caller
 // has just issued for the following step pinned one behind each of the first MFMAs.
 template <int NFB, int NL>
@@ -311,8 +318,9 @@ __device__ __forceinline__ void dbg_dump(const WaveDbg& d, int stage, const f32x
 // Fetched from the blob into registers EARLY instead, the weights hold 64 .. 192 registers across a layer and the
 // allocator shuffles ~200 values between the register files around them: +0.45 .. 0.75 % for the LDS form.)
 // ---------------------------------------------------------------------------------------------
-// sigma head (256 -> 1) in the grouping of head_partial<TM, 1> with four parts of 16 quads: part pp, chain u runs over
-// the quads 16 pp + u + 4 m, m = 0..3, four fmas each; S_pp = (c0 + c1) + (c2 + c3); sigma = (((b + S_0) + S_1) + S_2) + S_3.
+// sigma head (256 -> 1) as four parts of 16 feature quads with four chains each: part pp, chain u runs over the quads
+// 16 pp + u + 4 m, m = 0..3 in that order, four fmas per quad (features 4 q + 0 .. 3, from 0.f); S_pp = (c0 + c1) + (c2 + c3);
+// sigma = (((b + S_0) + S_1) + S_2) + S_3.
 // This lane holds the quads 2 s + h: its chains are u = h (s = 8 pp + 2 m) and u = h + 2 (s = 8 pp + 2 m + 1).
 // The head is written in two halves (parts 0, 1 over the feature blocks 0..3, parts 2, 3 over blocks 4..7).
 // sigma_in = the bias (half 0) or the result of half 0 (half 1)
@@ -344,8 +352,9 @@ __device__ __forceinline__ float head_sigma(const f32x16 (&in)[8], const float* 
     return sigma;
 }
 
-// 128 -> 3 head (rgb_net's last layer, MotionNet's flow) in the grouping of head_partial<TM, 3> with four parts of 8
-// quads: part pp, chain u over the quads 8 pp + u + 4 m, m = 0, 1.  Weights [3][128] in the LDS window, bias b3.
+// 128 -> 3 head (rgb_net's last layer, MotionNet's flow) in the same grouping with four parts of 8 quads per output: part pp,
+// chain u over the quads 8 pp + u + 4 m, m = 0, 1; out = (((b + S_0) + S_1) + S_2) + S_3.  Weights [3][128] in the LDS window,
+// bias b3.
 __device__ __forceinline__ void head3(const f32x16 (&in)[8], const float* wlds /* the 3 x 128 weights */, const float* __restrict__ b3,
                                       int lane, float (&out)[3]) {
     const float4* w4 = reinterpret_cast<const float4*>(wlds) + (lane >> 5);
@@ -582,5 +591,53 @@ __device__ __forceinline__ void motion_wave(const float* net, float* encw, float
     for (int c3 = 0; c3 < 3; ++c3) p[c3] = p[c3] + fl[c3];
     WP(WP_M_HEAD);
 }
+
+// ---------------------------------------------------------------------------------------------
+// MotionNet over the rows of a launch, one persistent workgroup per CU.  `Rows` says where a row's point and frame id come from
+// and returns the tap that writes what the caller wants besides the flow arithmetic:
+//   MotionFwdArgs  training (train_wave.hip: stnerf_train_motionnet_fwd): rows of xt, the encoding / activation / mask / flow taps;
+//   MotionOpArgs   the op-level stnerf_motionnet_fwd (stage_entry.hip): its work list, flow and / or xyz += flow.
+// Rows: int64_t row_count() (read on the device); Tap fetch(int64_t row, int64_t rows, float (&p)[3], float& tv); int32_t flags; net.
+// ---------------------------------------------------------------------------------------------
+template <class Rows>
+__global__ __launch_bounds__(WV_THREADS, 1) void train_motion_fwd_kernel(Rows a) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_mf[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* encw = reinterpret_cast<float*>(smem_mf) + wave * WV_WAVE_FLOATS;
+    f32x16 acc[8], in[8];
+    float4 wa[8], wb[8];
+#ifdef STNERF_WAVE_DEBUG
+    const WaveDbg dbg{nullptr, 0, -1};
+#endif
+#ifdef STNERF_WAVE_PROF
+    WaveProf wp;
+    for (int i = 0; i < 16; ++i) wp.acc[i] = 0;
+    wp.t = clock64();
+#endif
+    const int64_t rows = a.row_count();
+    const int64_t items = (rows + WV_ITEM - 1) / WV_ITEM;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t row = item * WV_ITEM + wave * WV_ROWS + (lane & 31);
+        float p[3], tv;
+        const auto tap = a.fetch(row, rows, p, tv);
+        motion_wave(a.net, encw, p, tv, a.flags, lane, acc, in, wa, wb WV_DBG_ARG WP_ARG, tap);
+    }
+}
+
+// One persistent workgroup per CU (at most one per item).
+template <class Rows>
+static int launch_motion_fwd(const Rows& a, int64_t max_rows, const char* what, hipStream_t stream) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t items = (max_rows + WV_ITEM - 1) / WV_ITEM;
+    const int grid = (int)(items < cus ? items : cus);
+    if (const int rc = reserve_dynamic_lds(reinterpret_cast<const void*>(train_motion_fwd_kernel<Rows>), WV_LDS, what)) return rc;
+    hipLaunchKernelGGL(train_motion_fwd_kernel<Rows>, dim3(grid), dim3(WV_THREADS), WV_LDS, stream, a);
+    STNERF_CHECK_LAUNCH(what);
+    return STNERF_OK;
+}
+
 
 }  // namespace stnerf

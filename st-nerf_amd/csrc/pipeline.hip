@@ -164,6 +164,8 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
             set_launch_tag(-1);
             return r2;
         }
+        // precision 2: one launch per network through the op-level entries -- the same exact-f32 wave arithmetic, scheduled
+        // network by network (the deformed points go back to xyz in between)
         for (int i = 0; i < l; ++i) {
             if (i == 0 ? !p->bkgd_use_deform_time : !p->use_deform_time) continue;
             if (i > 0 && !p->shown[i]) continue;  // a hidden layer's points are never consumed

@@ -17,6 +17,8 @@
 // and that pair is what modeling/autograd.py runs unless the model was built for exact f32; the forward's entry point is here, the chain's
 // beside its kernel.)
 //
+// The MotionNet's forward kernel (train_motion_fwd_kernel, mlp_wave_core.h) also runs the op-level stnerf_motionnet_fwd (stage_entry.hip).
+//
 // What is left to per-layer launches are the weight gradients dW_s = d y_s^T x_s (csrc/train.hip: a reduction over ALL rows that
 // no 128-row item can finish on its own) and the encodings' chain rule.
 //
@@ -233,40 +235,26 @@ struct MotionStoreTap {
         }
     }
 };
+// The training instantiation of train_motion_fwd_kernel (mlp_wave_core.h): row r of xt = {x, y, z, frame id} in, the MotionStoreTap
+// of row r out.
 struct MotionFwdArgs {
     const float* net;    // packed MotionNet (exact f32)
     const float* xt;     // [rows][4]: x, y, z, frame id
     int64_t rows;
     int32_t flags;       // STNERF_MOTION_PLAIN_TIME
     MotionTapArgs tap;
-};
-__global__ __launch_bounds__(WV_THREADS, 1) void train_motion_fwd_kernel(MotionFwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float4 smem_mf[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* encw = reinterpret_cast<float*>(smem_mf) + wave * WV_WAVE_FLOATS;
-    f32x16 acc[8], in[8];
-    float4 wa[8], wb[8];
-#ifdef STNERF_WAVE_DEBUG
-    const WaveDbg dbg{nullptr, 0, -1};
-#endif
-#ifdef STNERF_WAVE_PROF
-    WaveProf wp;
-    for (int i = 0; i < 16; ++i) wp.acc[i] = 0;
-    wp.t = clock64();
-#endif
-    const int64_t items = (a.rows + WV_ITEM - 1) / WV_ITEM;
-    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t row = item * WV_ITEM + wave * WV_ROWS + (lane & 31);
-        const bool valid = row < a.rows;
+    __device__ __forceinline__ int64_t row_count() const { return rows; }
+    __device__ __forceinline__ MotionStoreTap fetch(int64_t row, int64_t n, float (&p)[3], float& tv) const {
+        const bool valid = row < n;
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (valid) x = *reinterpret_cast<const float4*>(a.xt + row * 4);
-        float p[3] = {x.x, x.y, x.z};
-        const MotionStoreTap tap{&a.tap, (uint32_t)row, valid};
-        motion_wave(a.net, encw, p, x.w, a.flags, lane, acc, in, wa, wb WV_DBG_ARG WP_ARG, tap);
+        if (valid) x = *reinterpret_cast<const float4*>(xt + row * 4);
+        p[0] = x.x;
+        p[1] = x.y;
+        p[2] = x.z;
+        tv = x.w;
+        return MotionStoreTap{&tap, (uint32_t)row, valid};
     }
-}
+};
 
 // Backward chain: d a_{l-1} = (d a_l * [a_l > 0]) W_l from the flow head back to motion_net.0's input, the gradient in the wave's
 // registers between layers (128-wide products in K-step pairs like the forward), every masked gradient written once (the left
@@ -496,14 +484,7 @@ extern "C" int stnerf_train_motionnet_fwd(const void* packed, const float* xt, i
     a.tap.bits = relu_bits;
     a.tap.bits_stride = relu_bits_stride;
     a.tap.flow = flow;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t items = (rows + WV_ITEM - 1) / WV_ITEM;
-    const int grid = (int)(items < cus ? items : cus);
-    if (const int rc = reserve_dynamic_lds(reinterpret_cast<const void*>(train_motion_fwd_kernel), WV_LDS, "train_motionnet_fwd")) return rc;
-    hipLaunchKernelGGL(train_motion_fwd_kernel, dim3(grid), dim3(WV_THREADS), WV_LDS, as_stream(stream), a);
-    STNERF_CHECK_LAUNCH("train_motionnet_fwd");
-    return STNERF_OK;
+    return launch_motion_fwd(a, rows, "train_motionnet_fwd", as_stream(stream));
 }
 
 extern "C" int stnerf_train_motionnet_dx(const float* wt, const uint32_t* offsets_host /* motion_net.0, .2, .4, .6, .8, head */, const float* d_flow,

@@ -88,7 +88,7 @@ class LayeredRFRender(nn.Module):
                                            # also takes "z" (l,N,N2) / "xyz_c" / "xyz_f": the reference's own fine depths and deformed
                                            # points (teacher forcing, stnerf_amd.modeling.training.render_rays_train)
         self.mlp_schedule = "stage"        # "stage": one persistent MLP launch per stage (stnerf_mlp_stage); "per_net":
-                                           # one launch per (layer, network) as in round 1 (A/B measurements)
+                                           # one launch per (layer, network) through the op-level entries (A/B measurements)
         self.ray_window = (0, 0, 0)        # (first, stripe, period): which rays of the view `rays` are (include/stnerf.h);
                                            # keeps the RNG stream of a view under multi-GPU sharding
         self.shard_views = type(self).SHARD_VIEWS_DEFAULT

@@ -1,5 +1,5 @@
 """Deformation MLP with the reference's constructor and forward (modeling/motion_net.py:5-71); the forward pass
-is ``stnerf_motionnet_fwd`` (csrc/mlp.hip), including the fractional-time lerp of the encodings (:49-60)."""
+is ``stnerf_motionnet_fwd`` (csrc/stage_entry.hip: the stage kernel's MotionNet), including the fractional-time lerp of the encodings (:49-60)."""
 from __future__ import annotations
 
 import torch

@@ -2,7 +2,7 @@
 
 The parameters are ordinary ``nn.Linear`` modules under the reference's attribute names, so
 ``state_dict()`` / ``load_state_dict()`` speak the reference's checkpoint keys; the forward pass is the
-fused positional-encoding + 9-layer MFMA kernel behind ``stnerf_spacenet_fwd`` (csrc/mlp.hip).
+fused positional-encoding + 9-layer MFMA kernel behind ``stnerf_spacenet_fwd`` (the stage kernel of csrc/mlp_wave.hip on one layer).
 """
 from __future__ import annotations
 

@@ -228,13 +228,13 @@ def test_bf16x3_module_level_calls(ops):
     _close(flow.cpu(), f64, 1.0, "flow")
 
 
-def test_bf16x3_edge_semantics(ops):
+def test_stage_kernels_edge_semantics(ops):
     """What include/stnerf.h states for values outside the comfortable range, next to what ATen (the fp32 oracle) does:
       * sample points must be finite.  A sample with a NaN / +-inf coordinate is NOT turned into NaN outputs the way ATen does it
         (sin(inf) = NaN, carried through every layer): the stage kernels' ReLU is an integer max on the bit pattern (-inf and sign-bit
         NaNs become 0) and the bf16 split zeroes what is left -- bf16x3 returns the FINITE outputs of a network whose first layer's
-        activations are zero (the same density for every such sample, whatever its point), the exact-f32 kernel NaN for NaN / +inf
-        and those finite values for -inf.  What IS guaranteed:
+        activations are zero (the same density for every such sample, whatever its point), the exact-f32 kernel (the stage kernel, also
+        behind the op-level entry) NaN for +inf and finite values for -inf and NaN.  What IS guaranteed:
         only that sample is affected -- every other sample of the launch, of the same wave included, is bit-identical to a launch
         without the bad points;
       * activations that overflow fp32 (two layers scaled by 1e20: ATen carries +-inf / NaN on): unspecified for that sample, no fault,
@@ -268,8 +268,11 @@ def test_bf16x3_edge_semantics(ops):
     assert bool(torch.isnan(rgb32[is_bad]).all()) and bool(torch.isnan(sig32[is_bad]).all())          # ATen: NaN
     assert bool(torch.isfinite(got[is_bad]).all())                                                    # bf16x3: zeroed hidden units ...
     assert float((got[is_bad][:, 3] - got[is_bad][0, 3]).abs().max()) < 1e-6                         # ... the same sigma for each of them
-    assert bool(torch.isnan(got32[3, 5]).all()) and bool(torch.isnan(got32[7, 0]).all())              # exact f32: NaN for NaN / +inf,
-    assert bool(torch.isfinite(got32[9, 2]).all())                                                    # the integer ReLU's 0 for -inf
+    assert bool(torch.isnan(got32[7, 0]).all())                                                       # exact f32: NaN for +inf,
+    assert all(bool(torch.isfinite(got32[i, j]).all()) for i, j in ((3, 5), (9, 2), (9, 3)))          # the integer ReLU's 0 for -inf / NaN
+    raw_stage = torch.full((n, ns, 4), 7.0, device="cuda")                                            # (the one-layer stage, bit for bit)
+    ops.mlp_stage([dict(space=net32, motion=None, xyz=dev(bad), raw=raw_stage, times=None)], dev(dirs), ns)
+    assert torch.equal(got32.view(torch.int32), raw_stage.cpu().view(torch.int32))
     # ---- activations out of fp32's range: no fault, and what ATen keeps finite stays finite
     big = {k: v.clone() for k, v in sd.items()}
     big["net.stage1.0.weight"] *= 1e20

@@ -268,3 +268,24 @@ def test_weight_gradient_kernel_loops_are_what_the_design_says(tmp_path):
     for c in bx:
         assert c.get("ds_read_b128") == 32 and c.get("buffer_load_dwordx4") == 16 and c.get("s_barrier") == 2, dict(c)
         assert c.get("v_cvt_pk_bf16_f32") == 192 and valu(c) <= 5 * 192, (valu(c), dict(c))
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
+def test_motionnet_forward_instantiations_use_no_scratch_and_make_no_call(tmp_path):
+    """train_motion_fwd_kernel<Rows> (csrc/mlp_wave_core.h) runs the MotionNet of the stage kernel over the rows of a launch, one wave per
+    SIMD (as launched): its training instantiation (csrc/train_wave.hip, the taps) and the op-level one behind stnerf_motionnet_fwd
+    (csrc/stage_entry.hip, the work list).  Every instantiation: no scratch, no call, and the MFMAs of the network -- motion_net.0's 11 K
+    steps and the rolled body of the four 128 x 128 layers, 16 MFMAs per K step."""
+    found = []
+    for src, rows in (("train_wave.hip", "MotionFwdArgs"), ("stage_entry.hip", "MotionOpArgs")):
+        text = open(_compile(src, tmp_path)).read()
+        names = re.findall(r"^(_ZN6stnerf23train_motion_fwd_kernelI\S*):", text, re.M)
+        assert len(names) == 1 and rows in names[0], (src, names)
+        for k in names:
+            tail = text[text.index(k + ":"):]
+            body = tail[:tail.index("s_endpgm")]
+            assert int(re.search(r"; ScratchSize: (\d+)", tail).group(1)) == 0, k
+            assert "scratch_" not in body and "s_swappc" not in body, k
+            assert body.count("v_mfma_f32_32x32x2_f32") == 11 * 16 + 16 * 16, (k, body.count("v_mfma_f32_32x32x2_f32"))
+            found.append(k)
+    assert len(found) == 2, found

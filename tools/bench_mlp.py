@@ -1,4 +1,4 @@
-"""Microbenchmark of the fused per-network MLP kernels (mlp.hip: the op-level entry points)."""
+"""Microbenchmark of the op-level MLP entry points (one network per launch: the wave kernels of mlp_wave.hip / train_wave.hip)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -199,7 +199,7 @@ for prec in ("bf16x3", "fp32"):
     fdb, wdb = os.path.join(src, f"pmc_FETCH_SIZE_{prec}", "p_results.db"), os.path.join(src, f"pmc_WRITE_SIZE_{prec}", "p_results.db")
     if os.path.exists(fdb) and os.path.exists(wdb):
         cf, cw = sqlite3.connect(fdb).cursor(), sqlite3.connect(wdb).cursor()
-        for name, like in (("spacenet", "%spacenet_kernel%"), ("motionnet", "%motionnet_kernel%"), ("mlp_stage", "%mlp%stage_kernel%"), ("composite", "%composite%kernel%"),
+        for name, like in (("mlp_stage", "%mlp%stage_kernel%"), ("motionnet", "%train_motion_fwd_kernel%"), ("composite", "%composite%kernel%"),
                            ("resample", "%resample_kernel%"), ("sample_coarse", "%sample_coarse_kernel%")):
             nf, fkb = cf.execute("select count(*), sum(value) from counters_collection where counter_name='FETCH_SIZE' and kernel_name like ?", (like,)).fetchone()
             nw, wkb = cw.execute("select count(*), sum(value) from counters_collection where counter_name='WRITE_SIZE' and kernel_name like ?", (like,)).fetchone()
