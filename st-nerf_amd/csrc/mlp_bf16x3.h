@@ -58,4 +58,25 @@ struct StoreTapArgs;
 int launch_bf16x3_stage(const StageArgs& a, bool deep_rgb, int cus, hipStream_t stream);
 int launch_bf16x3_stage_store(const StageArgs& a, const StoreTapArgs& t, int cus, hipStream_t stream);
 
+// One MotionNet on its own (mlp_bf16x3_motion_kernel): rows (hit ray, j), j < ns, of a work list; row (ray, j) moves the point of
+// sample slots[ray][j] (slots == nullptr: sample j) in place, p += flow, with the stage kernel's arithmetic (motion_bx).  A slot
+// of -1 is no row.  The render pipeline runs it in front of stage launches that then skip the MotionNet (pipeline.hip).
+struct MotionBxArgs {
+    const float* net;          // packed bf16x3 MotionNet (1 KB aligned)
+    const int32_t* ray_list;   // the work list of include/stnerf.h
+    const int32_t* ray_count;
+    int64_t n_rays;
+    int32_t ns;                // rows per ray
+    int32_t flags;             // STNERF_MOTION_PLAIN_TIME
+    float* xyz;
+    int64_t xyz_ray_stride;
+    const float* times;
+    int64_t times_ray_stride;
+    const int32_t* slots;      // [ray][slot_ray_stride] or nullptr
+    int64_t slot_ray_stride;
+    uint32_t* queue;           // one counter, zero at launch
+    int64_t stream_off;        // (set by the launcher: bx_layout(STNERF_NET_MOTION).stream_off)
+};
+int launch_bf16x3_motion(const MotionBxArgs& a, int cus, hipStream_t stream);
+
 }  // namespace stnerf

@@ -27,10 +27,11 @@
 //   * PE, bias, ReLU, heads, outputs: fp32, as in the exact-f32 kernels; rgb_net.1's direction / time columns come per
 //     ray from mlp_raybias.hip (exact f32) as the layer's C operand.
 //
-// Three kernels are built from this machinery (round 6): the stage kernel of the render path (mlp_bf16x3_stage_kernel<DEEP, NoTapArgs>);
+// Four kernels are built from this machinery: the stage kernel of the render path (mlp_bf16x3_stage_kernel<DEEP, NoTapArgs>);
 // the same kernel with the training tap (<false, StoreTapArgs>: every layer's post-ReLU output and its mask bits written out as the
-// rows pass -- stnerf_train_spacenet_fwd_bf16x3); and the backward chain d x = (d y AND mask) W over the TRANSPOSED weights as a
-// second bf16x3 stream (train_space_dx_bx_kernel -- stnerf_train_spacenet_dx_bf16x3).  Packers: host (stnerf_pack_net_bf16x3) and
+// rows pass -- stnerf_train_spacenet_fwd_bf16x3); the backward chain d x = (d y AND mask) W over the TRANSPOSED weights as a
+// second bf16x3 stream (train_space_dx_bx_kernel -- stnerf_train_spacenet_dx_bf16x3); and the stage kernel's MotionNet alone over rows of
+// its own (mlp_bf16x3_motion_kernel: the render pipeline's MotionNet reuse, pipeline.hip).  Packers: host (stnerf_pack_net_bf16x3) and
 // device (stnerf_pack_net_bf16x3_device, stnerf_pack_dx_bf16x3_device) at the end of the file.
 //
 // Reference: modeling/spacenet.py:16-160, modeling/motion_net.py:7-71, modeling/layered_rfrender.py:340-418,495-576; training:
@@ -695,6 +696,9 @@ __device__ __forceinline__ void enc_to_act(const float* encw, int lane, bf16x8 (
 // ---------------------------------------------------------------------------------------------
 // MotionNet on the wave's 32 samples: p += flow (modeling/layered_rfrender.py:356,510).  19 slots.
 // ---------------------------------------------------------------------------------------------
+// INST: which kernel inlines it (0: the stage kernel, 1: mlp_bf16x3_motion_kernel).  One shared function body changed the stage
+// kernel's code (the same arithmetic, other registers and address constants in the MotionNet loop); two keep it as it was.
+template <int INST = 0>
 __device__ __forceinline__ void motion_bx(Ctx& cx, const float* net, const float* cm, float* encw, float (&p)[3], float tv, int flags,
                                           int lane, f32x16 (&big)[4], f32x16 (&small)[4], bf16x8 (&act)[3][16] BXP_PARAM) {
     const MotionLayout L = motion_layout();
@@ -1460,6 +1464,159 @@ int launch_bf16x3_stage_store(const StageArgs& a, const StoreTapArgs& t, int cus
         return rc;
     hipLaunchKernelGGL((mlp_bf16x3_stage_kernel<false, StoreTapArgs>), dim3(grid), dim3(WV_THREADS), BX_LDS, stream, a, t);
     STNERF_CHECK_LAUNCH("train_space_fwd (bf16x3)");
+    return STNERF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// MotionNet alone (MotionBxArgs): the stage kernel's item loop with one network.  motion_bx is the fused kernel's code, and a
+// sample's flow depends on nothing but its point, frame id and flags (its column of every product): the moved points are the
+// bits the stage kernel would have computed for the same rows.  The consts go to LDS once (one network per launch); the weight
+// stream is the MotionNet's 19 slots per item, three slots ahead across items as in the stage kernel.
+// ---------------------------------------------------------------------------------------------
+constexpr int BX_LDS_MOTION = BX_LDS_RING + BX_LDS_ENC + BX_CONST_MOTION * 4 + 16;
+static_assert(BX_LDS_MOTION <= 160 * 1024, "bf16x3 motion kernel: LDS budget");
+
+struct MotionBxIn {
+    float p[3], tv;
+    float* dst;   // the sample's point (valid rows)
+    bool valid;
+};
+
+__global__ __launch_bounds__(WV_THREADS, 1) void mlp_bf16x3_motion_kernel(MotionBxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_bxm[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    char* ring = smem_bxm;
+    float* encw = reinterpret_cast<float*>(smem_bxm + BX_LDS_RING) + wave * WV_ENC_FLOATS;
+    float* cm = reinterpret_cast<float*>(smem_bxm + BX_LDS_RING + BX_LDS_ENC);
+    uint32_t* qslot = reinterpret_cast<uint32_t*>(cm + BX_CONST_MOTION);
+    const int64_t rows = layer_rows(a.ray_count, a.n_rays, a.ns);
+    const uint32_t total = (uint32_t)((rows + WV_ITEM - 1) / WV_ITEM);
+    // row = 128 item + 32 wave + (lane & 31) = (hit ray rslot, j); both lane halves hold the same row
+    auto fetch = [&](uint32_t item, MotionBxIn& in) {
+        in.valid = false;
+        in.dst = nullptr;
+        in.tv = 0.f;
+#pragma unroll
+        for (int c3 = 0; c3 < 3; ++c3) in.p[c3] = 0.f;
+        const int64_t row = (int64_t)item * WV_ITEM + wave * WV_ROWS + (lane & 31);
+        if (item >= total || row >= rows) return;
+        const int64_t rslot = row / a.ns;
+        const int j = (int)(row - rslot * a.ns);
+        const int64_t ray = a.ray_list ? (int64_t)a.ray_list[rslot] : rslot;
+        const int k = a.slots ? a.slots[ray * a.slot_ray_stride + j] : j;
+        if (k < 0) return;
+        float* src = a.xyz + ray * a.xyz_ray_stride + 3 * k;
+#pragma unroll
+        for (int c3 = 0; c3 < 3; ++c3) in.p[c3] = src[c3];
+        in.tv = a.times[ray * a.times_ray_stride];
+        in.dst = src;
+        in.valid = true;
+    };
+    const char* stream0 = reinterpret_cast<const char*>(a.net) + a.stream_off;
+    auto seg_of = [&](uint32_t item) { return item < total ? Seg{stream0, (uint32_t)bx_motion_slots()} : Seg{nullptr, 0u}; };
+
+    // ---- prime: the consts, two items popped, the first one's inputs, three slots of the stream in flight
+    {
+        const char* mc = stream0 - BX_CONST_MOTION * 4 + lane * 16;
+        auto dm = (__attribute__((address_space(3))) char*)(cm);
+        __builtin_amdgcn_global_load_lds(mc + wave * BX_CHUNK, (__attribute__((address_space(3))) void*)(dm + wave * BX_CHUNK), 16, 0, 0);
+    }
+    if (tid == 0) {
+        qslot[0] = atomicAdd(a.queue, 1u);
+        qslot[1] = atomicAdd(a.queue, 1u);
+    }
+    __syncthreads();
+    uint32_t it0 = __builtin_amdgcn_readfirstlane(qslot[0]);
+    uint32_t it1 = __builtin_amdgcn_readfirstlane(qslot[1]);
+    __syncthreads();
+    if (it0 >= total) {  // (uniform)
+        BX_VMCNT(0);     // (no LDS-DMA may outlive the workgroup)
+        return;
+    }
+    MotionBxIn cur, nxt;
+    fetch(it0, cur);
+    Ctx cx;
+    cx.ring = ring;
+    cx.wave = wave;
+    cx.lane = lane;
+    cx.gi = 0;
+    cx.gc = 0;
+    cx.st_on = false;
+    cx.rcur = (uint32_t)(uintptr_t)ring + (uint32_t)lane * 16u;
+    cx.rnext = cx.rcur + BX_SLOT;
+    cx.seg[0] = seg_of(it0);
+    cx.seg[1] = Seg{nullptr, 0u};
+    cx.seg[2] = seg_of(it1);
+    cx.seg[3] = Seg{nullptr, 0u};
+    cx.idle = stream0;
+    dma_issue(cx);
+    dma_issue(cx);
+    dma_issue(cx);
+    BX_VMCNT(12);
+    __builtin_amdgcn_s_barrier();
+    a_read<0>(cx.A[0].p[0], cx.rcur);
+    a_read<BX_CHUNK>(cx.A[0].p[1], cx.rcur);
+    a_read<2 * BX_CHUNK>(cx.A[0].p[2], cx.rcur);
+    a_read<BX_UNIT>(cx.A[1].p[0], cx.rcur);
+    a_read<BX_UNIT + BX_CHUNK>(cx.A[1].p[1], cx.rcur);
+    a_read<BX_UNIT + 2 * BX_CHUNK>(cx.A[1].p[2], cx.rcur);
+    int par = 0;
+    f32x16 big[4], small[4];
+    bf16x8 act[3][16];
+#ifdef STNERF_BX_PROF
+    BxProf bp;
+    for (int i = 0; i < 16; ++i) bp.acc[i] = 0;
+    bp.t = clock64();
+#endif
+    while (it0 < total) {
+        uint32_t pending = 0;
+        if (tid == 0) pending = atomicAdd(a.queue, 1u);
+        // the next item's inputs: a chain of dependent loads (list -> slot -> point) that waits behind the ring's DMA queue,
+        // once per item, here rather than between the slots
+        fetch(it1, nxt);
+        float p[3];
+#pragma unroll
+        for (int c3 = 0; c3 < 3; ++c3) p[c3] = cur.p[c3];
+        int ln = lane;   // (opaque per item, as in the stage kernel)
+        asm volatile("" : "+v"(ln));
+        motion_bx<1>(cx, a.net, cm, encw, p, cur.tv, a.flags, ln, big, small, act BXP_ARG);
+        if (cur.valid && lane < 32) {
+#pragma unroll
+            for (int c3 = 0; c3 < 3; ++c3) cur.dst[c3] = p[c3];
+        }
+        if (tid == 0) qslot[par] = pending;
+        __syncthreads();
+        const uint32_t it2 = __builtin_amdgcn_readfirstlane(qslot[par]);
+        par ^= 1;
+        it0 = it1;
+        it1 = it2;
+        cur = nxt;
+        cx.seg[0] = cx.seg[2];
+        cx.seg[2] = seg_of(it1);
+        BXP(BXP_END);
+#ifdef STNERF_BX_PROF
+        bp.acc[BXP_ITEMS] += 1;
+#endif
+    }
+    BX_VMCNT(0);  // (no LDS-DMA may outlive the workgroup)
+#ifdef STNERF_BX_PROF
+    if (lane == 0)
+        for (int i = 0; i < 16; ++i) atomicAdd(&g_bxphase[i], bp.acc[i]);
+#endif
+}
+
+int launch_bf16x3_motion(const MotionBxArgs& args, int cus, hipStream_t stream) {
+    MotionBxArgs a = args;
+    a.stream_off = bx_layout(STNERF_NET_MOTION).stream_off;
+    const int64_t max_items = (a.n_rays * a.ns + WV_ITEM - 1) / WV_ITEM;
+    if (max_items == 0) return STNERF_OK;
+    const int grid = (int)(max_items < cus ? max_items : cus);  // one persistent workgroup per CU
+    if (const int rc = reserve_dynamic_lds(reinterpret_cast<const void*>(mlp_bf16x3_motion_kernel), BX_LDS_MOTION, "motionnet (bf16x3)"))
+        return rc;
+    hipLaunchKernelGGL(mlp_bf16x3_motion_kernel, dim3(grid), dim3(WV_THREADS), BX_LDS_MOTION, stream, a);
+    STNERF_CHECK_LAUNCH("motionnet (bf16x3)");
     return STNERF_OK;
 }
 

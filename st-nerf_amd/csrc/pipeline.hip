@@ -3,9 +3,11 @@
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
 // enqueued on the caller's stream into a caller-provided workspace (no allocation, no synchronisation).
+#include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
+#include "mlp_bf16x3.h"
 
 using namespace stnerf;
 
@@ -25,12 +27,15 @@ struct Carve {
 
 // sizes of the workspace regions for n rays (shared by the size query and the carve)
 struct Plan {
-    int64_t t_c, xyz_c, raw_c, w_c, t_f, xyz_f, raw_f, list, count, flags, raybias;
+    int64_t t_c, xyz_c, raw_c, w_c, slots, t_f, xyz_f, raw_f, list, count, flags, raybias;
     // Once the resampler has read t_c / w_c the whole coarse block [t_c | xyz_c | raw_c | w_c] is dead: the fine network outputs
     // (raw_f, the largest fine buffer) are written over it.  shared = the larger of the two.  64 + 64 samples: 9 n1 = 576 floats
     // of coarse block per (ray, layer) against 4 S = 512 of raw_f -- the workspace goes from 1728 to 1216 floats (- 30 %).
     static int64_t pad(int64_t floats) { return (floats + 63) & ~int64_t(63); }   // 256-byte granules, as Carve::take
-    int64_t coarse_block() const { return pad(t_c) + pad(xyz_c) + pad(raw_c) + pad(w_c); }
+    // The fine MotionNet's slot lists (MotionNet reuse, below) are written over raw_c / w_c, which are dead once the resampler
+    // has run, and read before the fine stage writes raw_f: 64 + 64 samples need n2 = 64 of the 5 l n1 words there.
+    int64_t tail() const { return pad(raw_c) + pad(w_c) > pad(slots) ? pad(raw_c) + pad(w_c) : pad(slots); }
+    int64_t coarse_block() const { return pad(t_c) + pad(xyz_c) + tail(); }
     int64_t shared() const { return coarse_block() > pad(raw_f) ? coarse_block() : pad(raw_f); }
 };
 Plan make_plan(int64_t n, int l, int n1, int n2, int only_coarse) {
@@ -40,12 +45,14 @@ Plan make_plan(int64_t n, int l, int n1, int n2, int only_coarse) {
     p.xyz_c = n * l * n1 * 3;
     p.raw_c = n * l * n1 * 4;
     p.w_c = only_coarse ? 0 : n * l * n1;
+    p.slots = only_coarse ? 0 : n * n2;   // int32, one layer at a time
     p.t_f = only_coarse ? 0 : n * l * S;
     p.xyz_f = only_coarse ? 0 : n * l * S * 3;
     p.raw_f = only_coarse ? 0 : n * l * S * 4;
     p.list = (int64_t)l * n;
     p.flags = n;                      // one byte per ray: the compositor's scratch
-    p.count = STNERF_MAX_LAYERS + 2;  // hit-ray counts + the work-queue heads of the two network stages
+    // hit-ray counts + the work-queue heads of the two network stages + those of the MotionNet launches (coarse, fine per layer)
+    p.count = STNERF_MAX_LAYERS + 2 + 2 * STNERF_MAX_LAYERS;
     p.raybias = (int64_t)l * n * 128;  // per (layer, ray): the C operands of rgb_net.1 (mlp_raybias.hip), reused by both stages
     return p;
 }
@@ -72,6 +79,86 @@ static int clear_mask_hints(uint8_t* mask, int64_t count, hipStream_t stream) {
     hipLaunchKernelGGL(clear_mask_hints_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, mask, count);
     STNERF_CHECK_LAUNCH("render_rays (mask)");
     return STNERF_OK;
+}
+
+// ---- MotionNet reuse (split-bf16 stages).  The fine pass deforms all n1 + n2 sorted depths of a performer ray (:495-510); n1 of
+// them ARE the coarse depths, which the coarse pass has deformed with the same network, frame id and flags (:340-356).  With the
+// same box edit in both passes a depth gives the same point (t d + o, then the un-edit: the same expression in the sampler and
+// the resampler), so the same flow.  Such a layer runs its MotionNet in launches of its own (mlp_bf16x3_motion_kernel): over the
+// coarse points in place, then -- after the resampler -- only over the fine samples whose depth is not one of the coarse ones;
+// the others take the moved coarse point.  Both stage launches then skip its MotionNet.  The points are the fused kernel's bits.
+
+// One wave per hit ray of `layer`: fine sample m whose depth is bitwise one of the coarse depths takes that coarse sample's moved
+// point; the others, ascending, are the ray's slot list (n2 entries, -1 padded: at least n1 of the S samples are coarse depths).
+static __global__ void __launch_bounds__(256) motion_reuse_fill_kernel(const float* __restrict__ t_c, const float* __restrict__ xyz_c,
+                                                                       const float* __restrict__ t_f, float* __restrict__ xyz_f,
+                                                                       const int32_t* __restrict__ ray_list, const int32_t* __restrict__ ray_count,
+                                                                       int64_t n, int l, int layer, int n1, int n2, int32_t* __restrict__ slots) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t cnt = *ray_count < n ? (int64_t)*ray_count : n;
+    if (w >= cnt) return;
+    const int64_t ray = ray_list[w];
+    const int S = n1 + n2;
+    const int64_t pair = ray * l + layer;
+    const uint32_t* tc = reinterpret_cast<const uint32_t*>(t_c) + pair * n1;
+    const uint32_t* tf = reinterpret_cast<const uint32_t*>(t_f) + pair * S;
+    int32_t* sl = slots + ray * n2;
+    int filled = 0;
+    for (int m0 = 0; m0 < S; m0 += 64) {
+        const int m = m0 + lane;
+        int match = -1;
+        if (m < S) {
+            const uint32_t v = tf[m];
+            for (int k = 0; k < n1 && match < 0; ++k) match = tc[k] == v ? k : -1;
+        }
+        const bool open = m < S && match < 0;
+        const uint64_t bal = __ballot(open);
+        if (open) {
+            const int pos = filled + __popcll(bal & ((1ull << lane) - 1ull));
+            if (pos < n2) sl[pos] = m;
+        } else if (m < S) {
+            const float* src = xyz_c + (pair * n1 + match) * 3;
+            float* dst = xyz_f + (pair * S + m) * 3;
+            dst[0] = src[0];
+            dst[1] = src[1];
+            dst[2] = src[2];
+        }
+        filled += __popcll(bal);
+    }
+    for (int j = filled + lane; j < n2; j += 64) sl[j] = -1;
+}
+
+// MotionNet of performer `layer` over rows (hit ray, j < ns) in place; slots: the fine pass's lists (nullptr: row j = sample j)
+static int motion_rows(const stnerf_nets* nets, const stnerf_render_params* p, const float* rays, int64_t n, int layer, int ns, int S,
+                       float* xyz, const int32_t* ray_list, const int32_t* ray_count, const int32_t* slots, int slot_stride,
+                       uint32_t* queue, hipStream_t st) {
+    STNERF_REQUIRE(((uintptr_t)nets->motion[layer] & 1023) == 0, "render_rays: packed MotionNet of layer %d must be 1024-byte aligned", layer);
+    MotionBxArgs a;
+    memset(&a, 0, sizeof(a));
+    a.net = static_cast<const float*>(nets->motion[layer]);
+    a.ray_list = ray_list + (int64_t)layer * n;
+    a.ray_count = ray_count + layer;
+    a.n_rays = n;
+    a.ns = ns;
+    a.flags = 0;
+    a.xyz = xyz + (int64_t)layer * S * 3;
+    a.xyz_ray_stride = (int64_t)p->l * S * 3;
+    a.times = rays + (p->retiming ? 6 + layer : 6);
+    a.times_ray_stride = p->ray_stride;
+    a.slots = slots;
+    a.slot_ray_stride = slot_stride;
+    a.queue = queue;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    set_launch_tag(layer);
+    int rc;
+    {
+        LaunchTimer timer(PROF_MOTIONNET, STNERF_NET_MOTION, n, ns, 0, st);
+        rc = launch_bf16x3_motion(a, cus, st);
+    }
+    set_launch_tag(-1);
+    return rc;
 }
 
 extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
@@ -109,6 +196,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
     float* xyz_c = cb.take<float>(pl.xyz_c);
     float* raw_c = cb.take<float>(pl.raw_c);
     float* w_c = cb.take<float>(pl.w_c);
+    int32_t* slots = reinterpret_cast<int32_t*>(raw_c);   // over raw_c / w_c: written after the resampler, read before the fine stage
     float* raw_f = shared;            // over the coarse block: first written by the fine stage, after the resampler read t_c / w_c
     float* t_f = ws.take<float>(pl.t_f);
     float* xyz_f = ws.take<float>(pl.xyz_f);
@@ -124,15 +212,27 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                               p->ray_index_stripe, p->ray_index_period,
                               p->has_edits ? p->edits_coarse : nullptr, p->pivot, t_c, xyz_c, mask, stream);
     if (rc) return rc;
-    if (hipMemsetAsync(ray_count, 0, sizeof(int32_t) * (STNERF_MAX_LAYERS + 2), st) != hipSuccess) {
+    if (hipMemsetAsync(ray_count, 0, sizeof(int32_t) * pl.count, st) != hipSuccess) {
         set_error("render_rays: hipMemsetAsync failed");
         return STNERF_ELAUNCH;
     }
     rc = stnerf_compact_rays(mask, n, l, ray_list, ray_count, stream);
     if (rc) return rc;
 
+    // ---- the performer layers whose MotionNet runs on its own (MotionNet reuse, above): split-bf16 stages, both passes, the same
+    // box edit in both (STNERF_MOTION_REUSE=0: every layer fused, for A/B runs and tests)
+    uint32_t reuse = 0;
+    if (p->precision == 3 && !p->only_coarse && p->use_deform_time) {
+        const char* sw = getenv("STNERF_MOTION_REUSE");
+        if (!(sw && sw[0] == '0'))
+            for (int i = 1; i < l; ++i)
+                if (p->shown[i] && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
+                    reuse |= 1u << i;
+    }
+    uint32_t* motion_queue = reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
+
     // ---- one network stage: deform + evaluate every shown layer on its hit rays (:340-418 / :495-576)
-    auto stage = [&](float* xyz, float* raw, int ns, bool fine) -> int {
+    auto stage = [&](float* xyz, float* raw, int ns, bool fine, uint32_t moved) -> int {
         const int64_t xs = (int64_t)l * ns * 3, ws_ = (int64_t)l * ns * 4;
         if (p->precision == 0 || p->precision == 3) {
             // exact f32 / bf16x3: ONE persistent launch over every shown layer (csrc/stage_entry.hip); deformed performers
@@ -147,7 +247,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                     const bool timed = (i > 0 ? 1 : p->bkgd_use_space_time) && p->use_space_time;
                     stnerf_stage_layer& e = sl[ns_l++];
                     e.space = i == 0 ? (fine ? nets->bkgd_fine : nets->bkgd) : (fine ? nets->space_fine[i] : nets->space[i]);
-                    e.motion = deform ? nets->motion[i] : nullptr;
+                    e.motion = deform && !(moved >> i & 1) ? nets->motion[i] : nullptr;   // (moved: points deformed already)
                     e.ray_list = i == 0 ? nullptr : ray_list + (int64_t)i * n;
                     e.ray_count = i == 0 ? nullptr : ray_count + i;
                     e.xyz = xyz + (int64_t)i * ns * 3;
@@ -197,7 +297,12 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
         set_launch_tag(-1);
         return STNERF_OK;
     };
-    rc = stage(xyz_c, raw_c, n1, false);
+    for (int i = 1; i < l; ++i) {
+        if (!(reuse >> i & 1)) continue;
+        rc = motion_rows(nets, p, rays, n, i, n1, n1, xyz_c, ray_list, ray_count, nullptr, 0, motion_queue + 2 * i, st);
+        if (rc) return rc;
+    }
+    rc = stage(xyz_c, raw_c, n1, false, reuse);
     if (rc) return rc;
 
     // ---- coarse: density edits, per-layer + merged composite (:414-448)
@@ -224,7 +329,16 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                          rays, rs,
                          p->has_edits ? p->edits_fine : nullptr, p->pivot, mask, t_f, xyz_f, nullptr, nullptr, nullptr, stream);
     if (rc) return rc;
-    rc = stage(xyz_f, raw_f, S, true);
+    for (int i = 1; i < l; ++i) {   // (xyz_c and t_c lie under raw_f: read here, before the fine stage)
+        if (!(reuse >> i & 1)) continue;
+        hipLaunchKernelGGL(motion_reuse_fill_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, t_c, xyz_c, t_f, xyz_f,
+                           ray_list + (int64_t)i * n, ray_count + i, n, l, i, n1, n2, slots);
+        STNERF_CHECK_LAUNCH("render_rays (MotionNet reuse)");
+        if (n2 == 0) continue;
+        rc = motion_rows(nets, p, rays, n, i, n2, S, xyz_f, ray_list, ray_count, slots, n2, motion_queue + 2 * i + 1, st);
+        if (rc) return rc;
+    }
+    rc = stage(xyz_f, raw_f, S, true, reuse);
     if (rc) return rc;
     cp.fine = 1;
     cp.cut_negative_t = 0;
