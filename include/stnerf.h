@@ -198,7 +198,7 @@ int stnerf_motionnet_fwd(const void* packed, int64_t n_rays, int ns, const int32
                          int64_t flow_ray_stride, int add_to_xyz, stnerf_stream_t stream);
 
 /* "bf16x3": the packed form of a network for the split-bf16 arithmetic of stnerf_mlp_stage (STNERF_STAGE_BF16X3;
- * csrc/mlp_bf16x3.hip).  modeling/spacenet.py:45-86, modeling/motion_net.py:20-32 are plain fp32 nn.Linear layers: every
+ * csrc/mlp_bf16x3.hip; packers: csrc/pack_bf16x3.hip).  modeling/spacenet.py:45-86, modeling/motion_net.py:20-32 are plain fp32 nn.Linear layers: every
  * weight (host side, here) and every activation (in the kernel) is split into three bf16 numbers, x = x0 + x1 + x2 --
  * 8 + 8 + 8 significand bits, i.e. exact for every finite fp32 value inside bf16's exponent range (|x| <= 3.39e38: above
  * bf16's largest finite value the leading piece rounds to inf; residual pieces below 2^-133 flush, an error < 2^-16 of
@@ -440,7 +440,7 @@ int stnerf_train_spacenet_fwd_bf16x3(int kind, const void* packed, int64_t n_ray
 int stnerf_train_spacenet_dx(const float* wt, const uint32_t* offsets_host, const float* d_raw, int64_t rows, const uint32_t* relu_bits,
                              int64_t relu_bits_stride, float* const* dy_host, const int32_t* ld_dy_host, float* dpe, int32_t ld_dpe,
                              stnerf_stream_t stream);
-/* stnerf_train_spacenet_dx in split bf16 (round 6; csrc/mlp_bf16x3.hip: train_space_dx_bx_kernel -- the forward kernel's machinery with
+/* stnerf_train_spacenet_dx in split bf16 (round 6; csrc/train_bf16x3.hip: train_space_dx_bx_kernel -- the forward kernel's machinery with
  * the transposed weights as a bf16x3 stream through the LDS ring, the masks fetched per work item by LDS-DMA): same inputs, same dy
  * matrices, fp32-faithful values.  The weights come as ONE blob, stnerf_pack_dx_bf16x3_device(kind, weights_dev (the network's 10
  * weight tensors in reference layout, host array of device pointers), 10, with_dpos, dst (1 KB aligned,

@@ -22,6 +22,7 @@ SOURCES = [
     ("sampler.hip", ["-ffp-contract=off"]),
     ("render.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
+    ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),
     # (no -mllvm -amdgpu-mfma-vgpr-form=1 here: it saves the v_accvgpr_read of every ReLU (+0.3 %), but with it two of
     # three instrumented variants of this file computed wrong, run-to-run varying results on the MI355X -- hipcc 7.2)
@@ -33,10 +34,12 @@ SOURCES = [
     ("train_dw.hip", []),
     ("render_bwd.hip", []),
     ("train_wave.hip", []),
+    ("train_bf16x3.hip", []),
 ]
 EXTRA = os.environ.get("STNERF_EXTRA_FLAGS", "").split()   # e.g. -DSTNERF_WAVE_PROF (development only)
 # STNERF_FLAGS_<source stem> (development): extra flags for ONE source of a variant build, e.g.
-# STNERF_LIB_TAG=noslp STNERF_FLAGS_mlp_bf16x3=-fno-slp-vectorize (the A/B of profiles/retired_designs.md)
+# STNERF_LIB_TAG=noslp STNERF_FLAGS_mlp_bf16x3=-fno-slp-vectorize (the A/B of profiles/retired_designs.md); the split-bf16 backward
+# chain is the stem train_bf16x3
 SOURCES = [(s, f + os.environ.get("STNERF_FLAGS_" + s[:-4], "").split()) for s, f in SOURCES]
 COMMON = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(REPO, "include"), "-I" + CSRC]

@@ -1,4 +1,5 @@
-// Blob layout of the split-bf16 ("bf16x3") networks, shared by the host packer and the stage kernel (mlp_bf16x3.hip).
+// Blob layouts of the split-bf16 ("bf16x3") networks, shared by the packers (pack_bf16x3.hip) and the kernels that stream them
+// (mlp_bf16x3.hip, train_bf16x3.hip).  The forward blob:
 //
 //   [ f32 section ]  the exact-f32 packed blob of the same network (stnerf_pack_net: SpaceLayout / MotionLayout) -- the
 //                    per-ray prologue (mlp_raybias.hip) and the scalar head biases read it
@@ -45,6 +46,12 @@ __host__ __device__ inline BxLayout bx_layout(int kind) {
     B.total_bytes = B.stream_off + (int64_t)B.n_slots * BX_SLOT;
     return B;
 }
+
+// The backward chain's blob (train_space_dx_bx_kernel, SpaceNets without deep_rgb): [consts][stream of the TRANSPOSED weights]
+constexpr int BXD_CONST = 1024;                    // floats: density_net.0's 256 weights | the colour head [3][128] | pad
+constexpr int BXD_W_SIGMA = 0, BXD_W_RGB2 = 256;
+// rgb_net.1[:, :256]: 2 passes x 8 K steps; six 256 x 256 layers: 2 x 16; with_dpos: the two half passes (2 blocks x 16 K steps) to PE(pos)
+__host__ __device__ inline int bxd_slots(bool with_dpos) { return 8 + 6 * 16 + (with_dpos ? 8 : 0); }
 
 // Input column of B-operand position (K step t, lane half h, element j):
 //   layers fed by the previous layer's accumulators: register 8 (t & 1) + j of block t >> 1 = feature 32 fb + 8 q + 4 h + r

@@ -1,4 +1,4 @@
-// Pieces shared by the MLP kernels (the stage kernels, the training kernels) and the host packers (pack.hip).
+// Pieces shared by the MLP kernels (the stage kernels, the training kernels) and the packers (pack.hip, pack_bf16x3.hip).
 #pragma once
 #include "common.h"
 

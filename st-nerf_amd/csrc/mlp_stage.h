@@ -66,7 +66,7 @@ __device__ __forceinline__ float lerp_enc(bool frac, float om, float wgt, float 
     return frac ? om * va + wgt * vb : va;
 }
 
-// Training: where a stage kernel's tap writes every layer's input (mlp_wave.hip: StoreTap, exact f32; mlp_bf16x3.hip:
+// Training: where a stage kernel's tap writes every layer's input (mlp_wave.hip: StoreTap, exact f32; mlp_bf16x3_core.h:
 // BxStoreTap, split bf16).  Row r of the launch <-> row r of every matrix.
 struct NoTapArgs {};
 constexpr int TAP_PE = 100;   // the taps' stage id of the staged encoding

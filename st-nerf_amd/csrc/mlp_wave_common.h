@@ -1,5 +1,5 @@
 // Pieces shared by the two sample-split ("a wave owns 32 samples") stage kernels: mlp_wave.hip (exact f32 MFMA) and
-// mlp_bf16x3.hip (split-bf16 MFMA): the wave-private encoding window in LDS, the positional encodings, the lane-pair
+// mlp_bf16x3.hip + mlp_bf16x3_core.h (split-bf16 MFMA): the wave-private encoding window in LDS, the positional encodings, the lane-pair
 // reduction of the heads, a work item's inputs.
 #pragma once
 #include <type_traits>

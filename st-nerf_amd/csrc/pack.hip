@@ -1,6 +1,7 @@
 // The packers of the exact-f32 networks -- host (stnerf_pack_net) and device (stnerf_pack_net_device): the reference's
 // nn.Linear tensors -> the [K/4][N][4] blob the MFMA kernels stream their A operands from (layouts: mlp_common.h) -- the
 // transposed sections of the fused backward chains (stnerf_pack_transposed), and the stand-alone positional encoding.
+// (The split-bf16 blobs: pack_bf16x3.hip.)
 //
 // Reference: modeling/spacenet.py:16-160, modeling/motion_net.py:7-71, utils/dimension_kernel.py:3-73.
 #include <stdlib.h>
@@ -36,85 +37,11 @@ __global__ void encode_kernel(const float* __restrict__ x, int64_t n, int dim, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side
+// The blob of a network, stated once: a table of segments, each either a linear layer's re-blocking -- (out, in) row-major ->
+// [ceil(in / 4) (padded to kq)][out][4], zero padded -- or a plain copy.  pack_table() lists the segments of a network kind;
+// pack_element() is one output float of one segment.  The host packer runs it in a CPU loop, the device packer in a grid-stride
+// kernel (blockIdx.y = the segment): one layout, and a test of the host blob is a test of the table both use.
 // ---------------------------------------------------------------------------------------------
-// (out,in) row-major -> [ceil(in/4) (padded to kq)][out][4], zero padded.
-static void pack_linear(const float* w, int out_f, int in_f, int kq, float* dst) {
-    memset(dst, 0, sizeof(float) * (size_t)kq * out_f * 4);
-    for (int n = 0; n < out_f; ++n)
-        for (int k = 0; k < in_f; ++k) dst[((size_t)(k >> 2) * out_f + n) * 4 + (k & 3)] = w[(size_t)n * in_f + k];
-}
-
-}  // namespace stnerf
-
-using namespace stnerf;
-
-extern "C" int64_t stnerf_packed_bytes(int kind) {
-    switch (kind) {
-        case STNERF_NET_SPACE: return space_layout(false).total * 4;
-        case STNERF_NET_SPACE_TIME: return space_layout(true).total * 4;
-        case STNERF_NET_SPACE_DEEP: return space_layout(false, true).total * 4;
-        case STNERF_NET_SPACE_TIME_DEEP: return space_layout(true, true).total * 4;
-        case STNERF_NET_MOTION: return motion_layout().total * 4;
-        default: set_error("packed_bytes: unknown net kind %d", kind); return STNERF_EINVAL;
-    }
-}
-
-extern "C" int stnerf_pack_net(int kind, const float* const* W, const float* const* B, int n_tensors, void* dst_host,
-                               int64_t dst_bytes) {
-    STNERF_REQUIRE(W && B && dst_host, "pack_net: null pointer");
-    float* dst = static_cast<float*>(dst_host);
-    if (STNERF_NET_IS_SPACE(kind)) {
-        const bool ut = STNERF_NET_USES_TIME(kind), deep = STNERF_NET_IS_DEEP(kind);
-        const SpaceLayout L = space_layout(ut, deep);
-        const int nt = deep ? 12 : 10;
-        STNERF_REQUIRE(n_tensors == nt, "pack_net: this SpaceNet kind takes %d tensors, got %d", nt, n_tensors);
-        STNERF_REQUIRE(dst_bytes >= L.total * 4, "pack_net: dst too small");
-        for (int i = 0; i < nt; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net: tensor %d is null", i);
-        memset(dst, 0, (size_t)L.total * 4);
-        const int in_f[7] = {63, 256, 256, 256, 319, 256, 256};
-        for (int i = 0; i < 7; ++i) {
-            pack_linear(W[i], 256, in_f[i], L.kq[i], dst + L.w[i]);
-            memcpy(dst + L.b[i], B[i], 256 * sizeof(float));
-        }
-        memcpy(dst + L.w_sigma, W[7], 256 * sizeof(float));
-        dst[L.b_sigma] = B[7][0];
-        pack_linear(W[8], 128, 256 + 27 + (ut ? 21 : 0), L.kq_rgb1, dst + L.w_rgb1);
-        memcpy(dst + L.b_rgb1, B[8], 128 * sizeof(float));
-        for (int i = 0; i < 2 && deep; ++i) {
-            pack_linear(W[9 + i], 128, 128, 32, dst + L.w_deep[i]);
-            memcpy(dst + L.b_deep[i], B[9 + i], 128 * sizeof(float));
-        }
-        memcpy(dst + L.w_rgb2, W[nt - 1], 3 * 128 * sizeof(float));
-        memcpy(dst + L.b_rgb2, B[nt - 1], 3 * sizeof(float));
-        return STNERF_OK;
-    }
-    if (kind == STNERF_NET_MOTION) {
-        const MotionLayout L = motion_layout();
-        STNERF_REQUIRE(n_tensors == 6, "pack_net: MotionNet takes 6 tensors, got %d", n_tensors);
-        STNERF_REQUIRE(dst_bytes >= L.total * 4, "pack_net: dst too small");
-        for (int i = 0; i < 6; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net: tensor %d is null", i);
-        memset(dst, 0, (size_t)L.total * 4);
-        const int in_f[5] = {84, 128, 128, 128, 128};
-        for (int i = 0; i < 5; ++i) {
-            pack_linear(W[i], 128, in_f[i], L.kq[i], dst + L.w[i]);
-            memcpy(dst + L.b[i], B[i], 128 * sizeof(float));
-        }
-        memcpy(dst + L.w_out, W[5], 3 * 128 * sizeof(float));
-        memcpy(dst + L.b_out, B[5], 3 * sizeof(float));
-        return STNERF_OK;
-    }
-    set_error("pack_net: unknown net kind %d", kind);
-    return STNERF_EINVAL;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The exact-f32 packing ON THE DEVICE: the same blob as stnerf_pack_net from tensors that live in HBM -- what a training loop needs
-// after every optimizer.step() (the host packer costs a D2H of the weights, a CPU loop and an H2D per network: 165 ms per
-// iteration for the eight networks of a C3 model against 40 ms of kernels).  One launch per network: a table of segments, each
-// either a linear layer's [Kq][N][4] re-blocking (zero padded) or a plain copy; blockIdx.y = the segment.
-// ---------------------------------------------------------------------------------------------
-namespace stnerf {
 struct PackSeg {
     const float* src;
     int64_t dst_off;   // floats
@@ -123,40 +50,35 @@ struct PackSeg {
 struct PackTable {
     PackSeg seg[26];
     int32_t count;
+    int64_t total;     // floats of the blob
 };
+__host__ __device__ inline int64_t pack_seg_floats(const PackSeg& sg) { return sg.kq > 0 ? (int64_t)sg.kq * sg.n * 4 : sg.n; }
+__host__ __device__ inline float pack_element(const PackSeg& sg, int64_t i) {
+    if (sg.kq == 0) return sg.src[i];
+    const int r = (int)(i & 3);
+    const int64_t q = i >> 2;
+    const int n = (int)(q % sg.n), k = 4 * (int)(q / sg.n) + r;
+    return k < sg.in_f ? sg.src[(int64_t)n * sg.in_f + k] : 0.f;
+}
 __global__ void pack_net_device_kernel(PackTable t, float* dst) {
     const PackSeg sg = t.seg[blockIdx.y];
-    const int64_t total = sg.kq > 0 ? (int64_t)sg.kq * sg.n * 4 : sg.n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        float v;
-        if (sg.kq > 0) {
-            const int r = (int)(i & 3);
-            const int64_t q = i >> 2;
-            const int n = (int)(q % sg.n), k = 4 * (int)(q / sg.n) + r;
-            v = k < sg.in_f ? sg.src[(int64_t)n * sg.in_f + k] : 0.f;
-        } else {
-            v = sg.src[i];
-        }
-        dst[sg.dst_off + i] = v;
-    }
+    const int64_t total = pack_seg_floats(sg);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        dst[sg.dst_off + i] = pack_element(sg, i);
 }
-}  // namespace stnerf
 
-extern "C" int stnerf_pack_net_device(int kind, const float* const* W, const float* const* B, int n_tensors, void* dst_dev, int64_t dst_bytes,
-                                      stnerf_stream_t stream) {
-    STNERF_REQUIRE(W && B && dst_dev, "pack_net_device: null pointer");
-    PackTable t;
+// The segments of a network (tensors in the reference's order; checks their count, not the pointers: each entry does that in its
+// own order); `who` names the entry in the error texts.
+static int pack_table(const char* who, int kind, const float* const* W, const float* const* B, int n_tensors, PackTable& t) {
     memset(&t, 0, sizeof(t));
     auto lin = [&](const float* w, int n, int in_f, int kq, int64_t off) { t.seg[t.count++] = PackSeg{w, off, n, in_f, kq}; };
     auto cpy = [&](const float* src, int count, int64_t off) { t.seg[t.count++] = PackSeg{src, off, count, 0, 0}; };
-    int64_t total = 0;
     if (STNERF_NET_IS_SPACE(kind)) {
         const bool ut = STNERF_NET_USES_TIME(kind), deep = STNERF_NET_IS_DEEP(kind);
         const SpaceLayout L = space_layout(ut, deep);
         const int nt = deep ? 12 : 10;
-        STNERF_REQUIRE(n_tensors == nt, "pack_net_device: this SpaceNet kind takes %d tensors, got %d", nt, n_tensors);
-        for (int i = 0; i < nt; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net_device: tensor %d is null", i);
-        total = L.total;
+        STNERF_REQUIRE(n_tensors == nt, "%s: this SpaceNet kind takes %d tensors, got %d", who, nt, n_tensors);
+        t.total = L.total;
         const int in_f[7] = {63, 256, 256, 256, 319, 256, 256};
         for (int i = 0; i < 7; ++i) {
             lin(W[i], 256, in_f[i], L.kq[i], L.w[i]);
@@ -174,9 +96,8 @@ extern "C" int stnerf_pack_net_device(int kind, const float* const* W, const flo
         cpy(B[nt - 1], 3, L.b_rgb2);
     } else if (kind == STNERF_NET_MOTION) {
         const MotionLayout L = motion_layout();
-        STNERF_REQUIRE(n_tensors == 6, "pack_net_device: MotionNet takes 6 tensors, got %d", n_tensors);
-        for (int i = 0; i < 6; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net_device: tensor %d is null", i);
-        total = L.total;
+        STNERF_REQUIRE(n_tensors == 6, "%s: MotionNet takes 6 tensors, got %d", who, n_tensors);
+        t.total = L.total;
         const int in_f[5] = {84, 128, 128, 128, 128};
         for (int i = 0; i < 5; ++i) {
             lin(W[i], 128, in_f[i], L.kq[i], L.w[i]);
@@ -185,12 +106,56 @@ extern "C" int stnerf_pack_net_device(int kind, const float* const* W, const flo
         cpy(W[5], 3 * 128, L.w_out);
         cpy(B[5], 3, L.b_out);
     } else {
-        set_error("pack_net_device: unknown net kind %d", kind);
+        set_error("%s: unknown net kind %d", who, kind);
         return STNERF_EINVAL;
     }
-    STNERF_REQUIRE(dst_bytes >= total * 4, "pack_net_device: dst too small");
-    // (the pads between the sections: the host packer zeroes the whole blob first)
-    if (hipMemsetAsync(dst_dev, 0, (size_t)total * 4, as_stream(stream)) != hipSuccess) return STNERF_ELAUNCH;
+    return STNERF_OK;
+}
+
+}  // namespace stnerf
+
+using namespace stnerf;
+
+extern "C" int64_t stnerf_packed_bytes(int kind) {
+    switch (kind) {
+        case STNERF_NET_SPACE: return space_layout(false).total * 4;
+        case STNERF_NET_SPACE_TIME: return space_layout(true).total * 4;
+        case STNERF_NET_SPACE_DEEP: return space_layout(false, true).total * 4;
+        case STNERF_NET_SPACE_TIME_DEEP: return space_layout(true, true).total * 4;
+        case STNERF_NET_MOTION: return motion_layout().total * 4;
+        default: set_error("packed_bytes: unknown net kind %d", kind); return STNERF_EINVAL;
+    }
+}
+
+// Host: tensors and destination in host memory.
+extern "C" int stnerf_pack_net(int kind, const float* const* W, const float* const* B, int n_tensors, void* dst_host,
+                               int64_t dst_bytes) {
+    STNERF_REQUIRE(W && B && dst_host, "pack_net: null pointer");
+    PackTable t;
+    if (const int rc = pack_table("pack_net", kind, W, B, n_tensors, t)) return rc;
+    STNERF_REQUIRE(dst_bytes >= t.total * 4, "pack_net: dst too small");
+    for (int i = 0; i < n_tensors; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net: tensor %d is null", i);
+    float* dst = static_cast<float*>(dst_host);
+    memset(dst, 0, (size_t)t.total * 4);   // (the pads between the sections)
+    for (int s = 0; s < t.count; ++s) {
+        const PackSeg& sg = t.seg[s];
+        const int64_t n = pack_seg_floats(sg);
+        for (int64_t i = 0; i < n; ++i) dst[sg.dst_off + i] = pack_element(sg, i);
+    }
+    return STNERF_OK;
+}
+
+// Device: the same blob from tensors that live in HBM -- what a training loop needs after every optimizer.step() (the host packer
+// costs a D2H of the weights, a CPU loop and an H2D per network: 165 ms per iteration for the eight networks of a C3 model against
+// 40 ms of kernels).  One launch per network.
+extern "C" int stnerf_pack_net_device(int kind, const float* const* W, const float* const* B, int n_tensors, void* dst_dev, int64_t dst_bytes,
+                                      stnerf_stream_t stream) {
+    STNERF_REQUIRE(W && B && dst_dev, "pack_net_device: null pointer");
+    PackTable t;
+    if (const int rc = pack_table("pack_net_device", kind, W, B, n_tensors, t)) return rc;
+    for (int i = 0; i < n_tensors; ++i) STNERF_REQUIRE(W[i] && B[i], "pack_net_device: tensor %d is null", i);
+    STNERF_REQUIRE(dst_bytes >= t.total * 4, "pack_net_device: dst too small");
+    if (hipMemsetAsync(dst_dev, 0, (size_t)t.total * 4, as_stream(stream)) != hipSuccess) return STNERF_ELAUNCH;
     hipLaunchKernelGGL(pack_net_device_kernel, dim3(64, t.count), dim3(256), 0, as_stream(stream), t, static_cast<float*>(dst_dev));
     STNERF_CHECK_LAUNCH("pack_net_device");
     return STNERF_OK;

@@ -3,6 +3,7 @@
 // Two arithmetics behind it, both in the sample-split organisation (a wave owns 32 samples, activations in registers):
 //   csrc/mlp_wave.hip    exact f32 (v_mfma_f32_32x32x2_f32)                       -- the default
 //   csrc/mlp_bf16x3.hip  split-bf16: three bf16 pieces per fp32 operand, six MFMAs -- STNERF_STAGE_BF16X3
+//                        (the machinery: mlp_bf16x3_core.h)
 // The op-level exact-f32 entries run the same arithmetic: stnerf_spacenet_fwd is the wave kernel on one layer without a queue,
 // stnerf_motionnet_fwd its MotionNet (motion_wave) in train_motion_fwd_kernel (mlp_wave_core.h).
 // Reference: modeling/layered_rfrender.py:340-418 (coarse), :495-576 (fine).

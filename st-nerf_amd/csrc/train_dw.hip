@@ -387,7 +387,7 @@ __device__ __forceinline__ void dwb_run(const DwwArgs& a, const DwbBundle& bd, c
 
 // ---- the 2 x 2 bundle in split-bf16 ("bf16x3", round 6): fp32-faithful products at the bf16 MFMA's rate -----------------------------
 // Both operands of dW = dY^T X are activations, so both are split on the fly: x = x0 + x1 + x2 (bf16 pieces, round-to-nearest of
-// the remainder: exact; csrc/mlp_bf16x3.hip's split8, 5.5 vector instructions per value) and a b ~ a0 b0 + a0 b1 + a1 b0 + a1 b1 +
+// the remainder: exact; csrc/mlp_bf16x3_core.h's split8, 5.5 vector instructions per value) and a b ~ a0 b0 + a0 b1 + a1 b0 + a1 b1 +
 // a0 b2 + a2 b0 on v_mfma_f32_32x32x16_bf16 (bf16 products are exact in fp32; dropped terms <= 2^-24 |a b|), into ONE accumulator per
 // block -- a dW sums thousands of samples: the f32 kernel rounds its running sum as often.  The instruction's contraction index is
 // 16 SAMPLES: lane (h, c) supplies samples 8 h .. 8 h + 7, so a ring slot (16 samples) is exactly one K step, and the lane's raw

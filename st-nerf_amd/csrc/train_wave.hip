@@ -13,8 +13,8 @@
 //                               values in both kernels), fetched at the start of an item; at every layer boundary the masked
 //                               gradient -- the pre-activation gradient d y_s the weight gradients need -- is written out once.
 //
-// (Round 6: both launches also exist in split bf16 -- csrc/mlp_bf16x3.hip: the stage kernel with a tap and train_space_dx_bx_kernel --
-// and that pair is what modeling/autograd.py runs unless the model was built for exact f32; the forward's entry point is here, the chain's
+// (Round 6: both launches also exist in split bf16 -- csrc/mlp_bf16x3.hip: the stage kernel with a tap; csrc/train_bf16x3.hip:
+// train_space_dx_bx_kernel -- and that pair is what modeling/autograd.py runs unless the model was built for exact f32; the forward's entry point is here, the chain's
 // beside its kernel.)
 //
 // The MotionNet's forward kernel (train_motion_fwd_kernel, mlp_wave_core.h) also runs the op-level stnerf_motionnet_fwd (stage_entry.hip).

@@ -225,7 +225,7 @@ class SpaceNetFunction(torch.autograd.Function):
             # ---- fused launches (csrc/train_wave.hip): the layers' inputs come from the forward itself (kept) or from one more run of
             # its stage kernel per chunk (recomputation); then the whole d x chain with the gradient carried in registers; only the
             # weight gradients and the encodings' chain rule stay per layer
-            # the d x chain in the forward's arithmetic: split bf16 (csrc/mlp_bf16x3.hip) or exact f32 (csrc/train_wave.hip)
+            # the d x chain in the forward's arithmetic: split bf16 (csrc/train_bf16x3.hip) or exact f32 (csrc/train_wave.hip)
             dx_bx = ctx.fwd_precision == "bf16x3" and DX_BF16X3
             if dx_bx:
                 dx_blob = dx_blob_bf16x3(m_, params, d_pos is not None)

@@ -1,9 +1,11 @@
-"""The bf16x3 packer (stnerf_pack_net_bf16x3, csrc/mlp_bf16x3.hip -- host code, no GPU): the blob it writes is decoded here
+"""The bf16x3 packer (stnerf_pack_net_bf16x3, csrc/pack_bf16x3.hip -- host code, no GPU): the blob it writes is decoded here
 with an independent numpy restatement of the layout in csrc/mlp_bf16x3.h and checked value by value:
   * the three bf16 pieces of every weight add up to the fp32 weight EXACTLY (8 + 8 + 8 significand bits), zero padding is zero;
   * every MFMA layer's weights sit where the kernel's K loops read them: [pass][K step][block of 32 outputs][piece][lane][8],
     K positions through the accumulator -> B-operand map of the hidden layers / the staged-encoding map of the first layers;
   * the consts section holds the bias vectors and head weights in the kernel's LDS order; the f32 section is the exact-f32 blob.
+The host entry executes the table of passes and the element function that the device entry (stnerf_pack_net_bf16x3_device) launches
+its kernel with, so the layout test here covers the table a training loop packs with; the f32 section likewise (csrc/pack.hip).
 Reference: modeling/spacenet.py:45-86 (layer list), modeling/motion_net.py:20-32."""
 import ctypes as C
 

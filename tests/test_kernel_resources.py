@@ -66,7 +66,8 @@ def test_wave_stage_kernel_vector_instruction_ceiling(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
 def test_bf16x3_stage_kernel_resources(tmp_path):
-    """csrc/mlp_bf16x3.hip: one wave per SIMD; (almost) no scratch traffic between the first and the last MFMA of a work
+    """csrc/mlp_bf16x3.hip (the stage kernel) and csrc/train_bf16x3.hip (the backward chain): one wave per SIMD; (almost) no
+    scratch traffic between the first and the last MFMA of a work
     item -- a reload there waits behind vmcnt(0), i.e. behind the weight ring's DMA queue, inside the K passes.  Tolerated:
     a few loop-invariant values reloaded in front of the first MFMA (the 1 / ns reciprocal of the row lookup ...), ONE
     reload in front of rgb_net.1's last slot (the ray index of the C-operand row, which waits for memory there anyway) and
@@ -102,10 +103,11 @@ def test_bf16x3_stage_kernel_resources(tmp_path):
             assert in_loop.count("global_store_dwordx4") == 9 * 16 + 8 + 1 and "buffer_store" not in in_loop, in_loop.count("global_store_dwordx4")
             assert "s_waitcnt vmcnt(24)" in in_loop      # the slot turns behind a boundary count its 18 stores in
     # ---- the backward chain (train_space_dx_bx_kernel<DPOS>): no scratch, no call, the ring structure, the masks' reads as asm
-    dx = re.findall(r"^(_ZN6stnerf24train_space_dx_bx_kernelILb[01]E\S*):", text, re.M)
+    dx_text = open(_compile("train_bf16x3.hip", tmp_path)).read()
+    dx = re.findall(r"^(_ZN6stnerf24train_space_dx_bx_kernelILb[01]E\S*):", dx_text, re.M)
     assert len(dx) == 2, dx
     for name in dx:
-        body = text[text.index(name + ":"):]
+        body = dx_text[dx_text.index(name + ":"):]
         body = body[:body.index("s_endpgm")]
         assert "scratch_" not in body and "s_swappc" not in body, name
         dpos = "ILb1E" in name
@@ -114,8 +116,8 @@ def test_bf16x3_stage_kernel_resources(tmp_path):
         assert body.count("v_mfma_f32_32x32x16_bf16") == 48 * slots, (name, body.count("v_mfma_f32_32x32x16_bf16"))
         # what drains the weight ring's DMA queue: the item's mask fetch (top of the item) and the kernel's end -- not the boundaries
         assert body.count("s_waitcnt vmcnt(0)") <= 3, body.count("s_waitcnt vmcnt(0)")
-    for name in kernels + dx:
-        tail = text[text.index(name + ":"):]
+    for name, source in [(k, text) for k in kernels] + [(k, dx_text) for k in dx]:
+        tail = source[source.index(name + ":"):]
         occ = int(re.search(r"; Occupancy: (\d+)", tail).group(1))
         scr = int(re.search(r"; ScratchSize: (\d+)", tail).group(1))
         assert occ == 1 and scr <= (0 if ("StoreTapArgs" in name or "dx_bx" in name) else 128), (name, occ, scr)

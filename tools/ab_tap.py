@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What the split-bf16 training forward's tap costs: the launch alone on 262,144 samples (STNERF_LIB selects a development build of
-csrc/mlp_bf16x3.hip with -DSTNERF_DEV_TAP_NO_STORES / -DSTNERF_DEV_TAP_NO_BITS; profiles/retired_designs.md).
+csrc/mlp_bf16x3.hip with -DSTNERF_DEV_TAP_NO_STORES / -DSTNERF_DEV_TAP_NO_BITS: STNERF_FLAGS_mlp_bf16x3=...; the backward chain's
+source is addressed as STNERF_FLAGS_train_bf16x3; profiles/retired_designs.md).
     STNERF_LIB=st-nerf_amd/libstnerf_hip_nostores.so python tools/ab_tap.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
