@@ -277,7 +277,7 @@ def aten_cpu_row_sum(x) -> "numpy.float32":
     vectors at every x86 capability level).  Rows of >= 8 elements: ``vectorized_inner_sum`` = ``row_sum`` over the full
     8-float vectors (4 interleaved accumulators, folded ((a0+a1)+a2)+a3; a cascade level folds the accumulators away
     every 16 rows), then a scalar chain over the leftover elements followed by the 8 vector lanes in order.  Shorter
-    rows: the scalar ``row_sum``.  The HIP resampler reproduces exactly this (csrc/render.hip); the oracle itself just
+    rows: the scalar ``row_sum``.  The HIP resampler reproduces exactly this (csrc/resample.hip); the oracle itself just
     calls torch.sum -- tests/test_host_cpu.py::test_aten_sum_order checks that the two agree on the running host."""
     import numpy as np
     f32 = np.float32

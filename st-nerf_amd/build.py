@@ -20,7 +20,8 @@ OBJDIR = os.path.join(PKG, "build" + ("_" + TAG if TAG else ""))
 SOURCES = [
     ("lib.hip", []),
     ("sampler.hip", ["-ffp-contract=off"]),
-    ("render.hip", ["-ffp-contract=off"]),
+    ("composite.hip", ["-ffp-contract=off"]),
+    ("resample.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

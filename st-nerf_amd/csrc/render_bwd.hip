@@ -14,25 +14,16 @@
 //   d alpha_k = gw_k T_k - (sum_{j>k} gw_j w_j) / om_k          (torch.cumprod's backward without zeros: reversed cumsum / input)
 //   d sigma_k = d alpha_k * delta_k e_k * [sigma' > 0] * f_k    (f: what the in-place density edits did to sigma: 0 where it
 //                                                                 was overwritten, sigma_scale where it was multiplied)
-// sigma' and f follow the forward's edit rules (csrc/render.hip, a10): modeling/layered_rfrender.py:414-422, :538-547, :564-566,
-// :575-576, and the fine stage's merged-only `t < near` cut (:605).
-#include <math.h>
-
-#include "common.h"
+// sigma' and f are the forward's edit rules (edit_sample in csrc/composite_rules.h, a10), and the fine stage's merged-only
+// `t < near` cut (modeling/layered_rfrender.py:605).  exp_neg and sigmoidf are the forward's own (csrc/wave_prims.h): the
+// recomputed alpha / sigmoid are the forward's bits.
+#include "composite_rules.h"
 
 namespace stnerf {
 namespace {
 
-__device__ __forceinline__ void bwd_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// the forward's exponential and sigmoid (csrc/render.hip): the recomputed alpha / sigmoid are the forward's own
-__device__ __forceinline__ float bwd_exp_neg(float x) { return __builtin_amdgcn_exp2f(x * -1.44269504088896340736f); }
-__device__ __forceinline__ float bwd_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + bwd_exp_neg(x)); }
-
-// inclusive scans over the 64 lanes (ds_bpermute shuffles: this kernel runs once per training step on a few thousand rays)
+// inclusive scans over the 64 lanes (ds_bpermute shuffles: this kernel runs once per training step on a few thousand rays; their
+// association order is part of this kernel's results, so they are not the forward's DPP scans)
 __device__ __forceinline__ float wave_incl_prod(float v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -70,40 +61,29 @@ __global__ void composite_bwd_kernel(CompositeBwdArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int LS = a.l * a.S;
     // per workgroup: the per-layer edit table; per wave: dacc[LS] float4 | T, om, gww, q, gw [LS] floats each
-    float* tab = reinterpret_cast<float*>(smem_raw);   // thr[16] | scale[16]
+    float* tab = reinterpret_cast<float*>(smem_raw);   // build_edit_table
     const int per_wave = (LS * 36 + 15) & ~15;          // (16-byte aligned regions: dacc is read and written as float4)
-    unsigned char* mine = smem_raw + 128 + (size_t)wave * per_wave;
+    unsigned char* mine = smem_raw + EDIT_TAB_BYTES + (size_t)wave * per_wave;
     float4* dacc = reinterpret_cast<float4*>(mine);
     float* sT = reinterpret_cast<float*>(mine + (size_t)LS * 16);
     float* sOm = sT + LS;
     float* sGww = sOm + LS;
     float* sQ = sGww + LS;
     float* sGw = sQ + LS;
-    if (threadIdx.x < STNERF_MAX_LAYERS) {
-        tab[threadIdx.x] = a.p.use_threshold[threadIdx.x] != 0 ? a.p.threshold[threadIdx.x] : -INFINITY;
-        tab[16 + threadIdx.x] = a.p.sigma_scale[threadIdx.x];
-    }
+    build_edit_table(tab, a.p, a.l);
     __syncthreads();
     const bool fine = a.p.fine != 0;
     const bool cut_neg_on = !fine && a.p.cut_negative_t != 0;
     const float nearv = a.p.near, border = a.p.border;
-    unsigned ev1 = 0, ev2 = 0;
-    for (int i = 0; i < a.l; ++i) {
-        if (a.p.evaluated[i] == 2) ev2 |= 1u << i;
-        else if (a.p.evaluated[i] != 0) ev1 |= 1u << i;
-    }
+    const EvalBits ev = eval_bits<false>(a.p, a.l);
     const int64_t rays_per_iter = (int64_t)gridDim.x * a.waves_per_block;
     for (int64_t ray = (int64_t)blockIdx.x * a.waves_per_block + wave; ray < a.n; ray += rays_per_iter) {
-        unsigned mask_bits = 0xffffu;
-        if (a.mask) {
-            const int v = lane < a.l ? a.mask[ray * a.l + lane] : 0;
-            mask_bits = (unsigned)__ballot((v & 1) != 0);
-        }
-        const unsigned have_m = ev2 | (ev1 & mask_bits);   // layers whose raw outputs this ray's composites read
+        const int mv = (a.mask && lane < a.l) ? a.mask[ray * a.l + lane] : 0;
+        const unsigned have_m = have_layers(ev, a.mask != nullptr, (unsigned)__ballot((mv & 1) != 0));   // layers whose raw outputs this ray's composites read
         const float* tr = a.t + ray * LS;
         const float4* rr = a.raw + ray * LS;
         for (int e = lane; e < LS; e += 64) dacc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-        bwd_wave_sync();
+        wave_sync();
         // streams 0 .. l-1: the layers' own composites; stream l: the merged one
         for (int stream = 0; stream <= a.l; ++stream) {
             const bool merged = stream == a.l;
@@ -131,20 +111,13 @@ __global__ void composite_bwd_kernel(CompositeBwdArgs a) {
                     have = (have_m >> layer & 1u) != 0;
                     float v = 0.f, f = 0.f;
                     if (have) {
-                        const float4 r = rr[src];
-                        v = r.w;
-                        f = 1.f;
-                        if (cut_neg_on && layer > 0 && tm < 0.f) { v = 0.f; f = 0.f; }              // :414
-                        if (v < tab[layer]) { v = 0.f; f = 0.f; }                                   // :416-418, :538-547, :564-566
-                        v = v * tab[16 + layer];                                                    // :575-576
-                        f = f * tab[16 + layer];
-                        if (!fine && layer == 0 && tm < nearv) { v = 0.f; f = 0.f; }                // :422
+                        sg = edit_sample(rr[src], tm, cut_neg_on && layer > 0, tab[layer], tab[16 + layer], !fine && layer == 0, nearv,
+                                         a.p.rgb_activated != 0, &f);
+                        v = sg.w;
                         if (merged && fine && tm < nearv) { v = 0.f; f = 0.f; }                     // :605
-                        if (a.p.rgb_activated) sg = make_float4(r.x, r.y, r.z, 0.f);
-                        else sg = make_float4(bwd_sigmoid(r.x), bwd_sigmoid(r.y), bwd_sigmoid(r.z), 0.f);
                     }
                     const float s = fmaxf(v, 0.f);
-                    const float ex = bwd_exp_neg(s * delta);
+                    const float ex = exp_neg(s * delta);
                     alpha = 1.f - ex;
                     om = (1.f - alpha) + 1e-10f;
                     q = v > 0.f ? delta * ex * f : 0.f;
@@ -177,7 +150,7 @@ __global__ void composite_bwd_kernel(CompositeBwdArgs a) {
                     }
                 }
             }
-            bwd_wave_sync();
+            wave_sync();
             // ---- back to front: the suffix sum of gw w behind every sample, d alpha, d sigma
             float tail = 0.f;
             for (int m0 = ((ns - 1) / 64) * 64; m0 >= 0; m0 -= 64) {
@@ -196,11 +169,11 @@ __global__ void composite_bwd_kernel(CompositeBwdArgs a) {
                     }
                 }
             }
-            bwd_wave_sync();
+            wave_sync();
         }
         float4* dr = a.d_raw + ray * LS;
         for (int e = lane; e < LS; e += 64) dr[e] = dacc[e];
-        bwd_wave_sync();
+        wave_sync();
     }
 }
 
@@ -218,11 +191,11 @@ extern "C" int stnerf_composite_bwd(const float* t, const float* raw, const uint
     STNERF_REQUIRE(!g_mixed || order, "composite_bwd: the merged composite's gradient needs the forward's `order`");
     if (n == 0) return STNERF_OK;
     const int64_t per_wave = ((int64_t)l * S * 36 + 15) & ~(int64_t)15;   // (as in the kernel: rounded up to 16 bytes)
-    STNERF_REQUIRE(per_wave + 128 <= 160 * 1024 - 1024, "composite_bwd: %d samples per ray need %lld B of LDS per wave", l * S,
+    STNERF_REQUIRE(per_wave + EDIT_TAB_BYTES <= 160 * 1024 - 1024, "composite_bwd: %d samples per ray need %lld B of LDS per wave", l * S,
                    (long long)per_wave);
-    int wpb = (int)((64 * 1024 - 128) / per_wave);
+    int wpb = (int)((64 * 1024 - EDIT_TAB_BYTES) / per_wave);
     wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
-    const int lds = (int)(128 + wpb * per_wave);
+    const int lds = (int)(EDIT_TAB_BYTES + wpb * per_wave);
     if (lds > 64 * 1024)
         if (const int rc = reserve_dynamic_lds(reinterpret_cast<const void*>(composite_bwd_kernel), lds, "composite_bwd")) return rc;
     CompositeBwdArgs a{t, reinterpret_cast<const float4*>(raw), mask, order, g_layer, g_mixed, reinterpret_cast<float4*>(d_raw), n, l, S, wpb,

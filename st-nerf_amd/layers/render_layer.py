@@ -1,5 +1,5 @@
 """``gen_weight`` / ``VolumeRenderer`` with the reference's signatures (layers/render_layer.py:8-58), computed by
-the wave-scan compositor (csrc/render.hip: ``stnerf_gen_weight`` / ``stnerf_composite``)."""
+the wave-scan compositor (csrc/composite.hip: ``stnerf_gen_weight`` / ``stnerf_composite``)."""
 from __future__ import annotations
 
 import torch

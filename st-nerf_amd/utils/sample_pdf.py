@@ -1,5 +1,5 @@
 """Inverse-CDF importance resampling with the reference's signature (utils/sample_pdf.py:18-63), computed by the
-wave-scan resampler (csrc/render.hip: ``stnerf_resample``)."""
+wave-scan resampler (csrc/resample.hip: ``stnerf_resample``)."""
 import itertools
 
 import numpy as np

@@ -276,7 +276,7 @@ def test_split_bf16_training_entries_check_their_arguments_on_the_host(lib):
 
 
 def test_composite_launch_plan(lib):
-    """stnerf_composite_plan: the sizing arithmetic of the compositor's launches (render.hip: plan_composite) on the CPU.
+    """stnerf_composite_plan: the sizing arithmetic of the compositor's launches (composite.hip: plan_composite) on the CPU.
     Every BASELINE shape takes the register / insertion-merge kernels; the single-layer pre-pass needs scratch; a merged
     list of all nine 192-sample layers would cost occupancy, so with scratch there are two launches and the first holds
     four layers; the `order` output and layers of more than 192 samples take the LDS-staged kernel; nothing plans more than

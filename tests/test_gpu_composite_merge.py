@@ -1,4 +1,4 @@
-"""The production compositor (csrc/render.hip: composite_single_kernel + composite_merge_kernel -- layers in registers,
+"""The production compositor (csrc/composite.hip: composite_single_kernel + composite_merge_kernel -- layers in registers,
 merged order built by inserting one layer at a time) against
   * the LDS-staged kernel (the `order` parity call still takes it): same merged order, same lanes, same arithmetic ->
     bit-identical images and weights, at every BASELINE shape (3 x 64 / 3 x 128, 5 x 128, 9 x 128 / 9 x 192) and at ragged

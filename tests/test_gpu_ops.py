@@ -451,7 +451,7 @@ def test_composite_descending_and_unsorted_layers(ops):
 @pytest.mark.parametrize("fine", [False, True])
 def test_composite_production_shortcuts_are_bitwise_neutral(ops, fine):
     """Without the `order` output the kernel drops layers a ray misses and reuses a single live layer's composite as the
-    mix (render.hip); with `order` it merges everything.  Same inputs -> bit-identical images and weights."""
+    mix (composite.hip); with `order` it merges everything.  Same inputs -> bit-identical images and weights."""
     torch.manual_seed(29 + fine)
     n, l, S = 4000, 3, 96
     t = torch.sort(torch.rand(n, l, S) * 6.0 - 0.3, -1)[0]

@@ -146,7 +146,7 @@ def test_ssim_restatement():
 @pytest.mark.parametrize("n", [1, 3, 6, 7, 8, 10, 14, 15, 16, 30, 62, 88, 126, 190, 254, 600, 1100])
 def test_aten_sum_order(n):
     """torch.sum over the last dim of a contiguous fp32 (rows, n) tensor == the order the resampler reproduces on the
-    device (csrc/render.hip: aten_cpu_row_sum; restated in numpy as oracle.aten_cpu_row_sum): 8-float vectors x 4
+    device (csrc/resample.hip: aten_cpu_row_sum; restated in numpy as oracle.aten_cpu_row_sum): 8-float vectors x 4
     interleaved accumulators, whatever the host's SIMD level.  If a torch upgrade changes ATen's reduction order this
     fails here, on the CPU, before any GPU parity test does."""
     torch.manual_seed(n)

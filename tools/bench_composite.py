@@ -2,7 +2,7 @@
 """Compositor alone at the BASELINE shapes (GPU box): ms per call and algorithmic TB/s, production kernels
 (composite_single_kernel + composite_merge_kernel) or, with STNERF_COMPOSITE_KERNEL=staged, the LDS-staged kernel.
 
-    python tools/bench_composite.py [rays]
+    python tools/bench_composite.py [rays [timed calls]]      (rays 0: the default count per case; timed calls: default 5)
 
 Depth lists as the sampler leaves them (ascending inside each layer's interval, -1000 on the rays a layer misses); `hit`
 is the probability that a ray crosses a performer's box (the taekwondo / walking views: ~0.4 of the rays cross any; the
@@ -49,6 +49,7 @@ def make(n, l, S, pattern, seed=0):
 
 def main():
     n_arg = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+    iters = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     which = os.environ.get("STNERF_COMPOSITE_KERNEL", "merge")
     only = os.environ.get("CASES")
     for name, l, S, fine, pattern in CASES:
@@ -62,7 +63,6 @@ def main():
             ops.composite(t, raw, mask, **kw)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        iters = 5
         e0.record()
         for _ in range(iters):
             ops.composite(t, raw, mask, **kw)
