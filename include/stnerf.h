@@ -49,7 +49,8 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
 /* Launch profiler: between _begin and _end every kernel launch of the entry points below is bracketed by a
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
- * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse; kind: the net kind for 0/1;
+ * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw; kind: the net kind
+ * for 0/1, to_dense for 6;
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
  * tag: the layer a stnerf_render_rays launch belongs to (-1 otherwise); bytes_per_ray: algorithmic HBM bytes
  * per ray for the HBM-bound kernels (2..4), 0 for the networks. */
@@ -522,6 +523,37 @@ int stnerf_render_rays(const float* rays, int64_t n, const float* boxes, int64_t
                        const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                        float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                        stnerf_stream_t stream);
+
+/* One layer's slice of the ray-major network outputs raw[n][l][ns][4] <-> a dense buffer dense[n][ns][4]: to_dense != 0 copies
+ * raw[:, layer] out, to_dense == 0 copies it back in (the other layers' slices are not touched).  16 bytes per sample and lane;
+ * both pointers 16-byte aligned.  HBM-bound: 32 ns bytes of traffic per ray. */
+int stnerf_copy_layer_raw(float* raw, int64_t n, int l, int layer, int ns, float* dense, int to_dense, stnerf_stream_t stream);
+
+/* The background layer's network outputs of a fixed view, kept by the caller across frames.  While the rays, the background box
+ * and edit, the seed, the sample counts, the arithmetic and the background networks (and, where it takes one, its frame id) stay
+ * what they were, layer 0's raw outputs of both stages are the same bits in every frame whatever the performers do: their frame
+ * ids, boxes, edits and shown flags, alpha and the density thresholds act on other layers or after the networks.  The CALLER
+ * decides when that holds (stnerf_amd.BackgroundCache keys it on the host); the library only moves the data.
+ *   raw_coarse[n][n1][4], raw_fine[n][n1+n2][4] (unused with only_coarse, may be NULL then): dense fp32, 16-byte aligned, exactly
+ *   what the stage kernels stored for layer 0 (before any density edit).
+ *   mode STNERF_BKGD_CACHE_OFF: as without a cache; _CAPTURE: render as usual and copy layer 0's slices out; _REUSE: leave layer 0
+ *   out of both network stages and copy the slices in.  Everything else (sampler, compaction, compositor, resampler) runs for every
+ *   layer in every mode, so a _REUSE frame is bit-identical to the frame rendered without a cache. */
+#define STNERF_BKGD_CACHE_OFF 0
+#define STNERF_BKGD_CACHE_CAPTURE 1
+#define STNERF_BKGD_CACHE_REUSE 2
+typedef struct stnerf_bkgd_cache {
+    float* raw_coarse;
+    float* raw_fine;
+    int32_t mode;
+} stnerf_bkgd_cache;
+/* stnerf_render_rays with a background cache (NULL: none; stnerf_render_rays forwards here with NULL).  The cache arguments are
+ * checked on the host before anything is launched. */
+int stnerf_render_rays_cached(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                              const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                              const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                              float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                              const stnerf_bkgd_cache* cache_host, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

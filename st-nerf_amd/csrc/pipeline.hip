@@ -1,4 +1,4 @@
-// stnerf_render_rays: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -161,11 +161,67 @@ static int motion_rows(const stnerf_nets* nets, const stnerf_render_params* p, c
     return rc;
 }
 
+// ---- the background cache (include/stnerf.h: stnerf_bkgd_cache).  One layer's slice of raw[n][l][ns][4] <-> dense[n][ns][4]: a lane
+// moves one 16-byte sample, four independent samples in flight per lane and trip; the dense side is coalesced, the strided side
+// runs of ns x 16 bytes.  64-bit flat index (a 1080p view at 64 + 64 samples has 2.7e8 samples, 4.2 GB, per layer).
+template <bool TO_DENSE>
+static __global__ void __launch_bounds__(256) copy_layer_raw_kernel(float4* __restrict__ raw, float4* __restrict__ dense, int64_t total,
+                                                                    int l, int layer, int ns) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += 4 * stride) {
+        float4 v[4];
+        int64_t at[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t i = i0 + j * stride;
+            const int64_t ray = i / ns;
+            at[j] = (ray * l + layer) * ns + (i - ray * ns);
+            if (i < total) v[j] = TO_DENSE ? raw[at[j]] : dense[i];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t i = i0 + j * stride;
+            if (i < total) (TO_DENSE ? dense[i] : raw[at[j]]) = v[j];
+        }
+    }
+}
+
+extern "C" int stnerf_copy_layer_raw(float* raw, int64_t n, int l, int layer, int ns, float* dense, int to_dense,
+                                     stnerf_stream_t stream) {
+    STNERF_REQUIRE(raw && dense, "copy_layer_raw: null pointer");
+    STNERF_REQUIRE(n >= 0 && l >= 1 && l <= STNERF_MAX_LAYERS && layer >= 0 && layer < l && ns >= 1, "copy_layer_raw: bad shape");
+    STNERF_REQUIRE((((uintptr_t)raw | (uintptr_t)dense) & 15) == 0, "copy_layer_raw: raw and dense must be 16-byte aligned");
+    const int64_t total = n * ns;
+    if (total == 0) return STNERF_OK;
+    // memory-bound: at most 8 workgroups per CU's worth of blocks, the rest by the grid-stride loop
+    const int64_t blocks = (total + 1023) / 1024;
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048));
+    hipStream_t st = as_stream(stream);
+    LaunchTimer timer(PROF_COPY_LAYER_RAW, to_dense ? 1 : 0, n, ns, 32 * (int64_t)ns, st);
+    if (to_dense)
+        hipLaunchKernelGGL(copy_layer_raw_kernel<true>, grid, dim3(256), 0, st, reinterpret_cast<float4*>(raw),
+                           reinterpret_cast<float4*>(dense), total, l, layer, ns);
+    else
+        hipLaunchKernelGGL(copy_layer_raw_kernel<false>, grid, dim3(256), 0, st, reinterpret_cast<float4*>(raw),
+                           reinterpret_cast<float4*>(dense), total, l, layer, ns);
+    STNERF_CHECK_LAUNCH("copy_layer_raw");
+    return STNERF_OK;
+}
+
 extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
                                   const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
                                   const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                                   float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                   stnerf_stream_t stream) {
+    return stnerf_render_rays_cached(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                     mixed_coarse, layer_fine, layer_coarse, mask, nullptr, stream);
+}
+
+extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                         const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                         const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                         float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                         const stnerf_bkgd_cache* cache, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -186,6 +242,16 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
     const int64_t need = stnerf_render_workspace_bytes(n, l, n1, n2, p->only_coarse);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
+    const int cache_mode = cache ? cache->mode : STNERF_BKGD_CACHE_OFF;
+    STNERF_REQUIRE(cache_mode == STNERF_BKGD_CACHE_OFF || cache_mode == STNERF_BKGD_CACHE_CAPTURE || cache_mode == STNERF_BKGD_CACHE_REUSE,
+                   "render_rays: unknown background cache mode %d", cache_mode);
+    if (cache_mode != STNERF_BKGD_CACHE_OFF) {
+        STNERF_REQUIRE(cache->raw_coarse, "render_rays: background cache without raw_coarse");
+        STNERF_REQUIRE(p->only_coarse || cache->raw_fine, "render_rays: background cache without raw_fine (required unless only_coarse)");
+        STNERF_REQUIRE(((uintptr_t)cache->raw_coarse & 15) == 0 && (p->only_coarse || ((uintptr_t)cache->raw_fine & 15) == 0),
+                       "render_rays: background cache buffers must be 16-byte aligned");
+    }
+    const bool cached = cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
     if (n == 0) return STNERF_OK;
 
     const Plan pl = make_plan(n, l, n1, n2, p->only_coarse);
@@ -240,7 +306,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
             stnerf_stage_layer sl[STNERF_MAX_LAYERS];
             int ns_l = 0;
             for (int pass = 0; pass < 2; ++pass) {
-                for (int i = 0; i < l; ++i) {
+                for (int i = cached ? 1 : 0; i < l; ++i) {
                     if (i > 0 && !p->shown[i]) continue;
                     const bool deform = i == 0 ? p->bkgd_use_deform_time != 0 : p->use_deform_time != 0;
                     if ((pass == 0) != deform) continue;
@@ -257,6 +323,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
                 }
             }
+            if (ns_l == 0) return STNERF_OK;   // (background from the cache, no performer shown: nothing to evaluate)
             set_launch_tag(fine ? 1 : 0);
             const int r2 = stnerf_mlp_stage(sl, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
                                             (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
@@ -266,7 +333,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
         }
         // precision 2: one launch per network through the op-level entries -- the same exact-f32 wave arithmetic, scheduled
         // network by network (the deformed points go back to xyz in between)
-        for (int i = 0; i < l; ++i) {
+        for (int i = cached ? 1 : 0; i < l; ++i) {
             if (i == 0 ? !p->bkgd_use_deform_time : !p->use_deform_time) continue;
             if (i > 0 && !p->shown[i]) continue;  // a hidden layer's points are never consumed
             set_launch_tag(i);
@@ -280,7 +347,7 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                                                       rs, nullptr, 0, flags, stream);
             if (r2) return r2;
         }
-        for (int i = 0; i < l; ++i) {
+        for (int i = cached ? 1 : 0; i < l; ++i) {
             if (i > 0 && !p->shown[i]) continue;
             set_launch_tag(i);
             const void* net = i == 0 ? (fine ? nets->bkgd_fine : nets->bkgd) : (fine ? nets->space_fine[i] : nets->space[i]);
@@ -302,7 +369,18 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
         rc = motion_rows(nets, p, rays, n, i, n1, n1, xyz_c, ray_list, ray_count, nullptr, 0, motion_queue + 2 * i, st);
         if (rc) return rc;
     }
-    rc = stage(xyz_c, raw_c, n1, false, reuse);
+    // The stage followed by the background cache's copy of layer 0's slice: out of `raw` after a capture frame's stage, into it
+    // in place of the stage's layer-0 items in a reuse frame.
+    auto stage_and_cache = [&](float* xyz, float* raw, int ns, bool fine, float* kept) -> int {
+        const int r2 = stage(xyz, raw, ns, fine, reuse);
+        if (r2 || cache_mode == STNERF_BKGD_CACHE_OFF) return r2;
+        set_launch_tag(0);
+        const int r3 = stnerf_copy_layer_raw(raw, n, l, 0, ns, kept, cache_mode == STNERF_BKGD_CACHE_CAPTURE, stream);
+        set_launch_tag(-1);
+        return r3;
+    };
+    // (raw_f lies over the whole coarse block: the coarse slice is copied here, before the compositor reads raw_c)
+    rc = stage_and_cache(xyz_c, raw_c, n1, false, cache ? cache->raw_coarse : nullptr);
     if (rc) return rc;
 
     // ---- coarse: density edits, per-layer + merged composite (:414-448)
@@ -338,7 +416,8 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
         rc = motion_rows(nets, p, rays, n, i, n2, S, xyz_f, ray_list, ray_count, slots, n2, motion_queue + 2 * i + 1, st);
         if (rc) return rc;
     }
-    rc = stage(xyz_f, raw_f, S, true, reuse);
+    // (the cached fine slice lands on t_c / xyz_c: after the MotionNet reuse launches above have read them)
+    rc = stage_and_cache(xyz_f, raw_f, S, true, cache ? cache->raw_fine : nullptr);
     if (rc) return rc;
     cp.fine = 1;
     cp.cut_negative_t = 0;

@@ -150,6 +150,10 @@ def _device_rays_by_pose_and_K(self, T, K, layer_frame_pair):
             frame_ids[layer_id] = float(frame_id)
     rays = ops.generate_rays(torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(T, dtype=torch.float32),
                              self.height, self.width, frame_ids=frame_ids)
+    # the rays of a whole view, made here from its camera: they carry the view's key, which lets a model with a background cache
+    # attached (LayeredRFRender.set_background_cache) serve the reference's own render_pose -> layered_batchify_ray call
+    from stnerf_amd.bkgd_cache import tag_view_rays
+    tag_view_rays(rays, K, T, self.height, self.width, frame_ids)
     n, dev = rays.shape[0], rays.device
     near_fars = self.near_far.to(dev).expand(n, 2)
     return rays, torch.zeros(1, device=dev).expand(n), torch.zeros(1, 8, 3, device=dev).expand(n, 8, 3), near_fars

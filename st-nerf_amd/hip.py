@@ -58,6 +58,12 @@ class RenderParams(C.Structure):
                 ("edits_fine", LayerEdit * MAX_LAYERS), ("pivot", C.c_float * 3)]
 
 
+class BkgdCache(C.Structure):
+    """stnerf_bkgd_cache (include/stnerf.h): layer 0's dense raw outputs of a launch piece and what to do with them."""
+    _fields_ = [("raw_coarse", C.c_void_p), ("raw_fine", C.c_void_p), ("mode", C.c_int32)]
+
+
+BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
 
 
@@ -142,6 +148,10 @@ _PROTOS = {
     "stnerf_render_workspace_bytes": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "stnerf_render_rays": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
                                      C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
+    "stnerf_render_rays_cached": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                            C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                            C.c_void_p]),
+    "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,
                                   C.c_void_p, c_f32p, C.c_void_p]),

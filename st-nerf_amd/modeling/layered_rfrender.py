@@ -101,6 +101,11 @@ class LayeredRFRender(nn.Module):
                                            # consumes: mixed + per-layer fine images, masks), "final" (the two mixed images);
                                            # entries that are not gathered come back as None
         self.shard_group = None            # the process group to shard over (None: the default group)
+        self._bkgd_cache = None            # stnerf_amd.BackgroundCache or None (set_background_cache)
+        self.view_key = None               # (view identity, background frame id) of the rays in flight (stnerf_amd.bkgd_cache.view_key),
+                                           # set and restored around a call by whoever generated the rays from a camera
+                                           # (stnerf_amd.parallel.render_view / render_view_share); None: rays of unknown origin,
+                                           # never cached
 
     FRESH_DRAWS_DEFAULT = False   # what a new model's fresh_draws_per_call starts as (dropin.patch_reference: True)
     SHARD_VIEWS_DEFAULT = False   # what a new model's shard_views starts as (the dropin launcher under torch.distributed.run: True)
@@ -115,6 +120,58 @@ class LayeredRFRender(nn.Module):
             if isinstance(m, (SpaceNet, MotionNet)):
                 m.precision = precision
         return self
+
+    def set_background_cache(self, cache):
+        """Attach a ``stnerf_amd.BackgroundCache`` (None: detach).  While one is attached, frames of a view whose camera the
+        caller names (``view_key``: ``stnerf_amd.parallel.render_view`` / ``render_view_share``, so ``render_pose`` and the
+        renderer's ``render_path``) evaluate the background networks once and later take their raw outputs from the cache as long
+        as ``background_cache_key`` stays the same -- bit-identical frames, about half the network work on a two-performer scene.
+        Calls with caller-made rays (``forward``, ``render_rays``), ``replay``, the training path and the per-sample background
+        time path are never cached.
+
+        While a cache is attached ``advance_seed()`` is a no-op: a cached run uses ONE jitter pattern for all its frames, also
+        with ``fresh_draws_per_call`` (what ``dropin.patch_reference`` switches on) -- fresh draws per frame would change every
+        background sample and nothing could be reused.  Detaching restores the per-call advance."""
+        self._bkgd_cache = cache
+        return self
+
+    def background_cache_key(self, view_key, piece, window, retiming, only_coarse, pivot=None):
+        """(group, piece): the key of a launch piece's background outputs -- host arithmetic only.  The group covers every input
+        of layer 0's raw outputs: the view (camera, h, w), the seed, n1 / n2 / only_coarse, the arithmetic and its schedule, the
+        ray format, the EDITED background box and layer 0's point un-edit (coarse and fine, with the pivot they use), near and
+        border, the background model flags, the parameter versions of the background networks and -- only where
+        BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME make it an input -- the background's frame id.  The piece part is the ray
+        range and its ray window.  Deliberately absent: performer frame ids, boxes, edits and shown flags, alpha and the two
+        density thresholds -- they act on other layers or after the networks, and a sweep over them must hit."""
+        from stnerf_amd.modeling._packed import _params_fingerprint
+        view, bkgd_frame = view_key
+        l = self.layer_num + 1
+        timed = self.bkgd_use_deform_time or (self.bkgd_use_space_time and self.use_space_time)
+        bk = self.bkgd_bbox
+        host = getattr(self, "_bkgd_bbox_host", None)          # (one D2H per box version, not per frame)
+        if host is None or host[0] is not bk or host[1] != bk._version:
+            host = self._bkgd_bbox_host = (bk, bk._version, bk.detach().cpu().float().clone())
+        box0 = host[2].clone()
+        if self.scale is not None and pivot is None:
+            pivot = self._pivot()
+        if self.scale is not None and len(self.scale) > 0:
+            box0 = (box0 - pivot) * self.scale[0] + pivot
+        if self.shift is not None and len(self.shift) > 0 and self.shift[0] is not None:
+            box0 = box0 + torch.tensor(self.shift[0], dtype=torch.float32)
+        def edit0(fine):
+            e = self._point_edits(l, fine)
+            if e is None:
+                return None
+            sh, sc = e[0]
+            return (None if sh is None else tuple(float(x) for x in sh), None if sc is None else float(sc))
+        nets = [self.bkgd_spacenet, self.bkgd_spacenet_fine] + ([self.bkgd_time_deform_net] if self.bkgd_use_deform_time else [])
+        prec = self.bkgd_spacenet.precision
+        group = (view, int(self.seed) & 0xFFFFFFFFFFFFFFFF, int(self.coarse_ray_sample), int(self.fine_ray_sample), bool(only_coarse),
+                 prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), box0.numpy().tobytes(), edit0(False), edit0(True),
+                 None if pivot is None else tuple(float(x) for x in pivot.tolist()), float(self.near), float(self.boarder_weight),
+                 (bool(self.bkgd_use_deform_time), bool(self.bkgd_use_space_time), bool(self.use_space_time), bool(self.deep_rgb)),
+                 tuple(_params_fingerprint(m) for m in nets), bkgd_frame if timed else None)
+        return group, (int(piece[0]), int(piece[1]), tuple(int(x) for x in window))
 
     # ---- reference API -----------------------------------------------------------------------
     def hide_layer(self, layer_id):
@@ -224,9 +281,10 @@ class LayeredRFRender(nn.Module):
             ops.spacenet_fwd(nets[i - 1]._packed("fp32"), xyz[:, i], rays[:, 3:6], tm, raw[:, i], ray_list=lst[i],
                              ray_count=cnt[i:i + 1])
 
-    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay):
+    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
-        (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3)."""
+        (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
+        the call's ray tensor when the background cache may serve it (a view key is set), else None."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.layer_num + 1
         p = hip.RenderParams()
@@ -269,8 +327,23 @@ class LayeredRFRender(nn.Module):
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != rays.device:
             self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=rays.device)
-        return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
-                               u=(replay.get("u") if replay else None))
+        cache, key, cache_arg = self._bkgd_cache, None, None
+        if piece is not None and cache is not None:
+            # the background's raw outputs of this piece: from the cache (hit), into it (miss with room), or neither (over budget)
+            key = self.background_cache_key(self.view_key, piece, window, retiming, only_coarse, pivot)
+            entry = cache.lookup(key)
+            mode = hip.BKGD_CACHE_REUSE
+            if entry is None:
+                entry, mode = cache.reserve(key, n, p.n1, p.n2, only_coarse, rays.device), hip.BKGD_CACHE_CAPTURE
+            if entry is not None:
+                cache_arg = (entry[0], entry[1], mode)
+        try:
+            return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
+                                   u=(replay.get("u") if replay else None), cache=cache_arg)
+        except Exception:
+            if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
+                cache.discard(key)             # (never filled)
+            raise
 
     def render_rays(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
                     ref_chunk: Optional[int] = None):
@@ -303,8 +376,9 @@ class LayeredRFRender(nn.Module):
 
     def advance_seed(self):
         """What a finished call does to ``seed`` (``fresh_draws_per_call``; a rank that owns no ray of a sharded view
-        calls this too, so that every rank's stream stays the same)."""
-        if self.fresh_draws_per_call and self.replay is None:
+        calls this too, so that every rank's stream stays the same).  A no-op while a background cache is attached
+        (``set_background_cache``: one jitter pattern for all the frames of a cached run)."""
+        if self.fresh_draws_per_call and self.replay is None and getattr(self, "_bkgd_cache", None) is None:
             self.seed = (int(self.seed) + 1) & 0xFFFFFFFFFFFFFFFF   # the next call draws new jitter / resampling numbers
 
     def render_rays_raw(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
@@ -365,6 +439,9 @@ class LayeredRFRender(nn.Module):
                 raise ValueError("a striped ray window needs chunk groups that start on a stripe boundary "
                                  "(frame ids that change inside the view: render it unstriped)")
         window_at = (lambda s: (first + s, 0, 0)) if stripe <= 0 else (lambda s: (first + s // stripe * period, stripe, period))
+        # the background cache serves calls whose view is known on the host (view_key) and whose draws are the device RNG's
+        cacheable = (getattr(self, "_bkgd_cache", None) is not None and getattr(self, "view_key", None) is not None
+                     and self.replay is None and not train and not per_sample_bkgd_time)
         for (g0, g1, boxes, pivot) in groups:
             for s in range(g0, g1, cap):
                 e = min(s + cap, g1)
@@ -381,8 +458,9 @@ class LayeredRFRender(nn.Module):
                     outs.append(render_rays_train(self, rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
                                                   bkgd_density_threshold, window_at(s), rp))
                 else:
+                    # (the piece travels only when the cache may serve it: uncached, the call is the nine-argument one it always was)
                     outs.append(self._render_launch(rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
-                                                    bkgd_density_threshold, window_at(s), rp))
+                                                    bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ())))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range(5))
         self.advance_seed()

@@ -277,7 +277,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
     return pack_net(hip.NET_MOTION, ws, bs, device, precision)
 
 
-PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage")
+PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw")
 
 
 def profile_begin() -> None:
@@ -533,10 +533,24 @@ def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool) 
     return int(nb)
 
 
+def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Tensor:
+    """One layer's slice of the ray-major network outputs raw (n,l,ns,4) <-> dense (n,ns,4) (stnerf_copy_layer_raw): ``to_dense``
+    copies ``raw[:, layer]`` into ``dense``, otherwise ``dense`` into ``raw[:, layer]`` (the other layers stay as they are).
+    Returns the tensor written."""
+    if raw.dim() != 4 or raw.shape[3] != 4 or tuple(dense.shape) != (raw.shape[0], raw.shape[2], 4):
+        raise ValueError(f"copy_layer_raw: raw must be (n,l,ns,4) and dense (n,ns,4), got {tuple(raw.shape)} and {tuple(dense.shape)}")
+    n, l, ns = raw.shape[0], raw.shape[1], raw.shape[2]
+    hip.check(hip.lib().stnerf_copy_layer_raw(hip.dptr(raw, name="raw"), n, l, int(layer), ns, hip.dptr(dense, name="dense"),
+                                              int(bool(to_dense)), hip.stream_ptr()), "stnerf_copy_layer_raw")
+    return dense if to_dense else raw
+
+
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
-                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None):
+                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
-    layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse)."""
+    layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
+    ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
+    (stnerf_render_rays_cached; mode hip.BKGD_CACHE_CAPTURE fills the two tensors, hip.BKGD_CACHE_REUSE renders from them)."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -550,11 +564,19 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     else:
         mix_f = torch.empty(n, 5, dtype=torch.float32, device=dev)
         lo_f = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
-    hip.check(hip.lib().stnerf_render_rays(hip.dptr(rays, name="rays"), n, bp, bstride, C.byref(nets), C.byref(params),
-                                           hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
-                                           hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
-                                           hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c),
-                                           hip.dptr(mask, torch.uint8), hip.stream_ptr()), "stnerf_render_rays")
+    args = (hip.dptr(rays, name="rays"), n, bp, bstride, C.byref(nets), C.byref(params),
+            hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
+            hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
+            hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8))
+    if cache is None:
+        hip.check(hip.lib().stnerf_render_rays(*args, hip.stream_ptr()), "stnerf_render_rays")
+    else:
+        raw_c, raw_f, mode = cache
+        S = params.n1 + params.n2
+        if tuple(raw_c.shape) != (n, params.n1, 4) or (raw_f is not None and tuple(raw_f.shape) != (n, S, 4)):
+            raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
+        bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
+        hip.check(hip.lib().stnerf_render_rays_cached(*args, C.byref(bc), hip.stream_ptr()), "stnerf_render_rays_cached")
     if params.only_coarse:
         return mix_c, mix_c, lo_c, lo_c, mask
     return mix_f, mix_c, lo_f, lo_c, mask

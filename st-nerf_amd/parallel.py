@@ -353,6 +353,14 @@ def render_rays_sharded(model, rays, chuncks: int, density_threshold=0.0, bkgd_d
                          only_coarse, density_threshold, bkgd_density_threshold, chuncks, model.replay)
 
 
+def _view_key(model, K, T, h, w, frame_ids):
+    """The view key of rays generated from this camera, for a model with a background cache attached (else None: no cost)."""
+    if getattr(model, "_bkgd_cache", None) is None:
+        return None
+    from stnerf_amd.bkgd_cache import view_key
+    return view_key(K, T, h, w, frame_ids)
+
+
 def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, bkgd_density_threshold=0.0,
                 chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda", gather: Optional[str] = None):
     """One view from its camera: rays generated on the device (no CPU ray tensor), ``layered_batchify_ray`` semantics, the
@@ -366,9 +374,14 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     n_total = h * w
     if act is None or n_total < chuncks:
         rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device)
-        with torch.no_grad():
-            return layered_batchify_ray(model, rays, None, None, chuncks=chuncks, density_threshold=density_threshold,
-                                        bkgd_density_threshold=bkgd_density_threshold)
+        saved_key = getattr(model, "view_key", None)
+        try:
+            model.view_key = _view_key(model, K, T, h, w, frame_ids)
+            with torch.no_grad():
+                return layered_batchify_ray(model, rays, None, None, chuncks=chuncks, density_threshold=density_threshold,
+                                            bkgd_density_threshold=bkgd_density_threshold)
+        finally:
+            model.view_key = saved_key
     rank, world, group = act
     stripe = w * max(1, int(stripe_rows))
     mode = gather_mode(model) if gather is None else gather
@@ -399,13 +412,13 @@ def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: 
         return torch.zeros((0, packed_width(l, mode)), dtype=torch.float32, device=device)
     rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, first_ray=window[0], n=n_local, device=device, stripe=stripe,
                              period=window[2])
-    saved = model.ray_window
+    saved, saved_key = model.ray_window, getattr(model, "view_key", None)
     try:
-        model.ray_window = window
+        model.ray_window, model.view_key = window, _view_key(model, K, T, h, w, frame_ids)
         with torch.no_grad():
             return pack_outputs(model.render_rays_raw(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks), mode)
     finally:
-        model.ray_window = saved
+        model.ray_window, model.view_key = saved, saved_key
 
 
 def init_from_env(backend: Optional[str] = None, single_device: bool = False):

@@ -32,7 +32,7 @@ from stnerf_amd.render.render_pose import render_pose as _render_pose
 class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
-                 model=None, gt_poses=None, gt_Ks=None):
+                 model=None, gt_poses=None, gt_Ks=None, cache_background=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -49,6 +49,7 @@ class LayeredNeuralRenderer:
             self.alpha = self.s_alpha[0]
         self.model = model
         self.model.scale, self.model.shift = self.scale, self.shift
+        self.cache_background = cache_background
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.layer_num + 1)}
@@ -70,6 +71,21 @@ class LayeredNeuralRenderer:
         self.layer_frame_pairs: List = []
         self.trace_layer = -1
         self.dir_name = ''
+
+    @property
+    def cache_background(self):
+        """True while the model keeps the background's network outputs of a fixed view across frames
+        (``LayeredRFRender.set_background_cache``: a time sweep from one camera -- ``set_path_fixed_gt_poses`` + retiming / the
+        edit schedule -- then evaluates the background once; the frames are bit-identical to uncached ones and share one
+        jitter pattern).  Setting it attaches a fresh ``stnerf_amd.BackgroundCache`` to the model or detaches it; not in the
+        reference (keyword-only, off by default)."""
+        return getattr(self.model, "_bkgd_cache", None) is not None
+
+    @cache_background.setter
+    def cache_background(self, on):
+        if bool(on) != self.cache_background:
+            from stnerf_amd.bkgd_cache import BackgroundCache
+            self.model.set_background_cache(BackgroundCache() if on else None)
 
     # ---- layer display / knobs (:643-686, :740-741) ----------------------------------------------------
     def hide_layer(self, layer_id):

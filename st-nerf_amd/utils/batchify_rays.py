@@ -12,10 +12,22 @@ def layered_batchify_ray(model, rays, labels, bboxes, chuncks=512 * 7, near_far=
     stnerf_amd.dropin demo/...`` sets that up) the chunks are dealt out to the ranks in turn and the whole 5-tuple is
     all-gathered, so every rank returns what the single-GPU call returns, bit for bit (stnerf_amd.parallel)."""
     N = rays.size(0)
-    if N < chuncks:
-        return model(rays, labels, bboxes, near_far=near_far, near_far_points=near_far_points)
-    from stnerf_amd import parallel
-    act = parallel.active_group(model)
-    if act is not None:
-        return parallel.render_rays_sharded(model, rays, chuncks, density_threshold, bkgd_density_threshold, act=act)
-    return model.render_rays(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks)
+    # rays this package generated from a camera and tagged with their view (the drop-in's device ray generation) may be served
+    # by the model's background cache; any other tensor has no view key and is never cached
+    key = None
+    if getattr(model, "_bkgd_cache", None) is not None and getattr(model, "view_key", None) is None:
+        from stnerf_amd.bkgd_cache import tagged_view_key
+        key = tagged_view_key(rays)
+    if key is not None:
+        model.view_key = key
+    try:
+        if N < chuncks:
+            return model(rays, labels, bboxes, near_far=near_far, near_far_points=near_far_points)
+        from stnerf_amd import parallel
+        act = parallel.active_group(model)
+        if act is not None:
+            return parallel.render_rays_sharded(model, rays, chuncks, density_threshold, bkgd_density_threshold, act=act)
+        return model.render_rays(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks)
+    finally:
+        if key is not None:
+            model.view_key = None

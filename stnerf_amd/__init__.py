@@ -16,3 +16,11 @@ _init = _util.module_from_spec(_spec)
 _spec.loader.exec_module(_init)
 __doc__ = _init.__doc__
 __version__ = _init.__version__
+
+
+def __getattr__(name):
+    # (lazily: importing the alias package alone stays free of torch)
+    if name == "BackgroundCache":
+        from stnerf_amd.bkgd_cache import BackgroundCache
+        return BackgroundCache
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
