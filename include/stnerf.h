@@ -72,6 +72,24 @@ typedef struct stnerf_layer_edit {
     int32_t has_scale;
 } stnerf_layer_edit;
 
+/* Per-layer rigid rotation R about `centre`, applied to the layer's content after its scale and shift: the box, the radiance
+ * field and the field's view dependence turn together.  Not in the reference (render/layered_neural_renderer.py:19-24 stores
+ * `rotation` and never reads it).  Rendering it means the layer sees the ray in its own frame, and is then rendered unrotated:
+ *     m = R^T (row-major), c = centre, q = o - c
+ *     o'[r] = ((m[3r] q[0] + m[3r+1] q[1]) + m[3r+2] q[2]) + c[r]
+ *     d'[r] =  (m[3r] d[0] + m[3r+1] d[1]) + m[3r+2] d[2]                    r = 0, 1, 2
+ * every product, sum and difference a separate IEEE fp32 operation in this order (no fused multiply-add).  For the layer,
+ * (o', d') take the place of (o, d) in the slab test, in the sample points t d' + o' of both passes (ahead of the point
+ * un-edit) and in the direction the colour branch encodes (stnerf_rgb_ray_bias).  Depths are the ray's own (the map is
+ * rigid), so the depth merge and the compositor see nothing new; the RNG keys, the mask bits and the frame ids stay as
+ * they are.  m must be a rotation: the caller checks (stnerf_amd.LayeredRFRender.layer_ray_transforms does).
+ * Host struct; the entries that take one read `enabled` first: 0 = this layer is not rotated. */
+typedef struct stnerf_layer_rotation {
+    float m[9];       /* R^T, row-major */
+    float centre[3];
+    int32_t enabled;
+} stnerf_layer_rotation;
+
 /* Which rays of a view a call works on.  Local ray i of a call is GLOBAL ray
  *     first + i                                    (stripe == 0: one contiguous window)
  *     first + (i / stripe) * period + i % stripe   (stripe  > 0: stripes of `stripe` rays, one every `period` rays --
@@ -113,6 +131,14 @@ int stnerf_sample_coarse(const float* rays, int64_t n, int ray_stride, const flo
                          int64_t ray_index_base, int64_t ray_index_stripe, int64_t ray_index_period,
                          const stnerf_layer_edit* edits_host, const float* pivot_host, float* t, float* xyz,
                          uint8_t* mask, stnerf_stream_t stream);
+/* The same with per-layer rotations (stnerf_layer_rotation above): rotations_host = host array of l entries, or NULL = none,
+ * which is what stnerf_sample_coarse forwards.  A call without an enabled entry launches the kernels of the plain call. */
+int stnerf_sample_coarse_rot(const float* rays, int64_t n, int ray_stride, const float* boxes,
+                             int64_t box_ray_stride, int l, int n1, const float* jitter, uint64_t seed,
+                             int64_t ray_index_base, int64_t ray_index_stripe, int64_t ray_index_period,
+                             const stnerf_layer_edit* edits_host, const float* pivot_host,
+                             const stnerf_layer_rotation* rotations_host, float* t, float* xyz,
+                             uint8_t* mask, stnerf_stream_t stream);
 
 /* Ragged work: list of rays whose mask[ray][layer] is set.  Replaces the boolean-mask indexing
  * (and its host sync) at modeling/layered_rfrender.py:344-353,400-413,497-510,555-563.
@@ -173,6 +199,13 @@ int stnerf_spacenet_fwd(int kind, const void* packed, int64_t n_rays, int ns, co
                         const float* dirs, int64_t dirs_ray_stride, const float* times,
                         int64_t times_ray_stride, float* raw, int64_t raw_ray_stride, float* ray_bias,
                         stnerf_stream_t stream);
+/* The same for a rotated layer: rotation_host = ONE struct (stnerf_layer_rotation, of the net's layer) or NULL; the colour branch then
+ * encodes d' = R^T d (only `m` is read: a direction has no centre).  xyz are the caller's points, as always. */
+int stnerf_spacenet_fwd_rot(int kind, const void* packed, int64_t n_rays, int ns, const int32_t* ray_list,
+                            const int32_t* ray_count, const float* xyz, int64_t xyz_ray_stride,
+                            const float* dirs, int64_t dirs_ray_stride, const float* times,
+                            int64_t times_ray_stride, float* raw, int64_t raw_ray_stride, float* ray_bias,
+                            const stnerf_layer_rotation* rotation_host, stnerf_stream_t stream);
 
 /* The per-ray part of rgb_net.1 (modeling/spacenet.py:80-86,141-151): the layer reads the 256 backbone features of a
  * sample and the encodings of the ray's direction and frame id -- the same 27 (+ 21) numbers for every sample of the ray
@@ -183,6 +216,10 @@ int stnerf_spacenet_fwd(int kind, const void* packed, int64_t n_rays, int ns, co
 int stnerf_rgb_ray_bias(int kind, const void* packed, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
                         const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride,
                         float* out, stnerf_stream_t stream);
+/* The same with the direction turned first: rotation_host = ONE stnerf_layer_rotation or NULL (none: the plain call's kernel). */
+int stnerf_rgb_ray_bias_rot(int kind, const void* packed, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
+                            const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride,
+                            float* out, const stnerf_layer_rotation* rotation_host, stnerf_stream_t stream);
 
 /* a7 + a8: fused positional encoding (with the fractional-time lerp) + MotionNet MLP (exact f32 MFMA: the MotionNet of
  * stnerf_mlp_stage and of stnerf_train_motionnet_fwd, one persistent launch).
@@ -255,6 +292,8 @@ typedef struct stnerf_stage_layer {
     const float* times;        /* frame id of ray j at times[j * times_ray_stride]; NULL if neither net takes it    */
     int32_t use_time;          /* the SpaceNet is of a *_TIME kind                                                  */
     int32_t motion_flags;      /* STNERF_MOTION_PLAIN_TIME                                                          */
+    const stnerf_layer_rotation* rotation;  /* host; NULL (a zeroed struct) or !enabled: none.  The layer's ray-bias launch
+                                             * encodes R^T dir (stnerf_rgb_ray_bias_rot); the stage kernel is the same   */
 } stnerf_stage_layer;
 int stnerf_mlp_stage(const stnerf_stage_layer* layers_host, int n_layers, int64_t n_rays, int ns, const float* dirs,
                      int64_t dirs_ray_stride, int64_t times_ray_stride, int64_t xyz_ray_stride,
@@ -349,6 +388,16 @@ int stnerf_resample(const float* t, const float* weights, int64_t n, int l, int 
                     int ray_stride, const stnerf_layer_edit* edits_host, const float* pivot_host, const uint8_t* mask,
                     float* t_fine, float* xyz_fine, float* z_new, int32_t* inds, float* cdf,
                     stnerf_stream_t stream);
+/* The same with per-layer rotations (host array of l stnerf_layer_rotation, or NULL = none, which is what stnerf_resample
+ * forwards): the points of a rotated layer are t d' + o', then un-edited.  Depths do not change.  A call with an enabled
+ * entry runs the kernel flavour that carries the box edits; one without launches what the plain call launches. */
+int stnerf_resample_rot(const float* t, const float* weights, int64_t n, int l, int n1, int n2,
+                        const float* u, uint64_t seed, int64_t ray_index_base, int64_t ray_index_stripe,
+                        int64_t ray_index_period, const float* rays,
+                        int ray_stride, const stnerf_layer_edit* edits_host, const float* pivot_host,
+                        const stnerf_layer_rotation* rotations_host, const uint8_t* mask,
+                        float* t_fine, float* xyz_fine, float* z_new, int32_t* inds, float* cdf,
+                        stnerf_stream_t stream);
 
 /* ---- backward pass of the two networks (csrc/train.hip) ------------------------------------------------------
  * What engine/layered_trainer.py:192-217's loss.backward() does to modeling/spacenet.py:45-86 / modeling/motion_net.py:20-32
@@ -554,6 +603,17 @@ int stnerf_render_rays_cached(const float* rays, int64_t n, const float* boxes, 
                               const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                               float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                               const stnerf_bkgd_cache* cache_host, stnerf_stream_t stream);
+/* stnerf_render_rays_cached with per-layer rotations (host array of params->l stnerf_layer_rotation, or NULL = none, which is
+ * what the two entries above forward): the table goes to the sampler, the resampler and every ray-bias launch of both passes,
+ * in all three precisions; the stage kernels, the compositor and the workspace are untouched, and a call without an enabled
+ * entry makes exactly the launches it made before.  The same table serves both passes, so MotionNet reuse holds.  A background
+ * cache is the CALLER's to key: layer 0's rotation is an input of the background's raw outputs, the performers' are not. */
+int stnerf_render_rays_rot(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                           const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                           const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                           float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                           const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                           stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

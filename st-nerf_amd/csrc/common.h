@@ -82,7 +82,51 @@ static inline void fill_edit_args(EditArgs& a, const stnerf_layer_edit* edits, c
     if (pivot) { a.pivot[0] = pivot[0]; a.pivot[1] = pivot[1]; a.pivot[2] = pivot[2]; }
 }
 
+// Per-layer rotations (include/stnerf.h: stnerf_layer_rotation), by value like EditArgs: m = R^T, c = centre; bit i of
+// `on` = layer i is rotated.
+struct RotArgs {
+    float m[STNERF_MAX_LAYERS][9];
+    float c[STNERF_MAX_LAYERS][3];
+    uint32_t on;
+};
+
+static inline void fill_rot_args(RotArgs& a, const stnerf_layer_rotation* rot, int l) {
+    a.on = 0;
+    for (int i = 0; i < STNERF_MAX_LAYERS; ++i) {
+        const bool set = rot && i < l && rot[i].enabled;
+        for (int j = 0; j < 9; ++j) a.m[i][j] = set ? rot[i].m[j] : (j % 4 == 0 ? 1.f : 0.f);
+        for (int j = 0; j < 3; ++j) a.c[i][j] = set ? rot[i].centre[j] : 0.f;
+        if (set) a.on |= 1u << i;
+    }
+}
+
 #if defined(__HIPCC__)
+// d' = R^T d and o' = R^T (o - c) + c of include/stnerf.h, every operation on its own in the stated order (contraction is
+// switched off here whatever the file's flags are).
+__device__ __forceinline__ void rotate_dir(const float* m, const float d[3], float out[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float a = m[3 * r] * d[0];
+        const float b = m[3 * r + 1] * d[1];
+        const float e = m[3 * r + 2] * d[2];
+        const float ab = a + b;
+        out[r] = ab + e;
+    }
+}
+__device__ __forceinline__ void rotate_ray(const float* m, const float* c, float o[3], float d[3]) {
+#pragma clang fp contract(off)
+    const float q[3] = {o[0] - c[0], o[1] - c[1], o[2] - c[2]};
+    float oq[3], dq[3];
+    rotate_dir(m, q, oq);
+    rotate_dir(m, d, dq);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        o[r] = oq[r] + c[r];
+        d[r] = dq[r];
+    }
+}
+
 // ---- Philox4x32-10 counter-based RNG (Salmon et al. 2011): stateless, so the draw of
 // (ray, layer, sample) does not depend on how rays are chunked or sharded over GPUs.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {

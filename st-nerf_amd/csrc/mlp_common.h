@@ -109,9 +109,10 @@ __device__ __forceinline__ void sincos_pe(float x, float& sn, float& cs) {
     cs = ((q + 1) & 2) ? -cv : cv;
 }
 
-// rgb_net.1's direction / time columns once per ray (mlp_raybias.hip): out[ray][128] for the listed rays.
+// rgb_net.1's direction / time columns once per ray (mlp_raybias.hip): out[ray][128] for the listed rays.  rotation (host, may
+// be null or !enabled = none: the plain kernel): the direction is turned into the layer's frame first (include/stnerf.h).
 int launch_ray_bias(int kind, const float* net, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
                     const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride, float* out,
-                    hipStream_t stream);
+                    hipStream_t stream, const stnerf_layer_rotation* rotation = nullptr);
 
 }  // namespace stnerf

@@ -16,14 +16,19 @@ namespace stnerf {
 constexpr int RB_RAYS = 16;     // rays per workgroup
 constexpr int RB_THREADS = 256;  // two groups of 128 threads (= 128 outputs), 8 rays each
 
-__global__ __launch_bounds__(RB_THREADS) void ray_bias_kernel(const float* __restrict__ net, int use_time, int deep,
-                                                              int64_t n_rays, const int32_t* __restrict__ ray_list,
-                                                              const int32_t* __restrict__ ray_count,
-                                                              const float* __restrict__ dirs, int64_t dirs_ray_stride,
-                                                              const float* __restrict__ times, int64_t times_ray_stride,
-                                                              float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float enc[RB_RAYS][48];
-    __shared__ int64_t ray_of[RB_RAYS];
+struct RayBiasRot {
+    float m[9];   // R^T of the layer (include/stnerf.h: stnerf_layer_rotation)
+};
+
+// ROT: the encoded direction is d' = R^T d, computed where d is read.  ray_bias_kernel is the ROT = false body.
+template <bool ROT>
+__device__ __forceinline__ void ray_bias_body(const float* __restrict__ net, int use_time, int deep,
+                                              int64_t n_rays, const int32_t* __restrict__ ray_list,
+                                              const int32_t* __restrict__ ray_count,
+                                              const float* __restrict__ dirs, int64_t dirs_ray_stride,
+                                              const float* __restrict__ times, int64_t times_ray_stride,
+                                              const RayBiasRot* rot, float* __restrict__ out, float (*enc)[48],
+                                              int64_t* ray_of) {
     const SpaceLayout L = space_layout(use_time != 0, deep != 0);
     int64_t cnt = n_rays;
     if (ray_count) {
@@ -44,6 +49,12 @@ __global__ __launch_bounds__(RB_THREADS) void ray_bias_kernel(const float* __res
         float v = 0.f;
         if (f < 27) {
             const float* d = dirs + ray * dirs_ray_stride;
+            float dr[3];
+            if (ROT) {
+                const float din[3] = {d[0], d[1], d[2]};
+                rotate_dir(rot->m, din, dr);
+                d = dr;
+            }
             if (f < 3) {
                 v = fmaxf(d[f], 0.f);
             } else {
@@ -91,11 +102,43 @@ __global__ __launch_bounds__(RB_THREADS) void ray_bias_kernel(const float* __res
     }
 }
 
+__global__ __launch_bounds__(RB_THREADS) void ray_bias_kernel(const float* __restrict__ net, int use_time, int deep,
+                                                              int64_t n_rays, const int32_t* __restrict__ ray_list,
+                                                              const int32_t* __restrict__ ray_count,
+                                                              const float* __restrict__ dirs, int64_t dirs_ray_stride,
+                                                              const float* __restrict__ times, int64_t times_ray_stride,
+                                                              float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float enc[RB_RAYS][48];
+    __shared__ int64_t ray_of[RB_RAYS];
+    ray_bias_body<false>(net, use_time, deep, n_rays, ray_list, ray_count, dirs, dirs_ray_stride, times, times_ray_stride, nullptr, out, enc,
+                         ray_of);
+}
+__global__ __launch_bounds__(RB_THREADS) void ray_bias_rot_kernel(const float* __restrict__ net, int use_time, int deep,
+                                                                  int64_t n_rays, const int32_t* __restrict__ ray_list,
+                                                                  const int32_t* __restrict__ ray_count,
+                                                                  const float* __restrict__ dirs, int64_t dirs_ray_stride,
+                                                                  const float* __restrict__ times, int64_t times_ray_stride,
+                                                                  RayBiasRot rot, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float enc[RB_RAYS][48];
+    __shared__ int64_t ray_of[RB_RAYS];
+    ray_bias_body<true>(net, use_time, deep, n_rays, ray_list, ray_count, dirs, dirs_ray_stride, times, times_ray_stride, &rot, out, enc,
+                         ray_of);
+}
+
 int launch_ray_bias(int kind, const float* net, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
                     const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride, float* out,
-                    hipStream_t stream) {
+                    hipStream_t stream, const stnerf_layer_rotation* rotation) {
     if (n_rays == 0) return STNERF_OK;
     const int64_t blocks = (n_rays + RB_RAYS - 1) / RB_RAYS;
+    if (rotation && rotation->enabled) {
+        RayBiasRot rot;
+        for (int j = 0; j < 9; ++j) rot.m[j] = rotation->m[j];
+        hipLaunchKernelGGL(ray_bias_rot_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), 0, stream, net,
+                           STNERF_NET_USES_TIME(kind) ? 1 : 0, STNERF_NET_IS_DEEP(kind) ? 1 : 0, n_rays, ray_list, ray_count, dirs,
+                           dirs_ray_stride, times, times_ray_stride, rot, out);
+        STNERF_CHECK_LAUNCH("rgb_ray_bias");
+        return STNERF_OK;
+    }
     hipLaunchKernelGGL(ray_bias_kernel, dim3((unsigned)blocks), dim3(RB_THREADS), 0, stream, net,
                        STNERF_NET_USES_TIME(kind) ? 1 : 0, STNERF_NET_IS_DEEP(kind) ? 1 : 0, n_rays, ray_list, ray_count, dirs,
                        dirs_ray_stride, times, times_ray_stride, out);
@@ -110,10 +153,18 @@ using namespace stnerf;
 extern "C" int stnerf_rgb_ray_bias(int kind, const void* packed, int64_t n_rays, const int32_t* ray_list,
                                    const int32_t* ray_count, const float* dirs, int64_t dirs_ray_stride,
                                    const float* times, int64_t times_ray_stride, float* out, stnerf_stream_t stream) {
+    return stnerf_rgb_ray_bias_rot(kind, packed, n_rays, ray_list, ray_count, dirs, dirs_ray_stride, times, times_ray_stride, out,
+                                   nullptr, stream);
+}
+
+extern "C" int stnerf_rgb_ray_bias_rot(int kind, const void* packed, int64_t n_rays, const int32_t* ray_list,
+                                       const int32_t* ray_count, const float* dirs, int64_t dirs_ray_stride,
+                                       const float* times, int64_t times_ray_stride, float* out,
+                                       const stnerf_layer_rotation* rotation_host, stnerf_stream_t stream) {
     STNERF_REQUIRE(STNERF_NET_IS_SPACE(kind), "rgb_ray_bias: bad kind %d", kind);
     STNERF_REQUIRE(packed && dirs && out, "rgb_ray_bias: null pointer");
     STNERF_REQUIRE(!STNERF_NET_USES_TIME(kind) || times, "rgb_ray_bias: net takes time but times is null");
     STNERF_REQUIRE(n_rays >= 0 && ((uintptr_t)out & 15) == 0, "rgb_ray_bias: bad shape / out must be 16-byte aligned");
     return launch_ray_bias(kind, static_cast<const float*>(packed), n_rays, ray_list, ray_count, dirs, dirs_ray_stride, times,
-                           times_ray_stride, out, as_stream(stream));
+                           times_ray_stride, out, as_stream(stream), rotation_host);
 }

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -213,8 +213,8 @@ extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* box
                                   const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                                   float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                   stnerf_stream_t stream) {
-    return stnerf_render_rays_cached(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                     mixed_coarse, layer_fine, layer_coarse, mask, nullptr, stream);
+    return stnerf_render_rays_rot(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                  mixed_coarse, layer_fine, layer_coarse, mask, nullptr, nullptr, stream);
 }
 
 extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
@@ -222,6 +222,17 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
                                          const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                                          float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                          const stnerf_bkgd_cache* cache, stnerf_stream_t stream) {
+    return stnerf_render_rays_rot(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                  mixed_coarse, layer_fine, layer_coarse, mask, cache, nullptr, stream);
+}
+
+// rot: per-layer rotations (include/stnerf.h) or null.  The table reaches the sampler, the resampler and the ray-bias launches
+// of both passes; everything else -- the stage kernels, the compositor, the workspace -- is what it was.
+extern "C" int stnerf_render_rays_rot(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                      const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                      const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                      float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                      const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -274,9 +285,9 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
     int rc;
 
     // ---- coarse samples + hit masks (+ un-edit), then the per-layer lists of hit rays
-    rc = stnerf_sample_coarse(rays, n, rs, boxes, box_ray_stride, l, n1, jitter, p->seed, p->ray_index_base,
-                              p->ray_index_stripe, p->ray_index_period,
-                              p->has_edits ? p->edits_coarse : nullptr, p->pivot, t_c, xyz_c, mask, stream);
+    rc = stnerf_sample_coarse_rot(rays, n, rs, boxes, box_ray_stride, l, n1, jitter, p->seed, p->ray_index_base,
+                                  p->ray_index_stripe, p->ray_index_period,
+                                  p->has_edits ? p->edits_coarse : nullptr, p->pivot, rot, t_c, xyz_c, mask, stream);
     if (rc) return rc;
     if (hipMemsetAsync(ray_count, 0, sizeof(int32_t) * pl.count, st) != hipSuccess) {
         set_error("render_rays: hipMemsetAsync failed");
@@ -321,6 +332,7 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
                     e.times = (timed || deform) ? rays + (p->retiming ? 6 + i : 6) : nullptr;
                     e.use_time = timed ? 1 : 0;
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
+                    e.rotation = rot ? rot + i : nullptr;
                 }
             }
             if (ns_l == 0) return STNERF_OK;   // (background from the cache, no performer shown: nothing to evaluate)
@@ -357,8 +369,9 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
             const float* times = timed ? rays + (p->retiming ? 6 + i : 6) : nullptr;
             const int32_t* lst = i == 0 ? nullptr : ray_list + (int64_t)i * n;
             const int32_t* cnt = i == 0 ? nullptr : ray_count + i;
-            const int r2 = stnerf_spacenet_fwd(kind, net, n, ns, lst, cnt, xyz + (int64_t)i * ns * 3, xs, rays + 3, rs,
-                                                     times, rs, raw + (int64_t)i * ns * 4, ws_, ray_bias + (int64_t)i * n * 128, stream);
+            const int r2 = stnerf_spacenet_fwd_rot(kind, net, n, ns, lst, cnt, xyz + (int64_t)i * ns * 3, xs, rays + 3, rs, times, rs,
+                                                   raw + (int64_t)i * ns * 4, ws_, ray_bias + (int64_t)i * n * 128, rot ? rot + i : nullptr,
+                                                   stream);
             if (r2) return r2;
         }
         set_launch_tag(-1);
@@ -403,9 +416,9 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
     if (p->only_coarse) return clear_mask_hints(mask, n * l, as_stream(stream));
 
     // ---- resample + fine points (:459-475), fine networks, fine composite (:538-606)
-    rc = stnerf_resample(t_c, w_c, n, l, n1, n2, u, p->seed, p->ray_index_base, p->ray_index_stripe, p->ray_index_period,
-                         rays, rs,
-                         p->has_edits ? p->edits_fine : nullptr, p->pivot, mask, t_f, xyz_f, nullptr, nullptr, nullptr, stream);
+    rc = stnerf_resample_rot(t_c, w_c, n, l, n1, n2, u, p->seed, p->ray_index_base, p->ray_index_stripe, p->ray_index_period,
+                             rays, rs,
+                             p->has_edits ? p->edits_fine : nullptr, p->pivot, rot, mask, t_f, xyz_f, nullptr, nullptr, nullptr, stream);
     if (rc) return rc;
     for (int i = 1; i < l; ++i) {   // (xyz_c and t_c lie under raw_f: read here, before the fine stage)
         if (!(reuse >> i & 1)) continue;

@@ -182,6 +182,7 @@ struct ResampleArgs {
     float* z_new;
     int32_t* inds;
     float* cdf_out;
+    RotArgs rot;           // per-layer rotations (include/stnerf.h); last, and read by the non-PLAIN flavours only
 };
 
 // NB1 > 0: the coarse list fits NB1 blocks of 64 lanes and is software pipelined -- the depths, weights and ray of pair
@@ -284,6 +285,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB1 >=
             } else {
                 const float* r = a.rays + ray * a.ray_stride;
                 o0 = r[0], o1 = r[1], o2 = r[2], d0 = r[3], d1 = r[4], d2 = r[5];
+            }
+            // a rotated layer's points are those of the ray in the layer's frame (the depths are the ray's own): before the
+            // all-missed shortcut's point and the fine points below
+            if (!PLAIN && (a.rot.on >> layer & 1)) {
+                float o[3] = {o0, o1, o2}, d[3] = {d0, d1, d2};
+                rotate_ray(a.rot.m[layer], a.rot.c[layer], o, d);
+                o0 = o[0], o1 = o[1], o2 = o[2], d0 = d[0], d1 = d[1], d2 = d[2];
             }
         }
         // ---- a layer the ray misses altogether: every coarse depth is -1000 (bin width 0), so every bin edge and every
@@ -487,6 +495,16 @@ extern "C" int stnerf_resample(const float* t, const float* weights, int64_t n, 
                                const float* rays, int ray_stride,
                                const stnerf_layer_edit* edits_host, const float* pivot_host, const uint8_t* mask, float* t_fine,
                                float* xyz_fine, float* z_new, int32_t* inds, float* cdf, stnerf_stream_t stream) {
+    return stnerf_resample_rot(t, weights, n, l, n1, n2, u, seed, ray_index_base, ray_index_stripe, ray_index_period, rays, ray_stride,
+                               edits_host, pivot_host, nullptr, mask, t_fine, xyz_fine, z_new, inds, cdf, stream);
+}
+
+extern "C" int stnerf_resample_rot(const float* t, const float* weights, int64_t n, int l, int n1, int n2, const float* u,
+                                   uint64_t seed, int64_t ray_index_base, int64_t ray_index_stripe, int64_t ray_index_period,
+                                   const float* rays, int ray_stride,
+                                   const stnerf_layer_edit* edits_host, const float* pivot_host,
+                                   const stnerf_layer_rotation* rotations_host, const uint8_t* mask, float* t_fine,
+                                   float* xyz_fine, float* z_new, int32_t* inds, float* cdf, stnerf_stream_t stream) {
     STNERF_REQUIRE(t && weights && rays && t_fine, "resample: null pointer");
     STNERF_REQUIRE(n >= 0 && l >= 1 && l <= STNERF_MAX_LAYERS && n1 >= 3 && n2 >= 0 && ray_stride >= 6,
                    "resample: bad shape n=%lld l=%d n1=%d n2=%d", (long long)n, l, n1, n2);
@@ -496,6 +514,7 @@ extern "C" int stnerf_resample(const float* t, const float* weights, int64_t n, 
     a.t = t; a.weights = weights; a.n = n; a.l = l; a.n1 = n1; a.n2 = n2; a.u = u; a.seed = seed;
     a.win = RayWindow{ray_index_base, ray_index_stripe, ray_index_period}; a.rays = rays; a.ray_stride = ray_stride;
     fill_edit_args(a.ed, edits_host, pivot_host, l);
+    fill_rot_args(a.rot, rotations_host, l);
     a.mask = mask;
     a.t_fine = t_fine; a.xyz_fine = xyz_fine; a.z_new = z_new; a.inds = inds; a.cdf_out = cdf;
     const int lds = 4 * resample_lds_floats(n1, n2) * (int)sizeof(float);
@@ -506,7 +525,7 @@ extern "C" int stnerf_resample(const float* t, const float* weights, int64_t n, 
     if (blocks > 256 * 32) blocks = 256 * 32;
     LaunchTimer timer(PROF_RESAMPLE, 0, n, n1 + n2, (int64_t)l * (8ll * n1 + (xyz_fine ? 16ll : 4ll) * (n1 + n2)) + 24,
                       as_stream(stream));
-    const bool plain = !u && !z_new && !inds && !cdf && !a.ed.any;
+    const bool plain = !u && !z_new && !inds && !cdf && !a.ed.any && !a.rot.on;
     const dim3 grid((unsigned)blocks), block(256);
     int reserve_rc = STNERF_OK;
     auto launch = [&](auto kernel) {

@@ -97,11 +97,15 @@ __global__ void intersect_kernel(const float* __restrict__ rays, int64_t n, int 
 
 // ------------------------------------------------------------------------------------- a6
 // One thread per (ray, layer, sample): consecutive threads write consecutive t / xyz elements.
-__global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t n, int ray_stride,
-                                     const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
-                                     const float* __restrict__ jitter, uint64_t seed, RayWindow win,
-                                     EditArgs ed, float* __restrict__ t_out, float* __restrict__ xyz_out,
-                                     uint8_t* __restrict__ mask_out) {
+// ROT: the layer sees the ray in its own frame (include/stnerf.h: stnerf_layer_rotation) -- the transform runs per thread,
+// ahead of the slab test; depths, RNG keys and mask bits are the plain kernel's.  The plain kernels below are the ROT = false
+// bodies with the signatures they always had.
+template <bool ROT>
+__device__ __forceinline__ void sample_coarse_body(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                                   const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                                   const float* __restrict__ jitter, uint64_t seed, const RayWindow& win,
+                                                   const EditArgs& ed, const RotArgs* rot, float* __restrict__ t_out,
+                                                   float* __restrict__ xyz_out, uint8_t* __restrict__ mask_out) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t per_ray = (int64_t)l * n1;
     if (e >= n * per_ray) return;
@@ -110,8 +114,9 @@ __global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t n, 
     const int layer = rem / n1;
     const int k = rem - layer * n1;
     const float* r = rays + ray * ray_stride;
-    const float o[3] = {r[0], r[1], r[2]};
-    const float d[3] = {r[3], r[4], r[5]};
+    float o[3] = {r[0], r[1], r[2]};
+    float d[3] = {r[3], r[4], r[5]};
+    if (ROT && (rot->on >> layer & 1)) rotate_ray(rot->m[layer], rot->c[layer], o, d);
     float far_t, near_t;
     intersect_box(o, d, boxes + ray * box_ray_stride + layer * 24, far_t, near_t);
     float start = near_t;
@@ -133,16 +138,32 @@ __global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t n, 
     if (k == 0) mask_out[ray * l + layer] = (fabsf(width) > 1e-5f ? 1 : 0) | ((width == 0.f && start == -1000.0f) ? 2 : 0);
 }
 
+__global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                     const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                     const float* __restrict__ jitter, uint64_t seed, RayWindow win,
+                                     EditArgs ed, float* __restrict__ t_out, float* __restrict__ xyz_out,
+                                     uint8_t* __restrict__ mask_out) {
+    sample_coarse_body<false>(rays, n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, nullptr, t_out, xyz_out, mask_out);
+}
+__global__ void sample_coarse_rot_kernel(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                         const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                         const float* __restrict__ jitter, uint64_t seed, RayWindow win,
+                                         EditArgs ed, RotArgs rot, float* __restrict__ t_out, float* __restrict__ xyz_out,
+                                         uint8_t* __restrict__ mask_out) {
+    sample_coarse_body<true>(rays, n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, &rot, t_out, xyz_out, mask_out);
+}
+
 // Same arithmetic, G = 4 or 2 consecutive samples of one (ray, layer) per thread: one slab test per group, vector
 // stores for t and points that leave as contiguous 16-byte stores.  Used when n1 % G == 0 (every group is then
 // 4G-byte aligned): G = 4 for the usual 64 / 128 samples, G = 2 for the 90 of configs/config_taekwondo.yml.
-template <int G>
-__global__ void sample_coarse_kernel_xg(const float* __restrict__ rays, int64_t n, int ray_stride,
-                                        const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
-                                        const float* __restrict__ jitter, uint64_t seed, RayWindow win,
-                                        EditArgs ed, float* __restrict__ t_out, float* __restrict__ xyz_out,
-                                        uint8_t* __restrict__ mask_out) {
-    __shared__ __attribute__((aligned(16))) float xyz_stage[4 * 64 * 3 * G];  // 4 waves x 64 groups x 3G floats
+// (ROT: as in sample_coarse_body -- one transform per group of G samples)
+template <int G, bool ROT>
+__device__ __forceinline__ void sample_coarse_xg_body(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                                      const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                                      const float* __restrict__ jitter, uint64_t seed, const RayWindow& win,
+                                                      const EditArgs& ed, const RotArgs* rot, float* __restrict__ t_out,
+                                                      float* __restrict__ xyz_out, uint8_t* __restrict__ mask_out,
+                                                      float* __restrict__ xyz_stage) {
     const int64_t g_raw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // group of G samples
     const int gpl = n1 / G;                                            // groups per (ray, layer)
     const int64_t per_ray = (int64_t)l * gpl;
@@ -153,8 +174,9 @@ __global__ void sample_coarse_kernel_xg(const float* __restrict__ rays, int64_t 
     const int layer = rem / gpl;
     const int k0 = (rem - layer * gpl) * G;
     const float* r = rays + ray * ray_stride;
-    const float o[3] = {r[0], r[1], r[2]};
-    const float d[3] = {r[3], r[4], r[5]};
+    float o[3] = {r[0], r[1], r[2]};
+    float d[3] = {r[3], r[4], r[5]};
+    if (ROT && (rot->on >> layer & 1)) rotate_ray(rot->m[layer], rot->c[layer], o, d);
     float far_t, near_t;
     intersect_box(o, d, boxes + ray * box_ray_stride + layer * 24, far_t, near_t);
     float start = near_t;
@@ -213,6 +235,27 @@ __global__ void sample_coarse_kernel_xg(const float* __restrict__ rays, int64_t 
         for (int q = lane; q < nf / 4; q += 64) dst[q] = src[q];
         if (lane < (nf & 3)) dstf[(nf & ~3) + lane] = stage[(nf & ~3) + lane];   // odd tail of the very last wave
     }
+}
+
+template <int G>
+__global__ void sample_coarse_kernel_xg(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                        const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                        const float* __restrict__ jitter, uint64_t seed, RayWindow win,
+                                        EditArgs ed, float* __restrict__ t_out, float* __restrict__ xyz_out,
+                                        uint8_t* __restrict__ mask_out) {
+    __shared__ __attribute__((aligned(16))) float xyz_stage[4 * 64 * 3 * G];  // 4 waves x 64 groups x 3G floats
+    sample_coarse_xg_body<G, false>(rays, n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, nullptr, t_out, xyz_out,
+                                    mask_out, xyz_stage);
+}
+template <int G>
+__global__ void sample_coarse_rot_kernel_xg(const float* __restrict__ rays, int64_t n, int ray_stride,
+                                            const float* __restrict__ boxes, int64_t box_ray_stride, int l, int n1,
+                                            const float* __restrict__ jitter, uint64_t seed, RayWindow win,
+                                            EditArgs ed, RotArgs rot, float* __restrict__ t_out, float* __restrict__ xyz_out,
+                                            uint8_t* __restrict__ mask_out) {
+    __shared__ __attribute__((aligned(16))) float xyz_stage[4 * 64 * 3 * G];
+    sample_coarse_xg_body<G, true>(rays, n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, &rot, t_out, xyz_out,
+                                   mask_out, xyz_stage);
 }
 
 // ------------------------------------------------------------------------------------- compaction
@@ -291,6 +334,16 @@ extern "C" int stnerf_sample_coarse(const float* rays, int64_t n, int ray_stride
                                     const stnerf_layer_edit* edits_host,
                                     const float* pivot_host, float* t, float* xyz, uint8_t* mask,
                                     stnerf_stream_t stream) {
+    return stnerf_sample_coarse_rot(rays, n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, ray_index_base, ray_index_stripe,
+                                    ray_index_period, edits_host, pivot_host, nullptr, t, xyz, mask, stream);
+}
+
+extern "C" int stnerf_sample_coarse_rot(const float* rays, int64_t n, int ray_stride, const float* boxes,
+                                        int64_t box_ray_stride, int l, int n1, const float* jitter, uint64_t seed,
+                                        int64_t ray_index_base, int64_t ray_index_stripe, int64_t ray_index_period,
+                                        const stnerf_layer_edit* edits_host, const float* pivot_host,
+                                        const stnerf_layer_rotation* rotations_host, float* t, float* xyz, uint8_t* mask,
+                                        stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && t && mask, "sample_coarse: null pointer");
     STNERF_REQUIRE(n >= 0 && ray_stride >= 6 && l >= 1 && l <= STNERF_MAX_LAYERS && n1 >= 1,
                    "sample_coarse: bad shape n=%lld stride=%d l=%d n1=%d", (long long)n, ray_stride, l, n1);
@@ -300,6 +353,8 @@ extern "C" int stnerf_sample_coarse(const float* rays, int64_t n, int ray_stride
     const RayWindow win{ray_index_base, ray_index_stripe, ray_index_period};
     EditArgs ed;
     fill_edit_args(ed, edits_host, pivot_host, l);
+    RotArgs rot;
+    fill_rot_args(rot, rotations_host, l);
     const int bs = 256;
     const int64_t tot = n * l * n1;
     STNERF_REQUIRE((tot + bs - 1) / bs < (1ll << 31), "sample_coarse: chunk too large");
@@ -311,7 +366,14 @@ extern "C" int stnerf_sample_coarse(const float* rays, int64_t n, int ray_stride
     if (aligned) {
         const int64_t groups = tot / G;
         const dim3 grid((unsigned)((groups + bs - 1) / bs));
-        if (G == 4)
+        if (rot.on) {
+            if (G == 4)
+                hipLaunchKernelGGL(sample_coarse_rot_kernel_xg<4>, grid, dim3(bs), 0, as_stream(stream), rays, n, ray_stride, boxes,
+                                   box_ray_stride, l, n1, jitter, seed, win, ed, rot, t, xyz, mask);
+            else
+                hipLaunchKernelGGL(sample_coarse_rot_kernel_xg<2>, grid, dim3(bs), 0, as_stream(stream), rays, n, ray_stride, boxes,
+                                   box_ray_stride, l, n1, jitter, seed, win, ed, rot, t, xyz, mask);
+        } else if (G == 4)
             hipLaunchKernelGGL(sample_coarse_kernel_xg<4>, grid, dim3(bs), 0, as_stream(stream), rays, n, ray_stride, boxes,
                                box_ray_stride, l, n1, jitter, seed, win, ed, t, xyz, mask);
         else
@@ -320,8 +382,12 @@ extern "C" int stnerf_sample_coarse(const float* rays, int64_t n, int ray_stride
         STNERF_CHECK_LAUNCH("sample_coarse");
         return STNERF_OK;
     }
-    hipLaunchKernelGGL(sample_coarse_kernel, dim3((unsigned)((tot + bs - 1) / bs)), dim3(bs), 0, as_stream(stream), rays,
-                       n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, t, xyz, mask);
+    if (rot.on)
+        hipLaunchKernelGGL(sample_coarse_rot_kernel, dim3((unsigned)((tot + bs - 1) / bs)), dim3(bs), 0, as_stream(stream), rays,
+                           n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, rot, t, xyz, mask);
+    else
+        hipLaunchKernelGGL(sample_coarse_kernel, dim3((unsigned)((tot + bs - 1) / bs)), dim3(bs), 0, as_stream(stream), rays,
+                           n, ray_stride, boxes, box_ray_stride, l, n1, jitter, seed, win, ed, t, xyz, mask);
     STNERF_CHECK_LAUNCH("sample_coarse");
     return STNERF_OK;
 }

@@ -101,7 +101,7 @@ extern "C" int stnerf_mlp_stage(const stnerf_stage_layer* layers, int n_layers, 
                                     : (deep_rgb ? STNERF_NET_SPACE_DEEP : STNERF_NET_SPACE);
         if (const int rc = launch_ray_bias(kind, static_cast<const float*>(s.space), n_rays, s.ray_list, s.ray_count, dirs,
                                            dirs_ray_stride, s.times, times_ray_stride, ray_bias + (int64_t)i * n_rays * 128,
-                                           as_stream(stream)))
+                                           as_stream(stream), s.rotation))
             return rc;
     }
     a.n_layers = n_layers;
@@ -125,6 +125,16 @@ extern "C" int stnerf_spacenet_fwd(int kind, const void* packed, int64_t n_rays,
                                    const float* dirs, int64_t dirs_ray_stride, const float* times,
                                    int64_t times_ray_stride, float* raw, int64_t raw_ray_stride, float* ray_bias,
                                    stnerf_stream_t stream) {
+    return stnerf_spacenet_fwd_rot(kind, packed, n_rays, ns, ray_list, ray_count, xyz, xyz_ray_stride, dirs, dirs_ray_stride, times,
+                                   times_ray_stride, raw, raw_ray_stride, ray_bias, nullptr, stream);
+}
+
+// (rotation_host: the layer's rotation or null -- it reaches the ray-bias launch only)
+extern "C" int stnerf_spacenet_fwd_rot(int kind, const void* packed, int64_t n_rays, int ns, const int32_t* ray_list,
+                                       const int32_t* ray_count, const float* xyz, int64_t xyz_ray_stride,
+                                       const float* dirs, int64_t dirs_ray_stride, const float* times,
+                                       int64_t times_ray_stride, float* raw, int64_t raw_ray_stride, float* ray_bias,
+                                       const stnerf_layer_rotation* rotation_host, stnerf_stream_t stream) {
     STNERF_REQUIRE(STNERF_NET_IS_SPACE(kind), "spacenet_fwd: bad kind %d", kind);
     STNERF_REQUIRE(packed && xyz && dirs && raw && ray_bias, "spacenet_fwd: null pointer");
     STNERF_REQUIRE(((uintptr_t)ray_bias & 15) == 0, "spacenet_fwd: ray_bias must be 16-byte aligned");
@@ -135,7 +145,7 @@ extern "C" int stnerf_spacenet_fwd(int kind, const void* packed, int64_t n_rays,
     if (n_rays == 0) return STNERF_OK;
     // rgb_net.1's direction / time columns once per ray (mlp_raybias.hip) -> the C operands of that layer
     if (const int rc = launch_ray_bias(kind, static_cast<const float*>(packed), n_rays, ray_list, ray_count, dirs, dirs_ray_stride,
-                                       times, times_ray_stride, ray_bias, as_stream(stream)))
+                                       times, times_ray_stride, ray_bias, as_stream(stream), rotation_host))
         return rc;
     StageArgs a;
     memset(&a, 0, sizeof(a));

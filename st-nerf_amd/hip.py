@@ -28,6 +28,11 @@ class LayerEdit(C.Structure):
     _fields_ = [("shift", C.c_float * 3), ("scale", C.c_float), ("has_shift", C.c_int32), ("has_scale", C.c_int32)]
 
 
+class LayerRotation(C.Structure):
+    """stnerf_layer_rotation (include/stnerf.h): m = R^T row-major, the centre, enabled."""
+    _fields_ = [("m", C.c_float * 9), ("centre", C.c_float * 3), ("enabled", C.c_int32)]
+
+
 class CompositeParams(C.Structure):
     _fields_ = [("border", C.c_float), ("near", C.c_float), ("fine", C.c_int32), ("cut_negative_t", C.c_int32),
                 ("threshold", C.c_float * MAX_LAYERS), ("use_threshold", C.c_int32 * MAX_LAYERS),
@@ -43,7 +48,7 @@ class Nets(C.Structure):
 class StageLayer(C.Structure):
     _fields_ = [("space", C.c_void_p), ("motion", C.c_void_p), ("ray_list", C.c_void_p), ("ray_count", C.c_void_p),
                 ("xyz", C.c_void_p), ("raw", C.c_void_p), ("times", C.c_void_p), ("use_time", C.c_int32),
-                ("motion_flags", C.c_int32)]
+                ("motion_flags", C.c_int32), ("rotation", C.POINTER(LayerRotation))]
 
 
 class RenderParams(C.Structure):
@@ -95,6 +100,9 @@ _PROTOS = {
     "stnerf_sample_coarse": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, c_i64, C.c_int, C.c_int, c_f32p, C.c_uint64,
                                        c_i64, c_i64, c_i64, C.POINTER(LayerEdit), C.POINTER(C.c_float), c_f32p, c_f32p,
                                        C.c_void_p, C.c_void_p]),
+    "stnerf_sample_coarse_rot": (C.c_int, [c_f32p, c_i64, C.c_int, c_f32p, c_i64, C.c_int, C.c_int, c_f32p, C.c_uint64,
+                                           c_i64, c_i64, c_i64, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.POINTER(LayerRotation),
+                                           c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
     "stnerf_compact_rays": (C.c_int, [C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_packed_bytes": (c_i64, [C.c_int]),
     "stnerf_pack_net": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, c_i64]),
@@ -104,6 +112,10 @@ _PROTOS = {
                                       c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, c_f32p, C.c_void_p]),
     "stnerf_rgb_ray_bias": (C.c_int, [C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_f32p, c_i64, c_f32p, c_i64,
                                       c_f32p, C.c_void_p]),
+    "stnerf_spacenet_fwd_rot": (C.c_int, [C.c_int, C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p, c_f32p, c_i64,
+                                          c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, c_f32p, C.POINTER(LayerRotation), C.c_void_p]),
+    "stnerf_rgb_ray_bias_rot": (C.c_int, [C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_f32p, c_i64, c_f32p, c_i64,
+                                          c_f32p, C.POINTER(LayerRotation), C.c_void_p]),
     "stnerf_packed_bytes_bf16x3": (c_i64, [C.c_int]),
     "stnerf_pack_net_bf16x3": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p,
                                          c_i64]),
@@ -151,10 +163,16 @@ _PROTOS = {
     "stnerf_render_rays_cached": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
                                             C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
                                             C.c_void_p]),
+    "stnerf_render_rays_rot": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                         C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                         C.POINTER(LayerRotation), C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,
                                   C.c_void_p, c_f32p, C.c_void_p]),
+    "stnerf_resample_rot": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
+                                      C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.POINTER(LayerRotation), C.c_void_p, c_f32p,
+                                      c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -43,6 +43,8 @@ class LayeredRFRender(nn.Module):
         self.sample_method = M.SAMPLE_METHOD
         self.boarder_weight = M.BOARDER_WEIGHT
         self.scale, self.shift = scale, shift
+        self.rotation = None               # per layer None | angle | R (3,3) | (angle | R, centre): layer_ray_transforms (not in the
+                                           # reference, whose renderer stores `rotation` and never reads it)
         self.near, self.alpha = 0, 1
         self.pose_refinement = False
         self.layer_num, self.camera_num = layer_num, camera_num
@@ -142,7 +144,8 @@ class LayeredRFRender(nn.Module):
         border, the background model flags, the parameter versions of the background networks and -- only where
         BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME make it an input -- the background's frame id.  The piece part is the ray
         range and its ray window.  Deliberately absent: performer frame ids, boxes, edits and shown flags, alpha and the two
-        density thresholds -- they act on other layers or after the networks, and a sweep over them must hit."""
+        density thresholds -- they act on other layers or after the networks, and a sweep over them must hit.  Of ``rotation`` the
+        group holds layer 0's (m, c) alone: a sweep over the performers' rotations hits."""
         from stnerf_amd.modeling._packed import _params_fingerprint
         view, bkgd_frame = view_key
         l = self.layer_num + 1
@@ -158,6 +161,13 @@ class LayeredRFRender(nn.Module):
             box0 = (box0 - pivot) * self.scale[0] + pivot
         if self.shift is not None and len(self.shift) > 0 and self.shift[0] is not None:
             box0 = box0 + torch.tensor(self.shift[0], dtype=torch.float32)
+        rot0 = None
+        if self.rotation is not None:                     # layer 0's ray transform (its default centre: the edited box's)
+            sp0 = self._rotation_specs()
+            if sp0 is not None and sp0[0] is not None:
+                m0 = sp0[0][0].T.contiguous()
+                c0 = sp0[0][1] if sp0[0][1] is not None else torch.mean(box0, 0)
+                rot0 = (m0.numpy().tobytes(), c0.numpy().tobytes())
         def edit0(fine):
             e = self._point_edits(l, fine)
             if e is None:
@@ -170,7 +180,7 @@ class LayeredRFRender(nn.Module):
                  prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), box0.numpy().tobytes(), edit0(False), edit0(True),
                  None if pivot is None else tuple(float(x) for x in pivot.tolist()), float(self.near), float(self.boarder_weight),
                  (bool(self.bkgd_use_deform_time), bool(self.bkgd_use_space_time), bool(self.use_space_time), bool(self.deep_rgb)),
-                 tuple(_params_fingerprint(m) for m in nets), bkgd_frame if timed else None)
+                 tuple(_params_fingerprint(m) for m in nets), bkgd_frame if timed else None, rot0)
         return group, (int(piece[0]), int(piece[1]), tuple(int(x) for x in window))
 
     # ---- reference API -----------------------------------------------------------------------
@@ -223,6 +233,78 @@ class LayeredRFRender(nn.Module):
                     continue
                 boxes[..., i, :, :] += torch.tensor(self.shift[i], dtype=torch.float32, device=boxes.device)
         return boxes, pivot
+
+    @staticmethod
+    def _parse_rotation(entry):
+        """One entry of ``rotation`` -> None | (R (3,3) fp32, centre (3,) fp32 | None).  A float is radians about +z (the up axis
+        of these scenes: the slab test's bottom / up faces, ``_pivot``), counter-clockwise seen from +z, its matrix built in
+        fp64 and rounded to fp32; a (3,3) matrix must be a rotation; a pair adds the centre."""
+        if entry is None:
+            return None
+        spec, centre = entry, None
+        if isinstance(entry, (tuple, list)) and len(entry) == 2:
+            spec, centre = entry
+            centre = torch.as_tensor(centre, dtype=torch.float32).reshape(-1)
+            if centre.numel() != 3:
+                raise ValueError(f"rotation: a centre has 3 coordinates, got {centre.numel()}")
+        a = torch.as_tensor(spec, dtype=torch.float64)
+        if a.dim() == 0:
+            c, s = math.cos(float(a)), math.sin(float(a))
+            R = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float64).to(torch.float32)
+        elif tuple(a.shape) == (3, 3):
+            R = a.to(torch.float32)
+            r64 = R.to(torch.float64)
+            # a non-rigid map would change the depths along a ray, which the depth merge of the layers relies on
+            if float((r64.T @ r64 - torch.eye(3, dtype=torch.float64)).abs().max()) > 1e-5 or float(torch.linalg.det(r64)) < 0:
+                raise ValueError("rotation: the 3x3 matrix is not a rotation (max |R^T R - I| > 1e-5 or det < 0)")
+        else:
+            raise ValueError(f"rotation: an entry is an angle, a 3x3 matrix or a (angle | matrix, centre) pair, got shape {tuple(a.shape)}")
+        return R, centre
+
+    def _rotation_specs(self):
+        """None (no layer is rotated) or one parsed entry per layer (``_parse_rotation``)."""
+        if self.rotation is None:
+            return None
+        l = self.layer_num + 1
+        if len(self.rotation) != l:
+            raise ValueError(f"rotation must have one entry per layer ({l}, layer 0 = the background), got {len(self.rotation)}")
+        specs = [self._parse_rotation(r) for r in self.rotation]
+        return specs if any(sp is not None for sp in specs) else None
+
+    def layer_ray_transforms(self, boxes):
+        """Per layer None | (m (3,3) fp32, c (3,) fp32): the numbers the library gets for ``rotation`` (host arithmetic only).
+        Layer i's content is turned by R_i about c_i after its scale and shift; rendering it, the layer sees the ray in its own
+        frame, q = o - c:
+            o'[r] = ((m[r,0] q[0] + m[r,1] q[1]) + m[r,2] q[2]) + c[r],   d'[r] = (m[r,0] d[0] + m[r,1] d[1]) + m[r,2] d[2]
+        with m = R_i^T, every operation a separate fp32 one in this order (include/stnerf.h: stnerf_layer_rotation).
+        boxes: the EDITED boxes (l,8,3) of the chunk group (any device), or None when every rotated layer names its centre.  A
+        rotated layer without a centre turns about the fp32 mean of its box's 8 corners."""
+        specs = self._rotation_specs()
+        l = self.layer_num + 1
+        if specs is None:
+            return [None] * l
+        out = []
+        for i, sp in enumerate(specs):
+            if sp is None:
+                out.append(None)
+                continue
+            R, c = sp
+            if c is None:
+                if boxes is None:
+                    raise ValueError(f"rotation of layer {i} has no centre and no box to take one from: give (rotation, centre)")
+                c = torch.mean(boxes[i].detach().to("cpu", torch.float32), 0)
+            out.append((R.T.contiguous(), c.clone()))
+        return out
+
+    def _per_ray_box_transforms(self, rays, boxes):
+        """``layer_ray_transforms`` for width-7 rays, whose edited boxes (n,l,8,3) are per ray: a default centre is row 0's box's,
+        which is every ray's only if the call has ONE frame id (one device-to-host check, paid only for a rotation without a
+        centre)."""
+        need_box = any(sp is not None and sp[1] is None for sp in self._rotation_specs())
+        if need_box and not bool((rays[:, 6] == rays[0, 6]).all()):
+            raise ValueError("rotation without a centre on rays that mix frame ids: the layer's box differs from ray to ray, "
+                             "give (rotation, centre)")
+        return self.layer_ray_transforms(boxes[0] if need_box else None)
 
     def _point_edits(self, l, fine):
         """Per-layer inverse edit for sample points: coarse :293-303; fine :467-475 (where a None shift
@@ -281,10 +363,11 @@ class LayeredRFRender(nn.Module):
             ops.spacenet_fwd(nets[i - 1]._packed("fp32"), xyz[:, i], rays[:, 3:6], tm, raw[:, i], ray_list=lst[i],
                              ray_count=cnt[i:i + 1])
 
-    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None):
+    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
-        the call's ray tensor when the background cache may serve it (a view key is set), else None."""
+        the call's ray tensor when the background cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
+        chunk group, passed only when a layer is rotated."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.layer_num + 1
         p = hip.RenderParams()
@@ -339,7 +422,7 @@ class LayeredRFRender(nn.Module):
                 cache_arg = (entry[0], entry[1], mode)
         try:
             return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
-                                   u=(replay.get("u") if replay else None), cache=cache_arg)
+                                   u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations)
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
                 cache.discard(key)             # (never filled)
@@ -415,34 +498,36 @@ class LayeredRFRender(nn.Module):
         train = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
         self._warn_if_eval_with_grad()
         step = N if ref_chunk is None else ref_chunk
-        groups = []  # (start, end, boxes, pivot)
+        rotated = self._rotation_specs() is not None
+        groups = []  # (start, end, boxes, pivot[, rotations])
         if retiming:
             row0 = rays[0::step, 6:].cpu()  # one D2H: row-0 frame ids of every reference chunk
             n_chunks, c0 = row0.shape[0], 0
             for c in range(1, n_chunks + 1):  # merge runs of reference chunks that share their boxes
                 if c == n_chunks or not torch.equal(row0[c], row0[c0]):
                     boxes, pivot = self._retimed_boxes(row0[c0])
-                    groups.append((c0 * step, min(c * step, N), boxes.to(rays.device), pivot))
+                    groups.append((c0 * step, min(c * step, N), boxes.to(rays.device), pivot)
+                                  + ((self.layer_ray_transforms(boxes),) if rotated else ()))
                     c0 = c
         else:
             fid = rays[:, 6].to(torch.int64) - 1
             bb = self.bboxes.to(rays.device).float().index_select(0, fid)                          # :193
             bk = self.bkgd_bbox.to(rays.device).float().unsqueeze(0).expand(N, 1, 8, 3)
             boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
-            groups.append((0, N, boxes, pivot))
+            groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))
         outs = []
         cap = self.max_rays_per_launch
         first, stripe, period = self.ray_window
         if stripe > 0:                     # launch pieces must start on a stripe boundary
             cap = max(stripe, cap // stripe * stripe)
-            if any(g0 % stripe for (g0, _, _, _) in groups):
+            if any(g[0] % stripe for g in groups):
                 raise ValueError("a striped ray window needs chunk groups that start on a stripe boundary "
                                  "(frame ids that change inside the view: render it unstriped)")
         window_at = (lambda s: (first + s, 0, 0)) if stripe <= 0 else (lambda s: (first + s // stripe * period, stripe, period))
         # the background cache serves calls whose view is known on the host (view_key) and whose draws are the device RNG's
         cacheable = (getattr(self, "_bkgd_cache", None) is not None and getattr(self, "view_key", None) is not None
                      and self.replay is None and not train and not per_sample_bkgd_time)
-        for (g0, g1, boxes, pivot) in groups:
+        for (g0, g1, boxes, pivot, *rot) in groups:
             for s in range(g0, g1, cap):
                 e = min(s + cap, g1)
                 bx = boxes if boxes.dim() == 3 else boxes[s:e].contiguous()
@@ -460,7 +545,8 @@ class LayeredRFRender(nn.Module):
                 else:
                     # (the piece travels only when the cache may serve it: uncached, the call is the nine-argument one it always was)
                     outs.append(self._render_launch(rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
-                                                    bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ())))
+                                                    bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ()),
+                                                    **(dict(rotations=rot[0]) if rot else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range(5))
         self.advance_seed()

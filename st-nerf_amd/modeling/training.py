@@ -121,6 +121,9 @@ def render_rays_train(model, rays, boxes, pivot, retiming: bool, only_coarse: bo
     """One launch piece of ``LayeredRFRender.render_rays_raw`` with autograd history: the five raw tensors
     (mixed_fine (n,5), mixed_coarse (n,5), layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8)."""
     n, l = rays.shape[0], model.layer_num + 1
+    if getattr(model, "rotation", None) is not None and any(r is not None for r in model.rotation):
+        raise NotImplementedError("per-layer rotation is a render-time edit: this op-by-op path (training, and batches that mix "
+                                  "background frame ids under BKGD_USE_SPACE_TIME) does not apply it -- clear model.rotation")
     n1, n2 = model.coarse_ray_sample, model.fine_ray_sample
     times_col = (lambda i: 6 + i) if retiming else (lambda i: 6)
     ec, ef = model._point_edits(l, False), model._point_edits(l, True)

@@ -52,6 +52,34 @@ def _edits(edits, pivot, l):
     return arr, pv
 
 
+def _rotation_struct(dst, entry):
+    """Fill one hip.LayerRotation from None | (m (3,3) = R^T, centre (3,) | None): fp32 numbers as they are."""
+    if entry is None:
+        dst.enabled = 0
+        return
+    m, c = entry
+    mv = torch.as_tensor(m, dtype=torch.float32).reshape(9).tolist()
+    cv = [0.0, 0.0, 0.0] if c is None else torch.as_tensor(c, dtype=torch.float32).reshape(3).tolist()
+    for j in range(9):
+        dst.m[j] = mv[j]
+    for j in range(3):
+        dst.centre[j] = cv[j]
+    dst.enabled = 1
+
+
+def _rotations(rotations, l):
+    """-> LayerRotation array of l entries | None.  rotations: per layer None | (m, centre), the pairs of
+    ``LayeredRFRender.layer_ray_transforms`` (include/stnerf.h: stnerf_layer_rotation)."""
+    if rotations is None or all(r is None for r in rotations):
+        return None
+    if len(rotations) != l:
+        raise ValueError(f"rotations must have one entry per layer ({l}), got {len(rotations)}")
+    arr = (hip.LayerRotation * l)()
+    for i in range(l):
+        _rotation_struct(arr[i], rotations[i])
+    return arr
+
+
 def _boxes_arg(boxes: Tensor, n: int):
     if boxes.dim() == 3:  # (l,8,3) shared
         return hip.dptr(boxes, name="boxes"), 0, boxes.shape[0]
@@ -102,10 +130,11 @@ def intersect(rays: Tensor, boxes: Tensor) -> Tensor:
 
 def sample_coarse(rays: Tensor, boxes: Tensor, n1: int, jitter: Optional[Tensor] = None, seed: int = 0,
                   ray_index_base: int = 0, edits=None, pivot=None, want_xyz: bool = True, ray_index_stripe: int = 0,
-                  ray_index_period: int = 0, raw_mask: bool = False):
+                  ray_index_period: int = 0, raw_mask: bool = False, rotations=None):
     """-> t (n,l,n1), xyz (n,l,n1,3) | None, mask (n,l) uint8 (0 / 1 = the reference's ray_mask; with ``raw_mask`` the
     library's byte: bit 1 = the sampler's "every depth of this pair is -1000" hint, which ``composite`` accepts).
-    layers/RaySamplePoint.py:70-107."""
+    layers/RaySamplePoint.py:70-107.  ``rotations``: per layer None | (m, centre) -- the layer sees the ray turned into its
+    frame (stnerf_sample_coarse_rot)."""
     n = rays.shape[0]
     bp, bstride, l = _boxes_arg(boxes, n)
     if jitter is not None and tuple(jitter.shape) != (l, n, n1):
@@ -114,11 +143,14 @@ def sample_coarse(rays: Tensor, boxes: Tensor, n1: int, jitter: Optional[Tensor]
     xyz = torch.empty(n, l, n1, 3, dtype=torch.float32, device=rays.device) if want_xyz else None
     mask = torch.empty(n, l, dtype=torch.uint8, device=rays.device)
     ed, pv = _edits(edits, pivot, l)
-    hip.check(hip.lib().stnerf_sample_coarse(hip.dptr(rays, name="rays"), n, rays.shape[1], bp, bstride, l, n1,
-                                             hip.dptr(jitter, name="jitter"), seed, ray_index_base, ray_index_stripe,
-                                             ray_index_period, ed, pv,
-                                             hip.dptr(t), hip.dptr(xyz), hip.dptr(mask, torch.uint8),
-                                             hip.stream_ptr()), "stnerf_sample_coarse")
+    rot = _rotations(rotations, l)
+    head = (hip.dptr(rays, name="rays"), n, rays.shape[1], bp, bstride, l, n1, hip.dptr(jitter, name="jitter"), seed, ray_index_base,
+            ray_index_stripe, ray_index_period, ed, pv)
+    tail = (hip.dptr(t), hip.dptr(xyz), hip.dptr(mask, torch.uint8), hip.stream_ptr())
+    if rot is None:
+        hip.check(hip.lib().stnerf_sample_coarse(*head, *tail), "stnerf_sample_coarse")
+    else:
+        hip.check(hip.lib().stnerf_sample_coarse_rot(*head, rot, *tail), "stnerf_sample_coarse_rot")
     return t, xyz, (mask if raw_mask else mask.bitwise_and_(1))
 
 
@@ -302,15 +334,16 @@ def _worklist(ray_list, ray_count):
 
 
 def spacenet_fwd(net: PackedNet, xyz: Tensor, dirs: Tensor, times: Optional[Tensor], raw: Tensor,
-                 ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None) -> Tensor:
+                 ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None, rotation=None) -> Tensor:
     """xyz (n,ns,3), dirs (n,3), times (n,) | None, raw (n,ns,4) out; all may be strided views whose
-    dim 0 is the ray.  Writes raw {r,g,b,sigma} for the listed rays.  modeling/spacenet.py:101-160."""
+    dim 0 is the ray.  Writes raw {r,g,b,sigma} for the listed rays.  modeling/spacenet.py:101-160.
+    ``rotation``: None | (m, centre) of the net's layer -- the colour branch encodes m @ dir (stnerf_spacenet_fwd_rot)."""
     n, ns = xyz.shape[0], xyz.shape[1]
     if net.use_time and times is None:
         raise ValueError("this SpaceNet takes time: pass times (n,)")
     if net.precision == "bf16x3":   # the split-bf16 arithmetic exists as the stage kernel: a one-layer stage
         mlp_stage([dict(space=net, motion=None, xyz=xyz, raw=raw, times=times if net.use_time else None, ray_list=ray_list,
-                        ray_count=ray_count)], dirs, ns, deep_rgb=net.kind in (hip.NET_SPACE_DEEP, hip.NET_SPACE_TIME_DEEP))
+                        ray_count=ray_count, rotation=rotation)], dirs, ns, deep_rgb=net.kind in (hip.NET_SPACE_DEEP, hip.NET_SPACE_TIME_DEEP))
         return raw
     xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
     dp, ds = _strided_view_ptr(dirs, (3,), "dirs")
@@ -322,15 +355,21 @@ def spacenet_fwd(net: PackedNet, xyz: Tensor, dirs: Tensor, times: Optional[Tens
     lp, cp = _worklist(ray_list, ray_count)
     # workspace of the per-ray part of rgb_net.1 (stnerf_rgb_ray_bias): one row of 128 floats per ray
     ray_bias = torch.empty(n, 128, dtype=torch.float32, device=raw.device)
-    hip.check(hip.lib().stnerf_spacenet_fwd(net.kind, hip.dptr(net.blob), n, ns, lp, cp, xp, xs, dp, ds, tp, ts, rp, rs,
-                                            hip.dptr(ray_bias), hip.stream_ptr()), "stnerf_spacenet_fwd")
+    if rotation is None:
+        hip.check(hip.lib().stnerf_spacenet_fwd(net.kind, hip.dptr(net.blob), n, ns, lp, cp, xp, xs, dp, ds, tp, ts, rp, rs,
+                                                hip.dptr(ray_bias), hip.stream_ptr()), "stnerf_spacenet_fwd")
+    else:
+        rot = _rotations([rotation], 1)
+        hip.check(hip.lib().stnerf_spacenet_fwd_rot(net.kind, hip.dptr(net.blob), n, ns, lp, cp, xp, xs, dp, ds, tp, ts, rp, rs,
+                                                    hip.dptr(ray_bias), rot, hip.stream_ptr()), "stnerf_spacenet_fwd_rot")
     return raw
 
 
 def rgb_ray_bias(net: PackedNet, dirs: Tensor, times: Optional[Tensor], ray_list: Optional[Tensor] = None,
-                 ray_count: Optional[Tensor] = None) -> Tensor:
+                 ray_count: Optional[Tensor] = None, rotations=None) -> Tensor:
     """The per-ray part of rgb_net.1 (stnerf_rgb_ray_bias): (n, 128) = bias + W[:, 256:] relu([PE_4(dir), PE_10(time)]) for
-    the listed rays (other rows are zero here).  modeling/spacenet.py:80-86,141-151."""
+    the listed rays (other rows are zero here).  modeling/spacenet.py:80-86,141-151.  ``rotations``: None, one (m, centre)
+    pair or a one-entry list of them -- the net's layer is rotated and m @ dir is encoded (stnerf_rgb_ray_bias_rot)."""
     n = dirs.shape[0]
     if net.precision != "fp32":
         raise ValueError("stnerf_rgb_ray_bias reads the exact-f32 blob layout: pack the network 'fp32' for this call "
@@ -344,8 +383,16 @@ def rgb_ray_bias(net: PackedNet, dirs: Tensor, times: Optional[Tensor], ray_list
         tp, ts = C.c_void_p(0), 0
     lp, cp = _worklist(ray_list, ray_count)
     out = torch.zeros(n, 128, dtype=torch.float32, device=dirs.device)
-    hip.check(hip.lib().stnerf_rgb_ray_bias(net.kind, hip.dptr(net.blob), n, lp, cp, dp, ds, tp, ts, hip.dptr(out),
-                                            hip.stream_ptr()), "stnerf_rgb_ray_bias")
+    if isinstance(rotations, list):
+        if len(rotations) != 1:
+            raise ValueError(f"rgb_ray_bias works on one layer: rotations must be one (m, centre) pair, got {len(rotations)} entries")
+        rotations = rotations[0]
+    if rotations is None:
+        hip.check(hip.lib().stnerf_rgb_ray_bias(net.kind, hip.dptr(net.blob), n, lp, cp, dp, ds, tp, ts, hip.dptr(out),
+                                                hip.stream_ptr()), "stnerf_rgb_ray_bias")
+    else:
+        hip.check(hip.lib().stnerf_rgb_ray_bias_rot(net.kind, hip.dptr(net.blob), n, lp, cp, dp, ds, tp, ts, hip.dptr(out),
+                                                    _rotations([rotations], 1), hip.stream_ptr()), "stnerf_rgb_ray_bias_rot")
     return out
 
 
@@ -375,10 +422,11 @@ def motionnet_fwd(net: PackedNet, xyz: Tensor, times: Tensor, flow: Optional[Ten
 def mlp_stage(layers: Sequence[dict], dirs: Tensor, ns: int, deep_rgb: bool = False, sigmoid_rgb: bool = False) -> None:
     """One persistent launch over every listed layer (stnerf_mlp_stage).  Each dict: space (PackedNet), motion
     (PackedNet | None), xyz (n,ns,3), raw (n,ns,4) out, times (n,) | None, ray_list / ray_count | None,
-    plain_time (bool).  Views may be strided as long as all layers share the ray strides.  The arithmetic follows the
+    plain_time (bool), rotation (None | (m, centre): the layer's ray-bias launch encodes m @ dir).  Views may be strided as long as all layers share the ray strides.  The arithmetic follows the
     nets' packing: all "fp32" (exact f32 MFMA) or all "bf16x3" (split-bf16 MFMA)."""
     n = dirs.shape[0]
     arr = (hip.StageLayer * len(layers))()
+    rots = (hip.LayerRotation * len(layers))()       # (outlives the call below)
     strides = None
     precs = set()
     dp, ds = _strided_view_ptr(dirs, (3,), "dirs")
@@ -400,6 +448,9 @@ def mlp_stage(layers: Sequence[dict], dirs: Tensor, ns: int, deep_rgb: bool = Fa
         a.space, a.motion = ly["space"].blob.data_ptr(), (ly["motion"].blob.data_ptr() if ly.get("motion") is not None else None)
         a.ray_list, a.ray_count, a.xyz, a.raw, a.times = lp.value, cp.value, xp.value, rp.value, tp.value
         a.use_time, a.motion_flags = int(ly["space"].use_time), (hip.MOTION_PLAIN_TIME if ly.get("plain_time") else 0)
+        if ly.get("rotation") is not None:
+            _rotation_struct(rots[i], ly["rotation"])
+            a.rotation = C.pointer(rots[i])
     if precs not in ({"fp32"}, {"bf16x3"}):
         raise ValueError(f"mlp_stage: every network of a launch must be packed 'fp32' or every one 'bf16x3' (got {sorted(precs)})")
     bx = 4 if precs == {"bf16x3"} else 0
@@ -486,11 +537,12 @@ def composite_bwd(t: Tensor, raw: Tensor, mask: Optional[Tensor], order: Optiona
 
 def resample(t: Tensor, weights: Tensor, n2: int, rays: Tensor, u: Optional[Tensor] = None, seed: int = 0,
              ray_index_base: int = 0, edits=None, pivot=None, want_xyz: bool = True, debug: bool = False,
-             ray_index_stripe: int = 0, ray_index_period: int = 0, mask: Optional[Tensor] = None):
+             ray_index_stripe: int = 0, ray_index_period: int = 0, mask: Optional[Tensor] = None, rotations=None):
     """t (n,l,n1), weights (n,l,n1) -> t_fine (n,l,n1+n2) ascending, xyz_fine (n,l,n1+n2,3) | None
     [, z_new (n,l,n2), inds (n,l,n2) int32, cdf (n,l,n1-1) if debug].
     utils/sample_pdf.py:18-63 + modeling/layered_rfrender.py:459-475.  ``mask`` (n,l) uint8 with the sampler's hints
-    (``sample_coarse(raw_mask=True)``): pairs flagged "missed" are skipped, their output rows stay unwritten."""
+    (``sample_coarse(raw_mask=True)``): pairs flagged "missed" are skipped, their output rows stay unwritten.
+    ``rotations``: per layer None | (m, centre) -- a rotated layer's points are those of the turned ray (stnerf_resample_rot)."""
     n, l, n1 = t.shape
     if u is not None and tuple(u.shape) != (l, n, n2):
         raise ValueError(f"u must be (l,n,n2) = {(l, n, n2)}, got {tuple(u.shape)}")
@@ -501,12 +553,15 @@ def resample(t: Tensor, weights: Tensor, n2: int, rays: Tensor, u: Optional[Tens
     inds = torch.empty(n, l, n2, dtype=torch.int32, device=dev) if debug else None
     cdf = torch.empty(n, l, n1 - 1, dtype=torch.float32, device=dev) if debug else None
     ed, pv = _edits(edits, pivot, l)
-    hip.check(hip.lib().stnerf_resample(hip.dptr(t, name="t"), hip.dptr(weights, name="weights"), n, l, n1, n2,
-                                        hip.dptr(u, name="u"), seed, ray_index_base, ray_index_stripe, ray_index_period,
-                                        hip.dptr(rays, name="rays"),
-                                        rays.shape[1], ed, pv, hip.dptr(mask, torch.uint8, "mask"), hip.dptr(t_fine), hip.dptr(xyz), hip.dptr(z_new),
-                                        hip.dptr(inds, torch.int32), hip.dptr(cdf), hip.stream_ptr()),
-              "stnerf_resample")
+    rot = _rotations(rotations, l)
+    head = (hip.dptr(t, name="t"), hip.dptr(weights, name="weights"), n, l, n1, n2, hip.dptr(u, name="u"), seed, ray_index_base,
+            ray_index_stripe, ray_index_period, hip.dptr(rays, name="rays"), rays.shape[1], ed, pv)
+    tail = (hip.dptr(mask, torch.uint8, "mask"), hip.dptr(t_fine), hip.dptr(xyz), hip.dptr(z_new), hip.dptr(inds, torch.int32),
+            hip.dptr(cdf), hip.stream_ptr())
+    if rot is None:
+        hip.check(hip.lib().stnerf_resample(*head, *tail), "stnerf_resample")
+    else:
+        hip.check(hip.lib().stnerf_resample_rot(*head, rot, *tail), "stnerf_resample_rot")
     if debug:
         return t_fine, xyz, z_new, inds, cdf
     return t_fine, xyz
@@ -546,11 +601,12 @@ def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Te
 
 
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
-                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None):
+                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
-    (stnerf_render_rays_cached; mode hip.BKGD_CACHE_CAPTURE fills the two tensors, hip.BKGD_CACHE_REUSE renders from them)."""
+    (stnerf_render_rays_cached; mode hip.BKGD_CACHE_CAPTURE fills the two tensors, hip.BKGD_CACHE_REUSE renders from them).
+    ``rotations``: per layer None | (m, centre), the pairs of ``LayeredRFRender.layer_ray_transforms`` (stnerf_render_rays_rot)."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -568,14 +624,19 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
             hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
             hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
             hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8))
-    if cache is None:
-        hip.check(hip.lib().stnerf_render_rays(*args, hip.stream_ptr()), "stnerf_render_rays")
-    else:
+    rot = _rotations(rotations, l)
+    bc = None
+    if cache is not None:
         raw_c, raw_f, mode = cache
         S = params.n1 + params.n2
         if tuple(raw_c.shape) != (n, params.n1, 4) or (raw_f is not None and tuple(raw_f.shape) != (n, S, 4)):
             raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
         bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
+    if rot is not None:
+        hip.check(hip.lib().stnerf_render_rays_rot(*args, None if bc is None else C.byref(bc), rot, hip.stream_ptr()), "stnerf_render_rays_rot")
+    elif bc is None:
+        hip.check(hip.lib().stnerf_render_rays(*args, hip.stream_ptr()), "stnerf_render_rays")
+    else:
         hip.check(hip.lib().stnerf_render_rays_cached(*args, C.byref(bc), hip.stream_ptr()), "stnerf_render_rays_cached")
     if params.only_coarse:
         return mix_c, mix_c, lo_c, lo_c, mask

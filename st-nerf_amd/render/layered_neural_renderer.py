@@ -32,7 +32,7 @@ from stnerf_amd.render.render_pose import render_pose as _render_pose
 class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
-                 model=None, gt_poses=None, gt_Ks=None, cache_background=False):
+                 model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -41,6 +41,15 @@ class LayeredNeuralRenderer:
         self.cfg = cfg
         self.scale, self.shift, self.rotation = scale, shift, rotation
         self.s_shift, self.s_scale, self.s_alpha = s_shift, s_scale, s_alpha
+        # s_rotation = (start, end): per-layer angles about +z (radians; None = that layer is not rotated), interpolated per
+        # frame like s_shift.  `rotation` itself goes to the model as scale / shift do (LayeredRFRender.rotation: angle, matrix
+        # or (angle | matrix, centre) per layer); the reference stores it and never reads it (:19-24).
+        self.s_rotation = s_rotation
+        if s_rotation is not None:
+            if len(s_rotation) != 2 or len(s_rotation[0]) != len(s_rotation[1]) or \
+                    any((a is None) != (b is None) for a, b in zip(s_rotation[0], s_rotation[1])):
+                raise ValueError("s_rotation is (start, end): two per-layer angle lists with None in the same places")
+            self.rotation = list(s_rotation[0])
         if s_shift is not None:
             self.shift = self.s_shift[0]
         if s_scale is not None:
@@ -49,6 +58,7 @@ class LayeredNeuralRenderer:
             self.alpha = self.s_alpha[0]
         self.model = model
         self.model.scale, self.model.shift = self.scale, self.shift
+        self.model.rotation = self.rotation
         self.cache_background = cache_background
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
@@ -150,6 +160,9 @@ class LayeredNeuralRenderer:
             a, b = self.s_alpha[0], self.s_alpha[1]
             step = (b - a) / (n - 1)
             self.s_alpha_frame = [(a + i * step) for i in range(n)]
+        if self.s_rotation is not None:
+            lerp = lambda a, b, i: None if a is None else a + i * ((b - a) / (n - 1))
+            self.s_rotation_frame = [[lerp(a, b, i) for a, b in zip(*self.s_rotation)] for i in range(n)]
 
     # ---- camera paths ---------------------------------------------------------------------------------------
     def set_smooth_path_poses(self, step_num, around=False, smooth_time=False):
@@ -255,6 +268,8 @@ class LayeredNeuralRenderer:
                 self.model.scale = self.s_scale_frame[idx]
             if self.s_alpha is not None:
                 self.model.alpha = self.s_alpha_frame[idx]
+            if self.s_rotation is not None:
+                self.model.rotation = self.s_rotation_frame[idx]
             color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                      self.layer_frame_pairs[idx], density_threshold,
                                                                      bkgd_density_threshold)
