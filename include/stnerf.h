@@ -346,6 +346,22 @@ int stnerf_composite(const float* t, const float* raw, const uint8_t* mask, int6
                      const stnerf_composite_params* params_host, float* layer_out, float* mixed_out,
                      float* weights, int32_t* order, uint8_t* scratch, stnerf_stream_t stream);
 
+/* stnerf_composite with the in-scene layer passes (stnerf_composite forwards here with two NULLs and launches what it always did).
+ * The merged composite gives every sample of the stably sorted union the weight w = alpha T (after the density edits, the fine
+ * stage's `t < near` cut on the merged copy, and with the deltas of the MERGED list, `border` last).
+ *   merged_weights[n][l][S]: that weight, stored at the sample's SOURCE index (layer-major, as `weights`); exact zeros for a layer
+ *     that takes no part on the ray (no network output and every depth -1000).  Needs mixed_out.
+ *   scene_out[n][l][5] = sum_k merged_weights {r, g, b, t, 1} per layer, in layer_out's layout: layer i's premultiplied colour,
+ *     weighted depth and alpha INSIDE the mixed image, occluded by and occluding the others (layer_out[i] is layer i alone).  r, g,
+ *     b are the colours the compositor used (sigmoid(rgb), or raw's own with rgb_activated); a layer without network output on the
+ *     ray (hidden, missed, a grazing hit) gets five exact zeros.  sum_i scene_out[i] equals mixed_out up to the order of the fp32
+ *     sums.  Needs merged_weights (STNERF_EINVAL before any launch otherwise); one more HBM-bound launch, 24 B per sample.
+ * Either may be NULL.  Same bits on every route, and the other outputs are the bits of stnerf_composite. */
+int stnerf_composite_scene(const float* t, const float* raw, const uint8_t* mask, int64_t n, int l, int S,
+                           const stnerf_composite_params* params_host, float* layer_out, float* mixed_out,
+                           float* weights, int32_t* order, uint8_t* scratch, float* merged_weights, float* scene_out,
+                           stnerf_stream_t stream);
+
 /* backward of stnerf_composite -- what loss.backward() (engine/layered_trainer.py:277) does to
  * VolumeRenderer.forward / gen_weight (layers/render_layer.py:8-58) and to the merge gather
  * (modeling/layered_rfrender.py:425-429, :587-592) through ATen: given g_layer[n][l][5] and g_mixed[n][5] = dLoss /
@@ -614,6 +630,16 @@ int stnerf_render_rays_rot(const float* rays, int64_t n, const float* boxes, int
                            float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                            const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
                            stnerf_stream_t stream);
+/* stnerf_render_rays_rot with the in-scene layer passes of the FINAL stage (fine, or coarse with only_coarse): scene_out[n][l][5]
+ * as stnerf_composite_scene defines it, or NULL = none, which is what the entries above forward and which makes exactly the
+ * launches they made before.  The merged weights live in the final stage's point buffer, which is dead once that stage's
+ * networks have run: the workspace is stnerf_render_workspace_bytes, unchanged. */
+int stnerf_render_rays_scene(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                             const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                             const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                             const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                             float* scene_out, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

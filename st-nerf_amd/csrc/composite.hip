@@ -94,11 +94,12 @@ __device__ __forceinline__ int composite_run(CompositeAcc& A, int count, float b
 
 // A whole layer in registers (block b of lane i = sample 64 b + i, tn = the depth of the sample behind it; FULL: S = 64 * MAXB,
 // no lane is ever idle): the layers of the single-layer and the merge kernel, which need no LDS staging.  cut_near: the
-// merged stream's `t < near` cut of the fine stage (modeling/layered_rfrender.py:605).  wdst: the layer's weights, or null.
+// merged stream's `t < near` cut of the fine stage (modeling/layered_rfrender.py:605).  wdst: the layer's weights, or null;
+// wdst2: a second copy of them (the layer's row of merged_weights where the merged composite IS this one), or null.
 template <int MAXB, bool FULL>
 __device__ __forceinline__ void composite_regs(CompositeAcc& A, unsigned S, float border, unsigned lane, const float (&tk)[MAXB],
                                                const float (&tn)[MAXB], const float4 (&rw)[MAXB], bool cut_near, float nearv,
-                                               float* wdst) {
+                                               float* wdst, float* wdst2 = nullptr) {
 #pragma unroll
     for (int b = 0; b < MAXB; ++b) {
         if (FULL || (unsigned)b * 64u < S) {  // (uniform)
@@ -109,6 +110,7 @@ __device__ __forceinline__ void composite_regs(CompositeAcc& A, unsigned S, floa
             const float sg = (cut_near && tk[b] < nearv) ? 0.f : rw[b].w;
             const float w = composite_block<FULL>(A, sg, delta, rw[b].x, rw[b].y, rw[b].z, tk[b], ok);
             if (wdst && ok) wdst[k] = w;
+            if (wdst2 && ok) wdst2[k] = w;
         }
     }
 }
@@ -143,14 +145,18 @@ struct CompositeArgs {
     int p2;  // floor_pow2(S)
     uint8_t* handled;  // [n] or nullptr: rays composite_single_kernel has already finished (it writes 0 / 1 for every ray)
     int lds_layers;    // composite_merge_kernel: layers its merged list holds (rays with more live layers are left to the next launch)
+    // [n][l][S] or nullptr: the weight of every sample in the MERGED composite, stored at its source index (zeros for a layer that
+    // is not live).  Needs mixed_out.  Only the MW instantiations of the production kernels look at it.
+    float* merged_weights;
 };
 
 // ONE live layer whose list is ascending, held in registers as composite_regs takes it (idle lanes: zeros): edit it,
 // composite it and write every output of the ray -- the layer's weights and composite, zeros for the layers the ray
 // misses, and the mix, which is that layer's composite (same samples, deltas, arithmetic) unless the fine stage's
 // `t < near` cut (:605) bites, which costs a second pass over the registers.  have: the layer has network output
-// (without it -- a hidden layer, a grazing hit -- its samples are the zero tensors of :398-399).
-template <int MAXB>
+// (without it -- a hidden layer, a grazing hit -- its samples are the zero tensors of :398-399).  MW: a.merged_weights (may
+// still be null) gets the weights of whichever pass made the mix; the others' rows are zero.
+template <int MAXB, bool MW>
 __device__ __forceinline__ void composite_single_layer(const CompositeArgs& a, int64_t ray, int layer, bool have, unsigned lane,
                                                        const float (&tk)[MAXB], const float (&tn)[MAXB], float4 (&rw)[MAXB]) {
     const float nearv = a.p.near;
@@ -159,13 +165,21 @@ __device__ __forceinline__ void composite_single_layer(const CompositeArgs& a, i
 #pragma unroll
         for (int b = 0; b < MAXB; ++b) rw[b] = edit_sample(rw[b], tk[b], ed.cut_neg, ed.thr, ed.scale, ed.cut_near, nearv, a.p.rgb_activated != 0);
     }
+    float* mw = nullptr;      // the layer's row of merged_weights
+    bool mw_first = false;    // ... which the first pass writes: the mix is the layer's composite
+    if (MW && a.merged_weights) {
+        mw = a.merged_weights + (ray * a.l + layer) * a.S;
+        mw_first = !(a.p.fine && __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tk[0]), 0)) < nearv);
+    }
     CompositeAcc A;
     composite_regs<MAXB, false>(A, (unsigned)a.S, a.p.border, lane, tk, tn, rw, false, 0.f,
-                                a.weights ? a.weights + (ray * a.l + layer) * a.S : nullptr);
+                                a.weights ? a.weights + (ray * a.l + layer) * a.S : nullptr, MW && mw_first ? mw : nullptr);
     for (int other = 0; other < a.l; ++other) {  // the layers the ray misses: zero weights and outputs
         if (other == layer) continue;
         if (a.weights)
             for (int k = (int)lane; k < a.S; k += 64) a.weights[(ray * a.l + other) * a.S + k] = 0.f;
+        if (MW && a.merged_weights)
+            for (int k = (int)lane; k < a.S; k += 64) a.merged_weights[(ray * a.l + other) * a.S + k] = 0.f;
         if (a.layer_out && lane < 5u) a.layer_out[(ray * a.l + other) * 5 + lane] = 0.f;
     }
     const float t_first = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tk[0]), 0));
@@ -174,7 +188,7 @@ __device__ __forceinline__ void composite_single_layer(const CompositeArgs& a, i
                      a.mixed_out && mix_is_layer ? a.mixed_out + ray * 5 : nullptr, lane);
     if (a.mixed_out && !mix_is_layer) {
         CompositeAcc M;
-        composite_regs<MAXB, false>(M, (unsigned)a.S, a.p.border, lane, tk, tn, rw, true, nearv, nullptr);
+        composite_regs<MAXB, false>(M, (unsigned)a.S, a.p.border, lane, tk, tn, rw, true, nearv, MW ? mw : nullptr);
         composite_store5(M, a.mixed_out + ray * 5, nullptr, lane);
     }
 }
@@ -309,7 +323,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(STNERF_WAVES_COMPOSITE, 8))) 
                 }
             }
             if (!__any(desc)) {  // (a descending list needs the merge to turn it round: general path)
-                composite_single_layer<MAXB>(a, ray, layer, have, (unsigned)lane, tk, tn, rw);
+                composite_single_layer<MAXB, true>(a, ray, layer, have, (unsigned)lane, tk, tn, rw);
                 if (a.order) {  // ascending single layer + leading -1000 samples of the others: computed below
                     const float* tsrc = a.t + ray * LS;
                     for (int e = lane; e < LS; e += 64) ts[e] = tsrc[e];
@@ -367,17 +381,26 @@ __global__ void __attribute__((amdgpu_waves_per_eu(STNERF_WAVES_COMPOSITE, 8))) 
             const bool single = __popc(live) == 1;  // one live layer: the union IS that layer
             for (int layer = 0; layer < a.l; ++layer) {
                 float* wdst = a.weights ? a.weights + (ray * a.l + layer) * a.S : nullptr;
+                float* mdst = a.merged_weights ? a.merged_weights + (ray * a.l + layer) * a.S : nullptr;
                 if (!(live >> layer & 1u)) {  // missed: every weight and every composite output is zero
                     if (wdst)
                         for (int k = lane; k < a.S; k += 64) wdst[k] = 0.f;
+                    if (mdst)
+                        for (int k = lane; k < a.S; k += 64) mdst[k] = 0.f;
                     if (a.layer_out && lane < 5) a.layer_out[(ray * a.l + layer) * 5 + lane] = 0.f;
                     continue;
                 }
                 const float* tl = ts + layer * a.S;
                 const float4* rl = raws + layer * a.S;
+                // merged weights of a single live layer without the near cut: these, if the list turns out ascending (a
+                // descending one goes through the merged composite below, which writes every live sample's slot again)
+                if (!(single && !(a.p.fine && tl[0] < a.p.near))) mdst = nullptr;
                 CompositeAcc A;
                 const int dir = composite_run(A, a.S, a.p.border, lane, [&](int k) { return tl[k]; }, [&](int k) { return rl[k]; },
-                                              [&](int k, float w) { if (wdst) wdst[k] = w; });
+                                              [&](int k, float w) {
+                                                  if (wdst) wdst[k] = w;
+                                                  if (mdst) mdst[k] = w;
+                                              });
                 const bool some_desc = __any(dir & 1), some_asc = __any(dir & 2);
                 if (some_desc && !some_asc) reversed |= 1u << layer;
                 sorted_ok = sorted_ok && !(some_desc && some_asc);
@@ -405,7 +428,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(STNERF_WAVES_COMPOSITE, 8))) 
                               if (cut_near && ts[src] < nearv) rw.w = 0.f;  // :605
                               return rw;
                           },
-                          [&](int, float) {});
+                          [&](int m, float w) {
+                              if (a.merged_weights) a.merged_weights[ray * LS + mord[m]] = w;
+                          });
             composite_store5(A, a.mixed_out + ray * 5, nullptr, (unsigned)lane);
         }
         CP(6);
@@ -438,7 +463,8 @@ struct SingleBuf {
     bool eligible;
 };
 
-template <int MAXB, int MAXCHK>
+// MW: the launch also writes a.merged_weights (the instantiation without it is the one every render without the pass runs).
+template <int MAXB, int MAXCHK, bool MW>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MAXB > 2 ? 4 : STNERF_WAVES_SINGLE, 8))) composite_single_kernel(CompositeArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -508,7 +534,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MAXB >
             for (int i = 0; i < MAXB; ++i) desc = desc || (i * 64 + lane + 1 < a.S && cur.tn[i] < cur.tk[i]);
             ok = __all(others_missed) && !__any(desc);
         }
-        if (ok) composite_single_layer<MAXB>(a, r0, cur.layer, true, (unsigned)lane, cur.tk, cur.tn, cur.rw);
+        if (ok) composite_single_layer<MAXB, MW>(a, r0, cur.layer, true, (unsigned)lane, cur.tk, cur.tn, cur.rw);
         if (lane == 0) a.handled[r0] = ok ? 1 : 0;
         cur = nxt;
         m1 = m2;
@@ -553,8 +579,11 @@ struct LayerRegs {
 
 // FULL: S == 64 * MAXB (64 / 128 / 192 samples per layer: every BASELINE configuration) -- no lane is ever idle, the
 // `k < S` predicates and their exec-mask bookkeeping disappear.
-template <int MAXB, bool FULL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_waves_per_simd(MAXB, FULL), 8))) composite_merge_kernel(CompositeArgs a) {
+// MW: a.merged_weights is written too.  The stores are compiled out of the instantiation every render without the pass runs,
+// so its registers and occupancy are what they were; with them the scatter's address takes one wave per SIMD where the
+// budget was tight.
+template <int MAXB, bool FULL, bool MW>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_waves_per_simd(MAXB, FULL) - (MW && FULL ? 1 : 0), 8))) composite_merge_kernel(CompositeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -664,6 +693,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_
                 for (int b = 0; b < MAXB; ++b)
                     if (ok_lane(b)) wz[(unsigned)b * 64u + lane] = 0.f;
             }
+            if (MW) {
+                float* mz = a.merged_weights + (ray * L + other) * S;
+#pragma unroll
+                for (int b = 0; b < MAXB; ++b)
+                    if (ok_lane(b)) mz[(unsigned)b * 64u + lane] = 0.f;
+            }
             if (a.layer_out && lane < 5u) a.layer_out[(ray * L + other) * 5 + lane] = 0.f;
         }
         if (a.handled && lane == 0u) a.handled[ray] = 1;
@@ -711,8 +746,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_
             float* wdst = a.weights ? a.weights + (ray * L + (unsigned)layer) * S : nullptr;
             const bool single_asc = a.mixed_out && nlive == 1u && !some_desc;
             {
+                float* mdst = nullptr;    // the layer's row of merged_weights
+                bool mw_first = false;    // ... which the first pass writes: the mix is the layer's composite
+                if (MW) {
+                    mdst = a.merged_weights + (ray * L + (unsigned)layer) * S;
+                    mw_first = single_asc && !(fine && __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cur.tk[0]))) < nearv);
+                }
                 CompositeAcc A;
-                composite_regs<MAXB, FULL>(A, S, border, lane, cur.tk, tn, cur.rw, false, 0.f, wdst);
+                composite_regs<MAXB, FULL>(A, S, border, lane, cur.tk, tn, cur.rw, false, 0.f, wdst, MW && mw_first ? mdst : nullptr);
                 const float t_first = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cur.tk[0])));
                 // one live, ascending layer: the union IS the layer; the mix differs from its composite only by the fine
                 // stage's `t < near` cut (:605)
@@ -721,7 +762,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_
                                  mix_is_layer ? a.mixed_out + ray * 5 : nullptr, lane);
                 if (single_asc && !mix_is_layer) {
                     CompositeAcc M;
-                    composite_regs<MAXB, FULL>(M, S, border, lane, cur.tk, tn, cur.rw, true, nearv, nullptr);
+                    composite_regs<MAXB, FULL>(M, S, border, lane, cur.tk, tn, cur.rw, true, nearv, MW ? mdst : nullptr);
                     composite_store5(M, a.mixed_out + ray * 5, nullptr, lane);
                 }
                 merged_done = single_asc;
@@ -861,7 +902,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_
                         if (have_m >> ly & 1u) v = edit_sample(rw[g], tk, cut_neg_on && ly > 0u, tab[ly], tab[16 + ly], !fine && ly == 0u, nearv, activated);
                         if (fine && tk < nearv) v.w = 0.f;                        // :605
                         const float delta = (mm + 1u < m) ? keyn[g] - tk : border;
-                        composite_block<FULL>(A, v.w, delta, v.x, v.y, v.z, tk, ok);
+                        const float w = composite_block<FULL>(A, v.w, delta, v.x, v.y, v.z, tk, ok);
+                        if (MW && ok) a.merged_weights[ray * LS + src[g]] = w;   // (scattered: back to the source index)
                     }
                 }
             }
@@ -872,6 +914,86 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(merge_
       }
     }
     CP_FLUSH;
+}
+
+// (the instantiations without the merged weights first: they are the ones a render runs, and the ones the build's resource
+// report is read for)
+template __global__ void composite_merge_kernel<1, true, false>(CompositeArgs);
+template __global__ void composite_merge_kernel<1, false, false>(CompositeArgs);
+template __global__ void composite_merge_kernel<2, true, false>(CompositeArgs);
+template __global__ void composite_merge_kernel<2, false, false>(CompositeArgs);
+template __global__ void composite_merge_kernel<3, true, false>(CompositeArgs);
+template __global__ void composite_merge_kernel<3, false, false>(CompositeArgs);
+
+// ---------------------------------------------------------------------------------------------
+// In-scene layer passes: layer i's share of the MIXED composite, scene_out[ray][i] = sum_k wM[i][k] {r, g, b, t, 1} with wM
+// the merged weights the compositor kernels above left at the samples' source indices.  sum_i scene_out[i] is mixed_out up to
+// the order of the fp32 sums.  One wave per ray; HBM-bound, 4 + 4 + 16 B per sample (density is loaded with the colour, not
+// used).  The colour goes through edit_sample, whose switches are off here: sigmoid(rgb) unless the caller's is activated.
+// A layer without network output on the ray (hidden, missed, a grazing hit) composited zero tensors: five exact zeros.
+// ---------------------------------------------------------------------------------------------
+struct LayerSceneArgs {
+    const float* t;
+    const float4* raw;
+    const uint8_t* mask;
+    const float* merged_weights;
+    int64_t n;
+    int l, S;
+    stnerf_composite_params p;
+    float* scene_out;
+};
+
+__global__ void __launch_bounds__(256) layer_scene_kernel(LayerSceneArgs a) {
+    const unsigned lane = threadIdx.x & 63u;
+    const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const int64_t first = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t LS = (int64_t)a.l * a.S;
+    const EvalBits ev = eval_bits<false>(a.p, a.l);
+    const bool activated = a.p.rgb_activated != 0;
+    for (int64_t ray = first; ray < a.n; ray += stride) {
+        const int mv = (a.mask && (int)lane < a.l) ? (int)a.mask[ray * a.l + lane] : 0;
+        const unsigned have_m = have_layers(ev, a.mask != nullptr, (unsigned)__ballot((mv & 1) != 0));
+        for (int layer = 0; layer < a.l; ++layer) {
+            float* dst = a.scene_out + (ray * a.l + layer) * 5;
+            if (!(have_m >> layer & 1u)) {   // (uniform)
+                if (lane < 5u) dst[lane] = 0.f;
+                continue;
+            }
+            const float* tl = a.t + ray * LS + (int64_t)layer * a.S;
+            const float* wl = a.merged_weights + ray * LS + (int64_t)layer * a.S;
+            const float4* rl = a.raw + ray * LS + (int64_t)layer * a.S;
+            CompositeAcc A;
+            // every load of the layer (three blocks at a time) is issued before the first one is consumed
+            constexpr int SB = 3;
+            for (int k0 = 0; k0 < a.S; k0 += 64 * SB) {
+                float tv[SB], wv[SB];
+                float4 rv[SB];
+#pragma unroll
+                for (int b = 0; b < SB; ++b) {
+                    const int k = k0 + b * 64 + (int)lane;
+                    tv[b] = wv[b] = 0.f;
+                    rv[b] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k < a.S) {
+                        wv[b] = wl[k];
+                        tv[b] = tl[k];
+                        rv[b] = rl[k];
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < SB; ++b) {
+                    if (k0 + b * 64 + (int)lane < a.S) {
+                        const float4 c = edit_sample(rv[b], tv[b], false, -INFINITY, 1.f, false, 0.f, activated);
+                        A.cr += wv[b] * c.x;
+                        A.cg += wv[b] * c.y;
+                        A.cb += wv[b] * c.z;
+                        A.cd += wv[b] * tv[b];
+                        A.ca += wv[b];
+                    }
+                }
+            }
+            composite_store5(A, dst, nullptr, lane);
+        }
+    }
 }
 
 }  // namespace stnerf
@@ -975,7 +1097,28 @@ extern "C" int stnerf_composite_plan(int l, int S, int with_scratch, int with_or
 extern "C" int stnerf_composite(const float* t, const float* raw, const uint8_t* mask, int64_t n, int l, int S,
                                 const stnerf_composite_params* params_host, float* layer_out, float* mixed_out,
                                 float* weights, int32_t* order, uint8_t* scratch, stnerf_stream_t stream) {
+    return stnerf_composite_scene(t, raw, mask, n, l, S, params_host, layer_out, mixed_out, weights, order, scratch, nullptr, nullptr,
+                                  stream);
+}
+
+// layer_scene_kernel over the rays of a finished composite (merged_weights written by it on the same stream)
+static int launch_layer_scene(const float* t, const float* raw, const uint8_t* mask, int64_t n, int l, int S,
+                              const stnerf_composite_params& p, const float* merged_weights, float* scene_out, hipStream_t stream) {
+    LayerSceneArgs a{t, reinterpret_cast<const float4*>(raw), mask, merged_weights, n, l, S, p, scene_out};
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(layer_scene_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    STNERF_CHECK_LAUNCH("composite (layer passes)");
+    return STNERF_OK;
+}
+
+extern "C" int stnerf_composite_scene(const float* t, const float* raw, const uint8_t* mask, int64_t n, int l, int S,
+                                      const stnerf_composite_params* params_host, float* layer_out, float* mixed_out,
+                                      float* weights, int32_t* order, uint8_t* scratch, float* merged_weights, float* scene_out,
+                                      stnerf_stream_t stream) {
     STNERF_REQUIRE(t && raw && params_host, "composite: null pointer");
+    STNERF_REQUIRE(!scene_out || merged_weights, "composite: scene_out needs merged_weights (the pass is a sum over them)");
+    STNERF_REQUIRE(!merged_weights || mixed_out, "composite: merged_weights needs mixed_out (they are the merged composite's weights)");
     STNERF_REQUIRE(n >= 0 && l >= 1 && l <= STNERF_MAX_LAYERS && S >= 1, "composite: bad shape n=%lld l=%d S=%d",
                    (long long)n, l, S);
     STNERF_REQUIRE(((uintptr_t)raw & 15) == 0, "composite: raw must be 16-byte aligned");
@@ -986,20 +1129,28 @@ extern "C" int stnerf_composite(const float* t, const float* raw, const uint8_t*
     STNERF_REQUIRE(fits, "composite: %d samples per ray need %lld B of LDS per wave, more than the %lld B this kernel may use", l * S,
                    (long long)plan.need, (long long)COMPOSITE_LDS_BUDGET);
     LaunchTimer timer(PROF_COMPOSITE, 0, n, S,
-                      20ll * l * S + l + 20ll * (l + 1) + (weights ? 4ll * l * S : 0) + (order ? 4ll * l * S : 0),
+                      20ll * l * S + l + 20ll * (l + 1) + (weights ? 4ll * l * S : 0) + (order ? 4ll * l * S : 0) +
+                          (merged_weights ? 4ll * l * S : 0) + (scene_out ? 24ll * l * S + l + 20ll * l : 0),
                       as_stream(stream));
+    const bool mw = merged_weights != nullptr;
     const int nblk = (S + 63) / 64;
     if (!plan.staged) {
         // ---- production path: rays with one live layer first when the caller lends n bytes of scratch (pipelined over
         // the rays of a wave, no LDS), the others -- or all of them -- in the register / insertion-merge kernel
         CompositeArgs a{t, reinterpret_cast<const float4*>(raw), mask, n, l, S, *params_host, layer_out, mixed_out,
                         weights, nullptr, 4, floor_pow2(S), nullptr};
+        a.merged_weights = merged_weights;
         if (plan.single) {
             int64_t waves = n < 256 * 32 ? n : 256 * 32;  // 8 waves per SIMD, every wave strides over the rays
             const dim3 grid((unsigned)((waves + 3) / 4));
             a.handled = scratch;
-            if (plan.single == 1) hipLaunchKernelGGL((composite_single_kernel<2, 6>), grid, dim3(256), 0, as_stream(stream), a);
-            else hipLaunchKernelGGL((composite_single_kernel<3, 24>), grid, dim3(256), 0, as_stream(stream), a);
+            if (plan.single == 1) {
+                if (mw) hipLaunchKernelGGL((composite_single_kernel<2, 6, true>), grid, dim3(256), 0, as_stream(stream), a);
+                else hipLaunchKernelGGL((composite_single_kernel<2, 6, false>), grid, dim3(256), 0, as_stream(stream), a);
+            } else {
+                if (mw) hipLaunchKernelGGL((composite_single_kernel<3, 24, true>), grid, dim3(256), 0, as_stream(stream), a);
+                else hipLaunchKernelGGL((composite_single_kernel<3, 24, false>), grid, dim3(256), 0, as_stream(stream), a);
+            }
             STNERF_CHECK_LAUNCH("composite (single-layer rays)");
         }
         if (plan.clear) {
@@ -1020,13 +1171,16 @@ extern "C" int stnerf_composite(const float* t, const float* raw, const uint8_t*
                 hipLaunchKernelGGL(kernel, grid, block, lds, as_stream(stream), a);
                 return STNERF_OK;
             };
-            const int rc = nblk == 1 ? (full ? launch(composite_merge_kernel<1, true>) : launch(composite_merge_kernel<1, false>))
-                         : nblk == 2 ? (full ? launch(composite_merge_kernel<2, true>) : launch(composite_merge_kernel<2, false>))
-                                     : (full ? launch(composite_merge_kernel<3, true>) : launch(composite_merge_kernel<3, false>));
+            const int rc = mw ? (nblk == 1 ? (full ? launch(composite_merge_kernel<1, true, true>) : launch(composite_merge_kernel<1, false, true>))
+                               : nblk == 2 ? (full ? launch(composite_merge_kernel<2, true, true>) : launch(composite_merge_kernel<2, false, true>))
+                                           : (full ? launch(composite_merge_kernel<3, true, true>) : launch(composite_merge_kernel<3, false, true>)))
+                         : nblk == 1 ? (full ? launch(composite_merge_kernel<1, true, false>) : launch(composite_merge_kernel<1, false, false>))
+                         : nblk == 2 ? (full ? launch(composite_merge_kernel<2, true, false>) : launch(composite_merge_kernel<2, false, false>))
+                                     : (full ? launch(composite_merge_kernel<3, true, false>) : launch(composite_merge_kernel<3, false, false>));
             if (rc) return rc;
             STNERF_CHECK_LAUNCH("composite");
         }
-        return STNERF_OK;
+        return scene_out ? launch_layer_scene(t, raw, mask, n, l, S, *params_host, merged_weights, scene_out, as_stream(stream)) : STNERF_OK;
     }
     // ---- the `order` parity output and layers of more than 192 samples: the LDS-staged kernel (every ray on its own)
     const int wpb = plan.wpb[0], lds = (int)plan.lds[0];
@@ -1034,9 +1188,10 @@ extern "C" int stnerf_composite(const float* t, const float* raw, const uint8_t*
         if (const int rc = reserve_dynamic_lds(reinterpret_cast<const void*>(composite_kernel), lds, "composite")) return rc;
     CompositeArgs a{t, reinterpret_cast<const float4*>(raw), mask, n, l, S, *params_host, layer_out, mixed_out,
                     weights, order, wpb, floor_pow2(S), nullptr};
+    a.merged_weights = merged_weights;
     int64_t blocks = (n + wpb - 1) / wpb;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(composite_kernel, dim3((unsigned)blocks), dim3(wpb * 64), lds, as_stream(stream), a);
     STNERF_CHECK_LAUNCH("composite");
-    return STNERF_OK;
+    return scene_out ? launch_layer_scene(t, raw, mask, n, l, S, *params_host, merged_weights, scene_out, as_stream(stream)) : STNERF_OK;
 }

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -226,13 +226,27 @@ extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const flo
                                   mixed_coarse, layer_fine, layer_coarse, mask, cache, nullptr, stream);
 }
 
-// rot: per-layer rotations (include/stnerf.h) or null.  The table reaches the sampler, the resampler and the ray-bias launches
-// of both passes; everything else -- the stage kernels, the compositor, the workspace -- is what it was.
 extern "C" int stnerf_render_rays_rot(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
                                       const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
                                       const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
                                       float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                       const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, stnerf_stream_t stream) {
+    return stnerf_render_rays_scene(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                    mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, nullptr, stream);
+}
+
+// rot: per-layer rotations (include/stnerf.h) or null.  The table reaches the sampler, the resampler and the ray-bias launches
+// of both passes; everything else -- the stage kernels, the compositor, the workspace -- is what it was.
+// scene_out: the in-scene layer passes of the final stage, or null.  Their merged weights (n l ns floats) are written over that
+// stage's points (xyz_c with only_coarse, else xyz_f: three times as large), which nobody reads once the stage's networks
+// have run: the background cache's copies move `raw` only, the MotionNet reuse reads xyz_c BEFORE the fine stage and the fine
+// compositor reads t_f / raw_f, neither of which overlaps xyz_f.
+extern "C" int stnerf_render_rays_scene(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                        const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                        const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                        float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                        const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                        stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -410,8 +424,9 @@ extern "C" int stnerf_render_rays_rot(const float* rays, int64_t n, const float*
         cp.use_threshold[i] = (p->retiming && i >= 1) ? 1 : 0;  // :416-418 (performers, retiming only)
         cp.threshold[i] = p->density_threshold;
     }
-    rc = stnerf_composite(t_c, raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w_c,
-                          nullptr, ray_flags, stream);
+    const bool scene_coarse = scene_out && p->only_coarse;   // (xyz_c is dead: the coarse networks have run)
+    rc = stnerf_composite_scene(t_c, raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w_c,
+                                nullptr, ray_flags, scene_coarse ? xyz_c : nullptr, scene_coarse ? scene_out : nullptr, stream);
     if (rc) return rc;
     if (p->only_coarse) return clear_mask_hints(mask, n * l, as_stream(stream));
 
@@ -439,7 +454,8 @@ extern "C" int stnerf_render_rays_rot(const float* rays, int64_t n, const float*
         cp.threshold[i] = i == 0 ? p->bkgd_density_threshold : p->density_threshold;
     }
     if (l > 2) cp.sigma_scale[2] = p->alpha;                             // :575-576
-    rc = stnerf_composite(t_f, raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, ray_flags, stream);
+    rc = stnerf_composite_scene(t_f, raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, ray_flags,
+                                scene_out ? xyz_f : nullptr, scene_out, stream);
     if (rc) return rc;
     return clear_mask_hints(mask, n * l, as_stream(stream));
 }

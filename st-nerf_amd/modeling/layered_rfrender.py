@@ -363,11 +363,13 @@ class LayeredRFRender(nn.Module):
             ops.spacenet_fwd(nets[i - 1]._packed("fp32"), xyz[:, i], rays[:, 3:6], tm, raw[:, i], ray_list=lst[i],
                              ray_count=cnt[i:i + 1])
 
-    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None):
+    def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
+                       scene=False):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
-        chunk group, passed only when a layer is rotated."""
+        chunk group, passed only when a layer is rotated.  scene: the in-scene layer passes come back as a sixth tensor (passed
+        only by ``render_rays_scene``)."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.layer_num + 1
         p = hip.RenderParams()
@@ -422,7 +424,8 @@ class LayeredRFRender(nn.Module):
                 cache_arg = (entry[0], entry[1], mode)
         try:
             return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
-                                   u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations)
+                                   u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
+                                   **(dict(scene=True) if scene else {}))
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
                 cache.discard(key)             # (never filled)
@@ -434,6 +437,26 @@ class LayeredRFRender(nn.Module):
         from row 0 of every ``ref_chunk``-ray piece) while launching kernels over far larger pieces."""
         return self.as_reference_tuple(self.render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold,
                                                             ref_chunk))
+
+    def render_rays_scene(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
+                          ref_chunk: Optional[int] = None):
+        """``render_rays`` plus the in-scene layer passes of the final stage -> (the reference 5-tuple, scene).  ``scene`` is a
+        list of l (colour (n,3), depth (n,1), alpha (n,1)) triples: layer i's share of the MIXED image -- premultiplied colour,
+        weighted depth and alpha with the other layers occluding it and being occluded by it (fine_layer[i] is layer i alone).
+        Their sum over the layers is the mixed triple up to fp32 summation order; a hidden layer's is exact zeros.  The five
+        standard outputs are the bits of ``render_rays``.  Inference only: no backward is defined for the pass."""
+        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("render_rays_scene in training mode: the in-scene layer passes have no backward; call model.eval() or "
+                               "wrap the render in torch.no_grad()")
+        from stnerf_amd import parallel
+        if parallel.active_group(self) is not None:
+            raise RuntimeError("render_rays_scene under shard_views with more than one rank: the all-gather's modes (stnerf_amd.parallel) "
+                               "have fixed widths and a \"scene\" gather mode is out of scope; render the passes on one rank "
+                               "(model.shard_views = False)")
+        raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True)
+        sc = raw[5]
+        scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.layer_num + 1)]
+        return self.as_reference_tuple(raw[:5]), scene
 
     def as_reference_tuple(self, raw):
         """(mixed_fine (n,5), mixed_coarse (n,5), layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l)) -> the
@@ -468,6 +491,10 @@ class LayeredRFRender(nn.Module):
                         ref_chunk: Optional[int] = None):
         """``render_rays`` before the outputs are cut into the reference's triples: the five tensors the library
         wrote (what stnerf_amd.parallel packs into its one all-gather)."""
+        return self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk)
+
+    def _render_rays_raw(self, rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=False):
+        """``render_rays_raw``; scene: a sixth tensor, the in-scene layer passes (n,l,5) of ``render_rays_scene``."""
         if not rays.is_cuda:
             raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
         rays = rays.contiguous().float()
@@ -492,6 +519,9 @@ class LayeredRFRender(nn.Module):
         if self.bkgd_use_space_time and self.use_space_time:
             from stnerf_amd.modeling import training as _training
             per_sample_bkgd_time = _training.mixed_bkgd_ids(rays)
+        if scene and per_sample_bkgd_time:
+            raise RuntimeError("render_rays_scene on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
+                               "op-by-op path, which has no in-scene layer passes; render one background frame id per call")
         # Training: model.train() + autograd enabled + trainable parameters = what engine/layered_trainer.py:186-194
         # sets up -> the same stages launched op by op with autograd history (stnerf_amd.modeling.training).  In eval() mode the
         # inference kernels run and the outputs carry no history, as under torch.no_grad() (render/layered_neural_renderer.py:377).
@@ -546,9 +576,9 @@ class LayeredRFRender(nn.Module):
                     # (the piece travels only when the cache may serve it: uncached, the call is the nine-argument one it always was)
                     outs.append(self._render_launch(rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
                                                     bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ()),
-                                                    **(dict(rotations=rot[0]) if rot else {})))
+                                                    **(dict(rotations=rot[0]) if rot else {}), **(dict(scene=True) if scene else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
-        raw = tuple(cat(j) for j in range(5))
+        raw = tuple(cat(j) for j in range(6 if scene else 5))
         self.advance_seed()
         return raw
 

@@ -522,6 +522,35 @@ def composite(t: Tensor, raw: Tensor, mask: Optional[Tensor], border: float = 1e
     return layer_out, mixed_out, weights, order
 
 
+def composite_scene(t: Tensor, raw: Tensor, mask: Optional[Tensor], border: float = 1e10, near: float = 0.0,
+                    fine: bool = False, cut_negative_t: bool = False, thresholds: Optional[Sequence[Optional[float]]] = None,
+                    sigma_scale: Optional[Sequence[float]] = None, evaluated: Optional[Sequence[int]] = None,
+                    want_weights: bool = False, want_order: bool = False, rgb_activated: bool = False, two_pass: bool = True,
+                    params: Optional["hip.CompositeParams"] = None):
+    """``composite`` with the in-scene layer passes (stnerf_composite_scene) ->
+    layer_out (n,l,5), mixed_out (n,5), weights (n,l,S) | None, merged_weights (n,l,S), scene (n,l,5).
+    merged_weights: every sample's weight in the MIXED composite, at its source index; scene[:, i] = layer i's share of the mixed
+    image {premultiplied colour(3), weighted depth, alpha}, occluded by and occluding the others.  sum_i scene[:, i] = mixed_out up
+    to fp32 summation order.  ``want_order`` selects the LDS-staged route, as in ``composite`` (the order itself is not returned)."""
+    n, l, S = t.shape
+    p = params if params is not None else composite_params(border, near, fine, cut_negative_t, thresholds, sigma_scale, evaluated,
+                                                           rgb_activated)
+    dev = t.device
+    layer_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
+    mixed_out = torch.empty(n, 5, dtype=torch.float32, device=dev)
+    weights = torch.empty(n, l, S, dtype=torch.float32, device=dev) if want_weights else None
+    order = torch.empty(n, l * S, dtype=torch.int32, device=dev) if want_order else None
+    scratch = torch.empty(n, dtype=torch.uint8, device=dev) if two_pass else None
+    merged = torch.empty(n, l, S, dtype=torch.float32, device=dev)
+    scene = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
+    hip.check(hip.lib().stnerf_composite_scene(hip.dptr(t, name="t"), hip.dptr(raw, name="raw"),
+                                               hip.dptr(mask, torch.uint8, "mask"), n, l, S, C.byref(p), hip.dptr(layer_out),
+                                               hip.dptr(mixed_out), hip.dptr(weights), hip.dptr(order, torch.int32),
+                                               hip.dptr(scratch, torch.uint8), hip.dptr(merged), hip.dptr(scene),
+                                               hip.stream_ptr()), "stnerf_composite_scene")
+    return layer_out, mixed_out, weights, merged, scene
+
+
 def composite_bwd(t: Tensor, raw: Tensor, mask: Optional[Tensor], order: Optional[Tensor], params: "hip.CompositeParams",
                   g_layer: Optional[Tensor], g_mixed: Optional[Tensor]) -> Tensor:
     """dLoss/d raw (n,l,S,4) from dLoss/d layer_out (n,l,5) and dLoss/d mixed_out (n,5) (either may be None):
@@ -601,12 +630,13 @@ def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Te
 
 
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
-                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None):
+                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
     (stnerf_render_rays_cached; mode hip.BKGD_CACHE_CAPTURE fills the two tensors, hip.BKGD_CACHE_REUSE renders from them).
-    ``rotations``: per layer None | (m, centre), the pairs of ``LayeredRFRender.layer_ray_transforms`` (stnerf_render_rays_rot)."""
+    ``rotations``: per layer None | (m, centre), the pairs of ``LayeredRFRender.layer_ray_transforms`` (stnerf_render_rays_rot).
+    ``scene``: append the in-scene layer passes of the final stage, (n,l,5) (stnerf_render_rays_scene), to the returned tuple."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -632,15 +662,18 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
         if tuple(raw_c.shape) != (n, params.n1, 4) or (raw_f is not None and tuple(raw_f.shape) != (n, S, 4)):
             raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
         bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
-    if rot is not None:
+    scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
+    if scene:
+        hip.check(hip.lib().stnerf_render_rays_scene(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), hip.stream_ptr()),
+                  "stnerf_render_rays_scene")
+    elif rot is not None:
         hip.check(hip.lib().stnerf_render_rays_rot(*args, None if bc is None else C.byref(bc), rot, hip.stream_ptr()), "stnerf_render_rays_rot")
     elif bc is None:
         hip.check(hip.lib().stnerf_render_rays(*args, hip.stream_ptr()), "stnerf_render_rays")
     else:
         hip.check(hip.lib().stnerf_render_rays_cached(*args, C.byref(bc), hip.stream_ptr()), "stnerf_render_rays_cached")
-    if params.only_coarse:
-        return mix_c, mix_c, lo_c, lo_c, mask
-    return mix_f, mix_c, lo_f, lo_c, mask
+    out = (mix_c, mix_c, lo_c, lo_c, mask) if params.only_coarse else (mix_f, mix_c, lo_f, lo_c, mask)
+    return out + (scene_out,) if scene else out
 
 
 # ---------------------------------------------------------------------------------------- 8(f)4: training GEMMs

@@ -32,7 +32,7 @@ from stnerf_amd.render.render_pose import render_pose as _render_pose
 class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
-                 model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None):
+                 model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -60,6 +60,10 @@ class LayeredNeuralRenderer:
         self.model.scale, self.model.shift = self.scale, self.shift
         self.model.rotation = self.rotation
         self.cache_background = cache_background
+        # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
+        # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
+        # hand the frame's dict to on_frame as the keyword `scene`; not in the reference (keyword-only, off by default)
+        self.scene_passes = bool(scene_passes)
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.layer_num + 1)}
@@ -246,20 +250,48 @@ class LayeredNeuralRenderer:
                 self.layer_frame_pairs[i][j] = (layer, round(weight * (new_end - new_start) + new_start))
 
     # ---- rendering -------------------------------------------------------------------------------------------
-    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0):
-        """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391)."""
+    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False):
+        """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
+        element, the dict of in-scene layer passes (stnerf_amd.render.render_pose)."""
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
-                            bkgd_density_threshold)
+                            bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}))
+
+    def _render_frame(self, idx, density_threshold, bkgd_density_threshold, inverse_y_axis):
+        """Frame ``idx`` of the path -> (color, depth, color_layer, depth_layer, passes): ``render_pose``, flipped on request;
+        ``passes`` is None unless ``scene_passes`` is on (then ``render_pose``'s dict, flipped alike)."""
+        passes = None
+        if self.scene_passes:
+            color, depth, color_layer, depth_layer, passes = self.render_pose(self.poses[idx], self.Ks[idx],
+                                                                             self.layer_frame_pairs[idx], density_threshold,
+                                                                             bkgd_density_threshold, scene_passes=True)
+        else:
+            color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
+                                                                     self.layer_frame_pairs[idx], density_threshold,
+                                                                     bkgd_density_threshold)
+        if inverse_y_axis:
+            color, depth = torch.flip(color, [0]), torch.flip(depth, [0])
+            color_layer = [torch.flip(i, [0]) for i in color_layer]
+            depth_layer = [torch.flip(i, [0]) for i in depth_layer]
+            if passes is not None:
+                passes = {k: [torch.flip(i, [0]) for i in v] for k, v in passes.items()}
+        return color, depth, color_layer, depth_layer, passes
+
+    def _keep_scene(self, passes, layer_id):
+        self.images_scene[layer_id].append(passes["color_scene"][layer_id].cpu())
+        self.alphas_scene[layer_id].append(passes["alpha_scene"][layer_id].cpu())
 
     def render_path(self, inverse_y_axis=False, density_threshold=0, bkgd_density_threshold=0, auto_save=True,
                     on_frame: Optional[Callable] = None):
         """Render every pose of the path with its (layer, frame) pairs and edit schedule (:401-488).  With
         ``auto_save`` the frames are kept in ``self.images`` / ``self.depths`` (CPU tensors, as the reference
         keeps them for ``save_video``); ``on_frame(idx, color, depth, color_layer, depth_layer)`` is called with
-        the device tensors (write files there)."""
+        the device tensors (write files there); with ``scene_passes`` it also gets ``scene=`` the frame's dict of in-scene layer
+        passes, which are kept in ``self.images_scene`` / ``self.alphas_scene`` next to ``images_layer``."""
         self.images, self.depths = [], []
         self.images_layer = [[] for _ in range(self.layer_num + 1)]
         self.depths_layer = [[] for _ in range(self.layer_num + 1)]
+        self.images_scene = [[] for _ in range(self.layer_num + 1)]
+        self.alphas_scene = [[] for _ in range(self.layer_num + 1)]
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -270,15 +302,10 @@ class LayeredNeuralRenderer:
                 self.model.alpha = self.s_alpha_frame[idx]
             if self.s_rotation is not None:
                 self.model.rotation = self.s_rotation_frame[idx]
-            color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
-                                                                     self.layer_frame_pairs[idx], density_threshold,
-                                                                     bkgd_density_threshold)
-            if inverse_y_axis:
-                color, depth = torch.flip(color, [0]), torch.flip(depth, [0])
-                color_layer = [torch.flip(i, [0]) for i in color_layer]
-                depth_layer = [torch.flip(i, [0]) for i in depth_layer]
+            color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
+                                                                                inverse_y_axis)
             if on_frame is not None:
-                on_frame(idx, color, depth, color_layer, depth_layer)
+                on_frame(idx, color, depth, color_layer, depth_layer, **(dict(scene=passes) if self.scene_passes else {}))
             if auto_save:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
@@ -286,6 +313,8 @@ class LayeredNeuralRenderer:
                     if self.is_shown_layer(layer_id):
                         self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                         self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
+                        if passes is not None:
+                            self._keep_scene(passes, layer_id)
             self.image_num += 1
         return self.images, self.depths
 
@@ -293,19 +322,19 @@ class LayeredNeuralRenderer:
                             on_frame: Optional[Callable] = None):
         """``render_path`` without the per-frame edit schedule plus the occlusion composite of the walking demo
         (:550-618): layer 2 is pasted over the background image wherever it is in front of it
-        (``depth_layer[2] < depth_layer[0]``) and has colour.  The composites are kept in ``self.images_hide``."""
+        (``depth_layer[2] < depth_layer[0]``) and has colour.  The composites are kept in ``self.images_hide``.  That paste is a
+        per-pixel depth test on images composited alone; with ``scene_passes`` the layers' shares of the mixed image, with the
+        compositor's own occlusion, are kept in ``self.images_scene`` / ``self.alphas_scene`` and given to ``on_frame`` as ``scene=``
+        (``color_hide`` stays the reference's computation)."""
         self.images, self.depths, self.images_hide = [], [], []
         self.images_layer = [[] for _ in range(self.layer_num + 1)]
         self.depths_layer = [[] for _ in range(self.layer_num + 1)]
+        self.images_scene = [[] for _ in range(self.layer_num + 1)]
+        self.alphas_scene = [[] for _ in range(self.layer_num + 1)]
         self.image_num = 0
         for idx in range(len(self.poses)):
-            color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
-                                                                     self.layer_frame_pairs[idx], density_threshold,
-                                                                     bkgd_density_threshold)
-            if inverse_y_axis:
-                color, depth = torch.flip(color, [0]), torch.flip(depth, [0])
-                color_layer = [torch.flip(i, [0]) for i in color_layer]
-                depth_layer = [torch.flip(i, [0]) for i in depth_layer]
+            color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
+                                                                                inverse_y_axis)
             color_hide = None
             if self.layer_num >= 2:
                 color_hide = color_layer[0].clone()                                   # :606-611
@@ -314,7 +343,7 @@ class LayeredNeuralRenderer:
                 index = torch.logical_and(index, color_layer[2] != 0)
                 color_hide[index] = color_layer[2][index]
             if on_frame is not None:
-                on_frame(idx, color, depth, color_layer, depth_layer)
+                on_frame(idx, color, depth, color_layer, depth_layer, **(dict(scene=passes) if self.scene_passes else {}))
             if auto_save:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
@@ -323,6 +352,8 @@ class LayeredNeuralRenderer:
                 for layer_id in range(self.layer_num + 1):
                     self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                     self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
+                    if passes is not None:
+                        self._keep_scene(passes, layer_id)
             self.image_num += 1
         return self.images, self.depths
 

@@ -14,7 +14,7 @@ from stnerf_amd.parallel import render_view
 
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
-                density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda"):
+                density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -25,19 +25,30 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     One process per GPU under an initialised torch.distributed group: every rank generates and renders its interleaved
     row stripes of the view only (``model.shard_views = True``: opt-in), one all-gather rebuilds the images this function
     returns on every rank -- gather mode "fine": 6 + 5 l floats per ray instead of the whole 5-tuple's 11 + 10 l
-    (stnerf_amd.parallel.render_view); the return value is the single-GPU one, bit for bit."""
+    (stnerf_amd.parallel.render_view); the return value is the single-GPU one, bit for bit.
+
+    ``scene_passes``: a fifth element, the in-scene layer passes (``LayeredRFRender.render_rays_scene``) as a dict of per-layer
+    image lists on the device: ``color_scene`` (H,W,3) premultiplied, ``alpha_scene`` (H,W,1), ``depth_scene`` (H,W,1) = the
+    weighted depth / far, not clamped.  Their sums over the layers are the mixed colour, alpha and (unclamped) depth.  One rank
+    only."""
     L = model.layer_num
     frame_ids = [0.0] * (L + 1)
     for layer_id, frame_id in layer_frame_pair:
         frame_ids[layer_id] = float(frame_id)
-    stage2, _, stage2_layer, _, _ = render_view(model, torch.as_tensor(K, dtype=torch.float32),
-                                                torch.as_tensor(pose, dtype=torch.float32), height, width, frame_ids,
-                                                density_threshold, bkgd_density_threshold, device=device, gather="fine")
+    out = render_view(model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width,
+                      frame_ids, density_threshold, bkgd_density_threshold, device=device, gather="fine",
+                      **(dict(scene=True) if scene_passes else {}))
+    (stage2, _, stage2_layer, _, _), scene = out if scene_passes else (out, None)
     color = stage2[0].reshape(height, width, 3)
     depth = stage2[1].reshape(height, width, 1).clamp_min(0) / far
     color_layer = [t[0].reshape(height, width, 3) for t in stage2_layer]
     depth_layer = [t[1].reshape(height, width, 1) / far for t in stage2_layer]
-    return color, depth, color_layer, depth_layer
+    if not scene_passes:
+        return color, depth, color_layer, depth_layer
+    passes = dict(color_scene=[t[0].reshape(height, width, 3) for t in scene],
+                  alpha_scene=[t[2].reshape(height, width, 1) for t in scene],
+                  depth_scene=[t[1].reshape(height, width, 1) / far for t in scene])
+    return color, depth, color_layer, depth_layer, passes
 
 
 def to_uint8(image: torch.Tensor) -> torch.Tensor:
