@@ -545,7 +545,11 @@ int stnerf_train_motionnet_dx(const float* wt, const uint32_t* offsets_host, con
  * coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> composite/merge -> resample -> [MotionNet] ->
  * fine SpaceNets -> composite/merge, all enqueued on `stream` into a caller-provided workspace.  Host-side
  * box interpolation / editing (l x 8 x 3 numbers, :190-242) stays with the caller, who passes the edited boxes
- * and the inverse point edits.  Packed-network pointers are device blobs of stnerf_pack_net[_bf16x3]. */
+ * and the inverse point edits.  Packed-network pointers are device blobs of stnerf_pack_net[_bf16x3].
+ * Entries of stnerf_nets may ALIAS: two layers may name one blob (and one MotionNet).  That is how a layer INSTANCE -- a performer
+ * shown a second time with its own frame-id column, box, edit, rotation, shown flag and opacity -- is expressed at this level: the
+ * library never compares or groups network pointers, every per-layer input above is indexed by the layer, and the RNG is keyed by
+ * the layer index, so an instance draws its own jitter. */
 typedef struct stnerf_nets {
     const void* bkgd;                           /* bkgd_spacenet            (STNERF_NET_SPACE)               */
     const void* bkgd_fine;                      /* bkgd_spacenet_fine                                        */
@@ -640,6 +644,17 @@ int stnerf_render_rays_scene(const float* rays, int64_t n, const float* boxes, i
                              float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                              const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
                              float* scene_out, stnerf_stream_t stream);
+/* stnerf_render_rays_scene with a per-layer opacity table: layer_alpha_host[params->l] floats on the host, or NULL = none, which is
+ * what the entries above forward and which makes exactly the launches and results they made before.  Entry i multiplies layer i's
+ * density in the FINE composite (stnerf_composite_params.sigma_scale[i]), where the reference's `alpha` acts on layer 2 alone
+ * (:575-576); the coarse composite, and so an only_coarse call, ignores the table as it ignores `alpha`.  While a table is given
+ * params->alpha is ignored.  Every entry must be finite and >= 0: checked on the host before anything is launched. */
+int stnerf_render_rays_opacity(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                               const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                               const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                               float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                               const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                               float* scene_out, const float* layer_alpha_host, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,9 @@
-// stnerf_render_rays[_cached | _rot | _scene]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
 // enqueued on the caller's stream into a caller-provided workspace (no allocation, no synchronisation).
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -247,6 +248,19 @@ extern "C" int stnerf_render_rays_scene(const float* rays, int64_t n, const floa
                                         float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                         const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
                                         stnerf_stream_t stream) {
+    return stnerf_render_rays_opacity(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                      mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, scene_out, nullptr, stream);
+}
+
+// layer_alpha: one density factor per layer for the FINE composite (host array of p->l floats), or null = the reference's
+// `if i == 2: density *= alpha` (p->alpha on layer 2).  A table replaces p->alpha; only_coarse ignores both.  Entries of
+// `nets` may alias (include/stnerf.h): nothing below compares or groups network pointers.
+extern "C" int stnerf_render_rays_opacity(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                          const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                          const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                          float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                          const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                          const float* layer_alpha, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -264,6 +278,10 @@ extern "C" int stnerf_render_rays_scene(const float* rays, int64_t n, const floa
         STNERF_REQUIRE(nets->space[i] && (p->only_coarse || nets->space_fine[i]), "render_rays: SpaceNet of layer %d missing", i);
         STNERF_REQUIRE(!p->use_deform_time || nets->motion[i], "render_rays: MotionNet of layer %d missing", i);
     }
+    if (layer_alpha)
+        for (int i = 0; i < l; ++i)
+            STNERF_REQUIRE(isfinite(layer_alpha[i]) && layer_alpha[i] >= 0.f,
+                           "render_rays: layer_alpha[%d] = %g is not a finite, non-negative factor", i, (double)layer_alpha[i]);
     const int64_t need = stnerf_render_workspace_bytes(n, l, n1, n2, p->only_coarse);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
@@ -453,7 +471,10 @@ extern "C" int stnerf_render_rays_scene(const float* rays, int64_t n, const floa
         cp.use_threshold[i] = p->retiming ? 1 : 0;                       // :538-547 (bkgd), :564-566 (performers)
         cp.threshold[i] = i == 0 ? p->bkgd_density_threshold : p->density_threshold;
     }
-    if (l > 2) cp.sigma_scale[2] = p->alpha;                             // :575-576
+    if (layer_alpha)
+        for (int i = 0; i < l; ++i) cp.sigma_scale[i] = layer_alpha[i];
+    else if (l > 2)
+        cp.sigma_scale[2] = p->alpha;                                    // :575-576
     rc = stnerf_composite_scene(t_f, raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, ray_flags,
                                 scene_out ? xyz_f : nullptr, scene_out, stream);
     if (rc) return rc;

@@ -145,7 +145,8 @@ def _device_rays_by_pose_and_K(self, T, K, layer_frame_pair):
     from stnerf_amd import ops
     frame_ids = None
     if self.use_deform_time or self.use_space_time:
-        frame_ids = [0.0] * (self.layer_num + 1)
+        # (pairs that name a layer instance of the model, LayeredRFRender.add_instance, widen the rays by its column)
+        frame_ids = [0.0] * max([self.layer_num + 1] + [int(layer_id) + 1 for layer_id, _ in layer_frame_pair])
         for layer_id, frame_id in layer_frame_pair:
             frame_ids[layer_id] = float(frame_id)
     rays = ops.generate_rays(torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(T, dtype=torch.float32),

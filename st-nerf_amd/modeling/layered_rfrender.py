@@ -46,6 +46,10 @@ class LayeredRFRender(nn.Module):
         self.rotation = None               # per layer None | angle | R (3,3) | (angle | R, centre): layer_ray_transforms (not in the
                                            # reference, whose renderer stores `rotation` and never reads it)
         self.near, self.alpha = 0, 1
+        self.layer_alpha = None            # None: `alpha` on layer 2, as the reference; else one density factor per layer of
+                                           # total_layers (None = 1.0) for the fine composite (stnerf_render_rays_opacity) --
+                                           # what lets a layer instance be a ghost.  Needs alpha == 1 (not in the reference)
+        self._instances = []               # add_instance: the source performer (1..layer_num) of layer layer_num + 1 + j
         self.pose_refinement = False
         self.layer_num, self.camera_num = layer_num, camera_num
         self.use_deform_view, self.bkgd_use_deform_time = False, bool(M.BKGD_USE_DEFORM_TIME)
@@ -112,6 +116,73 @@ class LayeredRFRender(nn.Module):
     FRESH_DRAWS_DEFAULT = False   # what a new model's fresh_draws_per_call starts as (dropin.patch_reference: True)
     SHARD_VIEWS_DEFAULT = False   # what a new model's shard_views starts as (the dropin launcher under torch.distributed.run: True)
 
+    # ---- layer instances (not in the reference: its advertised "duplication" edit) ---------------------
+    @property
+    def instances(self):
+        """The source performer of every instance, in layer order: layer ``layer_num + 1 + j`` borrows the networks and the
+        box column of performer ``instances[j]``."""
+        return tuple(self._instances)
+
+    @property
+    def total_layers(self):
+        """l: the background, the performers and the instances -- what the render path counts layers with."""
+        return self.layer_num + 1 + len(self._instances)
+
+    def add_instance(self, src):
+        """Show performer ``src`` (1..layer_num) a second time -> the new layer's id.  The instance borrows the source's networks
+        (the packed blobs themselves: no parameter, no second pack, no device copy) and its box column, and owns everything
+        else a layer has: its frame-id column of the rays, its ``scale`` / ``shift`` / ``rotation`` / ``layer_alpha`` entry and its
+        shown flag.  The model then renders what the WIDE model renders (LAYER_NUM + 1, the modules and
+        the box column copied), bit for bit; the RNG is keyed by the layer index, so the instance draws its own jitter.
+        Inference only."""
+        from stnerf_amd import hip
+        if isinstance(src, bool) or not isinstance(src, int) or not 1 <= src <= self.layer_num:
+            raise ValueError(f"add_instance: the source must be a performer 1..{self.layer_num} (not the background, not an "
+                             f"instance), got {src!r}")
+        if self.total_layers + 1 > hip.MAX_LAYERS:
+            raise ValueError(f"add_instance: {self.total_layers + 1} layers exceed STNERF_MAX_LAYERS = {hip.MAX_LAYERS}")
+        self._instances.append(src)
+        layer_id = self.total_layers - 1
+        self.display_layers[layer_id] = 1
+        return layer_id
+
+    def clear_instances(self):
+        """Drop every instance (the per-layer lists -- scale, shift, rotation, layer_alpha -- are the caller's to shorten)."""
+        for i in range(self.layer_num + 1, self.total_layers):
+            self.display_layers.pop(i, None)
+        self._instances = []
+
+    def _module_index(self, layer_id):
+        """Index into spacenets / spacenets_fine / time_deform_nets of layer ``layer_id`` >= 1: its own, or its source's."""
+        return (layer_id if layer_id <= self.layer_num else self._instances[layer_id - self.layer_num - 1]) - 1
+
+    def _box_table(self):
+        """``bboxes`` (frames, l - 1, 8, 3) with the instances' columns appended, each a copy of its source's: everything
+        downstream of it (the pivot, the edits, retiming, the rotations' default centres) sees l layers."""
+        if not self._instances:
+            return self.bboxes
+        return torch.cat([self.bboxes, self.bboxes[:, [s - 1 for s in self._instances]]], 1)
+
+    def _layer_alpha_table(self):
+        """None (``layer_alpha`` unset: ``alpha`` acts, on layer 2) or l floats for stnerf_render_rays_opacity."""
+        if self.layer_alpha is None:
+            return None
+        l = self.total_layers
+        if len(self.layer_alpha) != l:
+            raise ValueError(f"layer_alpha must have one entry per layer ({l}, layer 0 = the background), got {len(self.layer_alpha)}")
+        if float(self.alpha) != 1.0:
+            raise ValueError(f"layer_alpha together with alpha = {self.alpha}: alpha is layer 2's entry of the table -- set it there "
+                             "and leave model.alpha at 1")
+        return [1.0 if a is None else float(a) for a in self.layer_alpha]
+
+    def _inference_only_edits(self):
+        """What the op-by-op path (training, mixed background frame ids) does not implement, or None."""
+        if self._instances:
+            return "layer instances (add_instance)"
+        if self.layer_alpha is not None:
+            return "layer_alpha"
+        return None
+
     def set_precision(self, precision: str):
         """"bf16x3" (the default: three bf16 pieces per fp32 operand, six MFMAs per product, two accumulators: fp32's
         significand and range, closer to an fp64 evaluation than an fp32 fma chain, 1.5 x the speed) or "fp32" (exact f32
@@ -148,7 +219,7 @@ class LayeredRFRender(nn.Module):
         group holds layer 0's (m, c) alone: a sweep over the performers' rotations hits."""
         from stnerf_amd.modeling._packed import _params_fingerprint
         view, bkgd_frame = view_key
-        l = self.layer_num + 1
+        l = self.total_layers
         timed = self.bkgd_use_deform_time or (self.bkgd_use_space_time and self.use_space_time)
         bk = self.bkgd_bbox
         host = getattr(self, "_bkgd_bbox_host", None)          # (one D2H per box version, not per frame)
@@ -214,7 +285,7 @@ class LayeredRFRender(nn.Module):
     def _pivot(self):
         """Edit pivot, layered_rfrender.py:216-232: mean of the frame-0 centres of layers 1 and 2, with each
         centre's z replaced by corner-1's z."""
-        first = torch.cat([self.bkgd_bbox.detach().cpu().float(), self.bboxes[0].detach().cpu().float()], 0)
+        first = torch.cat([self.bkgd_bbox.detach().cpu().float(), self._box_table()[0].detach().cpu().float()], 0)
         centre = torch.mean(first, 1)
         centre[:, 2] = first[:, 1, 2]
         return (centre[2] + centre[1]) / 2
@@ -265,7 +336,7 @@ class LayeredRFRender(nn.Module):
         """None (no layer is rotated) or one parsed entry per layer (``_parse_rotation``)."""
         if self.rotation is None:
             return None
-        l = self.layer_num + 1
+        l = self.total_layers
         if len(self.rotation) != l:
             raise ValueError(f"rotation must have one entry per layer ({l}, layer 0 = the background), got {len(self.rotation)}")
         specs = [self._parse_rotation(r) for r in self.rotation]
@@ -280,7 +351,7 @@ class LayeredRFRender(nn.Module):
         boxes: the EDITED boxes (l,8,3) of the chunk group (any device), or None when every rotated layer names its centre.  A
         rotated layer without a centre turns about the fp32 mean of its box's 8 corners."""
         specs = self._rotation_specs()
-        l = self.layer_num + 1
+        l = self.total_layers
         if specs is None:
             return [None] * l
         out = []
@@ -330,8 +401,8 @@ class LayeredRFRender(nn.Module):
     def _retimed_boxes(self, row0_frame_ids):
         """One box per layer for a (reference) chunk from ROW 0's frame ids (:195-208), edited.
         row0_frame_ids: CPU fp32 tensor (l,) = rays[0, 6:]."""
-        L = self.layer_num
-        bb = self.bboxes.detach().cpu().float()
+        L = self.total_layers - 1
+        bb = self._box_table().detach().cpu().float()
         per = torch.zeros(L, 8, 3)
         for i in range(L):
             f = row0_frame_ids[i + 1] - 1                        # fp32 0-dim tensor, as in the reference
@@ -347,20 +418,20 @@ class LayeredRFRender(nn.Module):
         """Deform + evaluate every layer's network on its (masked) rays through the op-level entry points
         (:340-418 / :495-576).  The render path itself runs this inside stnerf_render_rays; this op-level
         composition is kept for stage-by-stage debugging (tools/debug_stages.py)."""
-        l = self.layer_num + 1
+        l = self.total_layers
         bk, nets = self._nets(fine)
         if self.use_deform_time:
             for i in range(1, l):
                 if not self.is_shown_layer(i):
                     continue  # a hidden layer's points are never consumed
-                ops.motionnet_fwd(self.time_deform_nets[i - 1]._packed("fp32"), xyz[:, i], rays[:, times_col(i)],
+                ops.motionnet_fwd(self.time_deform_nets[self._module_index(i)]._packed("fp32"), xyz[:, i], rays[:, times_col(i)],
                                   add_to_xyz=True, ray_list=lst[i], ray_count=cnt[i:i + 1])
         ops.spacenet_fwd(bk._packed("fp32"), xyz[:, 0], rays[:, 3:6], None, raw[:, 0])
         for i in range(1, l):
             if not self.is_shown_layer(i):
                 continue
             tm = rays[:, times_col(i)] if self.use_space_time else None
-            ops.spacenet_fwd(nets[i - 1]._packed("fp32"), xyz[:, i], rays[:, 3:6], tm, raw[:, i], ray_list=lst[i],
+            ops.spacenet_fwd(nets[self._module_index(i)]._packed("fp32"), xyz[:, i], rays[:, 3:6], tm, raw[:, i], ray_list=lst[i],
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
@@ -371,7 +442,7 @@ class LayeredRFRender(nn.Module):
         chunk group, passed only when a layer is rotated.  scene: the in-scene layer passes come back as a sixth tensor (passed
         only by ``render_rays_scene``)."""
         from stnerf_amd import hip
-        n, l = rays.shape[0], self.layer_num + 1
+        n, l = rays.shape[0], self.total_layers
         p = hip.RenderParams()
         p.l, p.n1, p.n2, p.ray_stride = l, self.coarse_ray_sample, self.fine_ray_sample, rays.shape[1]
         p.retiming, p.only_coarse = int(retiming), int(only_coarse)
@@ -405,9 +476,11 @@ class LayeredRFRender(nn.Module):
         for i in range(1, l):
             if not self.is_shown_layer(i):
                 continue
-            nets.space[i], nets.space_fine[i] = ptr(self.spacenets[i - 1]), ptr(self.spacenets_fine[i - 1])
+            j = self._module_index(i)                                # (an instance: its source's blobs, the same pointers)
+            nets.space[i], nets.space_fine[i] = ptr(self.spacenets[j]), ptr(self.spacenets_fine[j])
             if self.use_deform_time:
-                nets.motion[i] = ptr(self.time_deform_nets[i - 1])
+                nets.motion[i] = ptr(self.time_deform_nets[j])
+        table = self._layer_alpha_table()
         need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse)
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != rays.device:
@@ -425,7 +498,8 @@ class LayeredRFRender(nn.Module):
         try:
             return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
                                    u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
-                                   **(dict(scene=True) if scene else {}))
+                                   **(dict(scene=True) if scene else {}),
+                                   **(dict(layer_alpha=table) if table is not None else {}))
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
                 cache.discard(key)             # (never filled)
@@ -455,14 +529,14 @@ class LayeredRFRender(nn.Module):
                                "(model.shard_views = False)")
         raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True)
         sc = raw[5]
-        scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.layer_num + 1)]
+        scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.total_layers)]
         return self.as_reference_tuple(raw[:5]), scene
 
     def as_reference_tuple(self, raw):
         """(mixed_fine (n,5), mixed_coarse (n,5), layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l)) -> the
         reference's 5-tuple of (color (n,3), depth (n,1), acc (n,1)) triples and bool masks (layered_rfrender.py:725-734)."""
         mix_f, mix_c, lo_f, lo_c, mask = raw
-        l = self.layer_num + 1
+        l = self.total_layers
         trip = lambda x: None if x is None else (x[:, 0:3], x[:, 3:4], x[:, 4:5])
         fine_layer = None if lo_f is None else [trip(lo_f[:, i]) for i in range(l)]
         coarse_layer = None if lo_c is None else [trip(lo_c[:, i]) for i in range(l)]
@@ -498,7 +572,7 @@ class LayeredRFRender(nn.Module):
         if not rays.is_cuda:
             raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
         rays = rays.contiguous().float()
-        N, L = rays.shape[0], self.layer_num
+        N, L = rays.shape[0], self.total_layers - 1      # (performers and instances: one frame-id column each with retiming)
         width = rays.shape[1]
         if width == 7:
             retiming = False
@@ -526,6 +600,13 @@ class LayeredRFRender(nn.Module):
         # sets up -> the same stages launched op by op with autograd history (stnerf_amd.modeling.training).  In eval() mode the
         # inference kernels run and the outputs carry no history, as under torch.no_grad() (render/layered_neural_renderer.py:377).
         train = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+        if train or per_sample_bkgd_time:
+            what = self._inference_only_edits()
+            if what is not None:
+                raise NotImplementedError(f"{what} on the op-by-op path (training, and batches that mix background frame ids under "
+                                          "BKGD_USE_SPACE_TIME): a render-time edit, as rotation is -- call model.eval() or wrap the "
+                                          "render in torch.no_grad(), and clear_instances() / layer_alpha = None to train")
+        self._layer_alpha_table()          # (its ValueErrors before anything is launched)
         self._warn_if_eval_with_grad()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None
@@ -541,7 +622,7 @@ class LayeredRFRender(nn.Module):
                     c0 = c
         else:
             fid = rays[:, 6].to(torch.int64) - 1
-            bb = self.bboxes.to(rays.device).float().index_select(0, fid)                          # :193
+            bb = self._box_table().to(rays.device).float().index_select(0, fid)                    # :193
             bk = self.bkgd_bbox.to(rays.device).float().unsqueeze(0).expand(N, 1, 8, 3)
             boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
             groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))

@@ -124,6 +124,10 @@ def render_rays_train(model, rays, boxes, pivot, retiming: bool, only_coarse: bo
     if getattr(model, "rotation", None) is not None and any(r is not None for r in model.rotation):
         raise NotImplementedError("per-layer rotation is a render-time edit: this op-by-op path (training, and batches that mix "
                                   "background frame ids under BKGD_USE_SPACE_TIME) does not apply it -- clear model.rotation")
+    what = model._inference_only_edits() if hasattr(model, "_inference_only_edits") else None
+    if what is not None:
+        raise NotImplementedError(f"{what}: a render-time edit, which this op-by-op path (training, and batches that mix background "
+                                  "frame ids under BKGD_USE_SPACE_TIME) does not apply -- clear_instances() / layer_alpha = None")
     n1, n2 = model.coarse_ray_sample, model.fine_ray_sample
     times_col = (lambda i: 6 + i) if retiming else (lambda i: 6)
     ec, ef = model._point_edits(l, False), model._point_edits(l, True)

@@ -630,13 +630,16 @@ def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Te
 
 
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
-                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False):
+                jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
+                layer_alpha: Optional[Sequence[float]] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
     (stnerf_render_rays_cached; mode hip.BKGD_CACHE_CAPTURE fills the two tensors, hip.BKGD_CACHE_REUSE renders from them).
     ``rotations``: per layer None | (m, centre), the pairs of ``LayeredRFRender.layer_ray_transforms`` (stnerf_render_rays_rot).
-    ``scene``: append the in-scene layer passes of the final stage, (n,l,5) (stnerf_render_rays_scene), to the returned tuple."""
+    ``scene``: append the in-scene layer passes of the final stage, (n,l,5) (stnerf_render_rays_scene), to the returned tuple.
+    ``layer_alpha``: params.l density factors, one per layer, for the fine composite (stnerf_render_rays_opacity; the library
+    refuses an entry that is negative or not finite); params.alpha is ignored then.  None: params.alpha on layer 2, as ever."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -663,7 +666,13 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
             raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
         bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
-    if scene:
+    if layer_alpha is not None:
+        if len(layer_alpha) != l:
+            raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
+        table = (C.c_float * l)(*(float(a) for a in layer_alpha))
+        hip.check(hip.lib().stnerf_render_rays_opacity(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
+                                                       hip.stream_ptr()), "stnerf_render_rays_opacity")
+    elif scene:
         hip.check(hip.lib().stnerf_render_rays_scene(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), hip.stream_ptr()),
                   "stnerf_render_rays_scene")
     elif rot is not None:

@@ -214,6 +214,21 @@ def check_collective(fingerprint, what: str, group=None, device=None) -> None:
                            "ranks render different views")
 
 
+def total_layers(model) -> int:
+    """l of a model: the background, the performers and the layer instances (``LayeredRFRender.total_layers``)."""
+    return int(getattr(model, "total_layers", model.layer_num + 1))
+
+
+def layers_fingerprint(model):
+    """The layer instances and per-layer opacities of a model as a fixed number of floats (``check_collective``): ranks that
+    disagree on them would render different layer counts into one all-gather."""
+    cap = 16                                                # (STNERF_MAX_LAYERS)
+    src = [float(x) for x in getattr(model, "instances", ())]
+    alpha = getattr(model, "layer_alpha", None)
+    al = [] if alpha is None else [1.0 if a is None else float(a) for a in alpha]
+    return [len(src)] + (src + [0.0] * cap)[:cap] + [-1.0 if alpha is None else len(al)] + (al + [-1.0] * cap)[:cap]
+
+
 def rays_fingerprint(rays: torch.Tensor):
     """N, the width, and three cheap checksums of a ray tensor (one tiny D2H)."""
     n = rays.shape[0]
@@ -319,7 +334,7 @@ def gather_stripes(local: torch.Tensor, n_total: int, stripe: int, rank: int, wo
 
 def _render_local(model, local_rays, window, n_total, stripe, rank, world, group, only_coarse, thr, bthr, chuncks, replay_full):
     """This rank's stripes through the model (ray window set: the RNG stream is the view's), packed, gathered, unpacked."""
-    l = model.layer_num + 1
+    l = total_layers(model)
     mode = gather_mode(model)
     saved_window, saved_replay = model.ray_window, model.replay
     try:
@@ -346,8 +361,8 @@ def render_rays_sharded(model, rays, chuncks: int, density_threshold=0.0, bkgd_d
     launch sequence and the whole 5-tuple is rebuilt on every rank by one all-gather.  Bitwise equal to the unsharded
     render: the device RNG is keyed by the ray's index in the view."""
     rank, world, group = act or active_group(model)
-    check_collective(rays_fingerprint(rays) + [chuncks, float(density_threshold), float(bkgd_density_threshold), int(model.seed) % (1 << 52)],
-                     "layered_batchify_ray (sharded)", group, rays.device)
+    check_collective(rays_fingerprint(rays) + [chuncks, float(density_threshold), float(bkgd_density_threshold), int(model.seed) % (1 << 52)]
+                     + layers_fingerprint(model), "layered_batchify_ray (sharded)", group, rays.device)
     local = take_stripes(rays, chuncks, rank, world)
     return _render_local(model, local, (rank * chuncks, chuncks, world * chuncks), rays.shape[0], chuncks, rank, world, group,
                          only_coarse, density_threshold, bkgd_density_threshold, chuncks, model.replay)
@@ -395,11 +410,11 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     mode = gather_mode(model) if gather is None else gather
     check_collective([h, w, stripe_rows, chuncks, float(density_threshold), float(bkgd_density_threshold), int(model.seed) % (1 << 52)]
                      + torch.as_tensor(K, dtype=torch.float64).flatten().tolist() + torch.as_tensor(T, dtype=torch.float64).flatten().tolist()
-                     + [float(f) for f in frame_ids], "render_view (sharded)", group, device)
+                     + layers_fingerprint(model) + [float(f) for f in frame_ids], "render_view (sharded)", group, device)
     packed = render_view_share(model, K, T, h, w, frame_ids, rank, world, density_threshold, bkgd_density_threshold, chuncks,
                                stripe_rows, device, mode)
     whole = gather_stripes(packed, n_total, stripe, rank, world, group)
-    return model.as_reference_tuple(unpack_outputs(whole, model.layer_num + 1, mode))
+    return model.as_reference_tuple(unpack_outputs(whole, total_layers(model), mode))
 
 
 def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: int, density_threshold=0.0,
@@ -414,7 +429,7 @@ def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: 
     stripe = w * max(1, int(stripe_rows))
     window = (rank * stripe, stripe, world * stripe)
     n_local = ops.window_size(n_total, *window)
-    l = model.layer_num + 1
+    l = total_layers(model)
     if n_local == 0:                          # more ranks than stripes: only the collective (and the seed) on this rank
         model.advance_seed()
         return torch.zeros((0, packed_width(l, mode)), dtype=torch.float32, device=device)

@@ -32,7 +32,8 @@ from stnerf_amd.render.render_pose import render_pose as _render_pose
 class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
-                 model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False):
+                 model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
+                 layer_alpha=None, s_layer_alpha=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -50,6 +51,15 @@ class LayeredNeuralRenderer:
                     any((a is None) != (b is None) for a, b in zip(s_rotation[0], s_rotation[1])):
                 raise ValueError("s_rotation is (start, end): two per-layer angle lists with None in the same places")
             self.rotation = list(s_rotation[0])
+        # layer_alpha: one opacity per layer (None = 1.0; LayeredRFRender.layer_alpha: every layer's density factor in the fine
+        # composite, where `alpha` reaches layer 2 alone); s_layer_alpha = (start, end), interpolated per frame like s_rotation.
+        # Not in the reference (keyword-only)
+        self.layer_alpha, self.s_layer_alpha = layer_alpha, s_layer_alpha
+        if s_layer_alpha is not None:
+            if len(s_layer_alpha) != 2 or len(s_layer_alpha[0]) != len(s_layer_alpha[1]) or \
+                    any((a is None) != (b is None) for a, b in zip(s_layer_alpha[0], s_layer_alpha[1])):
+                raise ValueError("s_layer_alpha is (start, end): two per-layer opacity lists with None in the same places")
+            self.layer_alpha = list(s_layer_alpha[0])
         if s_shift is not None:
             self.shift = self.s_shift[0]
         if s_scale is not None:
@@ -59,6 +69,7 @@ class LayeredNeuralRenderer:
         self.model = model
         self.model.scale, self.model.shift = self.scale, self.shift
         self.model.rotation = self.rotation
+        self.model.layer_alpha = self.layer_alpha
         self.cache_background = cache_background
         # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
         # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
@@ -66,13 +77,13 @@ class LayeredNeuralRenderer:
         self.scene_passes = bool(scene_passes)
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
-        self.display_layers = {i: 1 for i in range(self.layer_num + 1)}
+        self.display_layers = {i: 1 for i in range(self.total_layers)}
         self.gt_poses = torch.as_tensor(gt_poses, dtype=torch.float32)
         self.gt_Ks = [torch.as_tensor(k, dtype=torch.float32) for k in gt_Ks]
         self.far = 20.0
         off = cfg.DATASETS.FRAME_OFFSET
-        self.min_frame = [1 + off for _ in range(self.layer_num + 1)]
-        self.max_frame = [self.frame_num + off for _ in range(self.layer_num + 1)]
+        self.min_frame = [1 + off for _ in range(self.total_layers)]
+        self.max_frame = [self.frame_num + off for _ in range(self.total_layers)]
         self.images, self.depths = [], []
         self.image_num = 0
         self.camera_num = self.gt_poses.shape[0]
@@ -85,6 +96,42 @@ class LayeredNeuralRenderer:
         self.layer_frame_pairs: List = []
         self.trace_layer = -1
         self.dir_name = ''
+
+    @property
+    def total_layers(self):
+        """l: the background, the cfg's performers and the model's layer instances (``duplicate_layer``)."""
+        return int(getattr(self.model, "total_layers", self.layer_num + 1))
+
+    def duplicate_layer(self, src, *, shift=None, scale=None, rotation=None, alpha=None):
+        """Show performer ``src`` a second time -> the copy's layer id (``LayeredRFRender.add_instance``: the source's networks,
+        no second copy of them).  The copy is a layer like any other: it starts with the source's frame span, and
+        ``set_frame_duration(..., layer_id)`` / ``retime_by_key_frames(layer_id, ...)`` retime it on its own; ``shift``, ``scale``,
+        ``rotation`` and ``alpha`` are its entries of the per-layer edit lists, which grow by one (a list that was None is created
+        with neutral entries -- zero shift, scale 1, no rotation, opaque -- when the copy needs it; a list that already has an
+        entry for the new layer, such as the start of an ``s_*`` schedule given with the final layer count, keeps it unless
+        the argument names another).  Call it before any path setter: the (layer, frame) pairs of a path are laid out for
+        the layers that exist then.  Not in the reference."""
+        if self.layer_frame_pairs:
+            raise RuntimeError("duplicate_layer after a path setter: the path's (layer, frame) pairs are already laid out -- "
+                               "duplicate the layers first, then set the path")
+        layer_id = self.model.add_instance(src)
+        self.display_layers[layer_id] = 1
+        self.min_frame = list(self.min_frame[:layer_id]) + [self.min_frame[src]]
+        self.max_frame = list(self.max_frame[:layer_id]) + [self.max_frame[src]]
+
+        def grown(cur, value, neutral):
+            if cur is None and value is None:
+                return None
+            out = list(cur) if cur is not None else []
+            out += [neutral() for _ in range(layer_id + 1 - len(out))]
+            if value is not None:
+                out[layer_id] = value
+            return out
+        self.shift = self.model.shift = grown(self.shift, shift, lambda: [0.0, 0.0, 0.0])
+        self.scale = self.model.scale = grown(self.scale, scale, lambda: 1.0)
+        self.rotation = self.model.rotation = grown(self.rotation, rotation, lambda: None)
+        self.layer_alpha = self.model.layer_alpha = grown(self.layer_alpha, alpha, lambda: None)
+        return layer_id
 
     @property
     def cache_background(self):
@@ -124,8 +171,8 @@ class LayeredNeuralRenderer:
 
     def set_frame_duration(self, min_frame, max_frame, layer_id=-1):
         if layer_id == -1:
-            self.min_frame = [min_frame for _ in range(self.layer_num + 1)]
-            self.max_frame = [max_frame for _ in range(self.layer_num + 1)]
+            self.min_frame = [min_frame for _ in range(self.total_layers)]
+            self.max_frame = [max_frame for _ in range(self.total_layers)]
         else:
             self.min_frame[layer_id], self.max_frame[layer_id] = min_frame, max_frame
 
@@ -143,7 +190,7 @@ class LayeredNeuralRenderer:
     def _append_layer_frame_pairs(self, n_poses, smooth_time=False):
         for idx in range(n_poses + 1):
             pair = []
-            for layer_id in range(self.layer_num + 1):
+            for layer_id in range(self.total_layers):
                 if self.is_shown_layer(layer_id):
                     span = (self.max_frame[layer_id] - self.min_frame[layer_id]) / n_poses * idx
                     frame_id = (span if smooth_time else int(span)) + self.min_frame[layer_id]
@@ -151,7 +198,14 @@ class LayeredNeuralRenderer:
             self.layer_frame_pairs.append(pair)
 
     def _edit_schedule(self, n):
-        """Linear per-frame schedules of the editing knobs (:232-243, :279-301)."""
+        """Linear per-frame schedules of the editing knobs (:232-243, :279-301).  A per-layer schedule has one entry per layer
+        of ``total_layers`` (the layer instances included), else ValueError."""
+        l = self.total_layers
+        for name in ("s_shift", "s_scale", "s_rotation", "s_layer_alpha"):
+            sched = getattr(self, name)
+            if sched is not None and (len(sched[0]) != l or len(sched[1]) != l):
+                raise ValueError(f"{name} must have one entry per layer ({l}, layer 0 = the background, layer instances included), "
+                                 f"got {len(sched[0])} and {len(sched[1])}")
         if self.s_shift is not None:
             a, b = np.array(self.s_shift[0]), np.array(self.s_shift[1])
             step = (b - a) / (n - 1)
@@ -167,6 +221,9 @@ class LayeredNeuralRenderer:
         if self.s_rotation is not None:
             lerp = lambda a, b, i: None if a is None else a + i * ((b - a) / (n - 1))
             self.s_rotation_frame = [[lerp(a, b, i) for a, b in zip(*self.s_rotation)] for i in range(n)]
+        if self.s_layer_alpha is not None:
+            lerp = lambda a, b, i: None if a is None else a + i * ((b - a) / (n - 1))
+            self.s_layer_alpha_frame = [[lerp(a, b, i) for a, b in zip(*self.s_layer_alpha)] for i in range(n)]
 
     # ---- camera paths ---------------------------------------------------------------------------------------
     def set_smooth_path_poses(self, step_num, around=False, smooth_time=False):
@@ -288,10 +345,10 @@ class LayeredNeuralRenderer:
         the device tensors (write files there); with ``scene_passes`` it also gets ``scene=`` the frame's dict of in-scene layer
         passes, which are kept in ``self.images_scene`` / ``self.alphas_scene`` next to ``images_layer``."""
         self.images, self.depths = [], []
-        self.images_layer = [[] for _ in range(self.layer_num + 1)]
-        self.depths_layer = [[] for _ in range(self.layer_num + 1)]
-        self.images_scene = [[] for _ in range(self.layer_num + 1)]
-        self.alphas_scene = [[] for _ in range(self.layer_num + 1)]
+        self.images_layer = [[] for _ in range(self.total_layers)]
+        self.depths_layer = [[] for _ in range(self.total_layers)]
+        self.images_scene = [[] for _ in range(self.total_layers)]
+        self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -302,6 +359,8 @@ class LayeredNeuralRenderer:
                 self.model.alpha = self.s_alpha_frame[idx]
             if self.s_rotation is not None:
                 self.model.rotation = self.s_rotation_frame[idx]
+            if self.s_layer_alpha is not None:
+                self.model.layer_alpha = self.s_layer_alpha_frame[idx]
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
                                                                                 inverse_y_axis)
             if on_frame is not None:
@@ -309,7 +368,7 @@ class LayeredNeuralRenderer:
             if auto_save:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
-                for layer_id in range(self.layer_num + 1):
+                for layer_id in range(self.total_layers):
                     if self.is_shown_layer(layer_id):
                         self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                         self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
@@ -327,10 +386,10 @@ class LayeredNeuralRenderer:
         compositor's own occlusion, are kept in ``self.images_scene`` / ``self.alphas_scene`` and given to ``on_frame`` as ``scene=``
         (``color_hide`` stays the reference's computation)."""
         self.images, self.depths, self.images_hide = [], [], []
-        self.images_layer = [[] for _ in range(self.layer_num + 1)]
-        self.depths_layer = [[] for _ in range(self.layer_num + 1)]
-        self.images_scene = [[] for _ in range(self.layer_num + 1)]
-        self.alphas_scene = [[] for _ in range(self.layer_num + 1)]
+        self.images_layer = [[] for _ in range(self.total_layers)]
+        self.depths_layer = [[] for _ in range(self.total_layers)]
+        self.images_scene = [[] for _ in range(self.total_layers)]
+        self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.image_num = 0
         for idx in range(len(self.poses)):
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
@@ -349,7 +408,7 @@ class LayeredNeuralRenderer:
                 self.depths.append(depth.cpu())
                 if color_hide is not None:
                     self.images_hide.append(color_hide.cpu())
-                for layer_id in range(self.layer_num + 1):
+                for layer_id in range(self.total_layers):
                     self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                     self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
                     if passes is not None:

@@ -10,7 +10,7 @@ from typing import Sequence, Tuple
 
 import torch
 
-from stnerf_amd.parallel import render_view
+from stnerf_amd.parallel import render_view, total_layers
 
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
@@ -31,8 +31,7 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     image lists on the device: ``color_scene`` (H,W,3) premultiplied, ``alpha_scene`` (H,W,1), ``depth_scene`` (H,W,1) = the
     weighted depth / far, not clamped.  Their sums over the layers are the mixed colour, alpha and (unclamped) depth.  One rank
     only."""
-    L = model.layer_num
-    frame_ids = [0.0] * (L + 1)
+    frame_ids = [0.0] * total_layers(model)       # (the layer instances have their own frame ids)
     for layer_id, frame_id in layer_frame_pair:
         frame_ids[layer_id] = float(frame_id)
     out = render_view(model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width,
