@@ -24,6 +24,12 @@ colour by up to 1e-3.  This file calls torch.sort as the reference does (so on s
 algorithm); the HIP compositor merges in the order of a stable sort; make_golden.py keeps such rays out of the
 one fixture large enough to contain them (rays_with_depth_ties).
 
+Beyond the reference: four render-time features of this project are not in it -- per-layer rotation,
+layer instances, the per-layer opacity table and the in-scene layer passes.  They are stated here as well (``OracleModel.sources`` /
+``rotation`` / ``layer_alpha``, ``layer_rays``, ``scene_passes``), restated from DESIGN.md's text and include/stnerf.h's formula and
+from no host code of the product; no fixture can pin them, tests/test_oracle_scene_edits_cpu.py holds them to the rest of this
+file instead.  All are absent by default, and then every line below computes what it computed before them.
+
 Teacher forcing (``render_chunk(forced=...)``, round 6): the fine depths and deformed points of a recorded
 reference run replace the oracle's own, so that an fp64 evaluation sits on the reference's positions.
 """
@@ -102,16 +108,21 @@ def intersection(rays: Tensor, bbox: Tensor) -> Tensor:
     return tl.topk(k=2, dim=-1)[0]
 
 
-def sample_coarse(rays: Tensor, boxes: Tensor, n_coarse: int, jitter: Sequence[Tensor]):
+def sample_coarse(rays: Tensor, boxes: Tensor, n_coarse: int, jitter: Sequence[Tensor],
+                  layer_rays: Optional[Sequence[Tensor]] = None):
     """RaySamplePoint.forward (:70-107).  boxes (n, l, 8, 3); jitter[i] (n, n_coarse) in [0,1).
 
     Returns lists over layers of t (n,N1,1), xyz (n,N1,3), mask (n,) bool.
     Layer 0 clamps a non-positive near hit to 0 (:93-95); performers keep it.  mask = |bin|>1e-5.
+    ``layer_rays`` (not in the reference; DESIGN.md section 7, per-layer rotation): layer i is sampled on layer_rays[i]
+    (n, >=6), the ray as that layer sees it, instead of ``rays`` -- the slab test, the clamp and the points alike.
     """
     n, l = rays.shape[0], boxes.shape[1]
     k = torch.arange(0, n_coarse, dtype=rays.dtype).reshape(1, n_coarse)
     ts, pts, masks = [], [], []
+    every = rays
     for i in range(l):
+        rays = every if layer_rays is None else layer_rays[i]
         far_near = intersection(rays, boxes[:, i])
         start = far_near[:, 1].reshape(n, 1).clone()
         if i == 0:
@@ -343,9 +354,22 @@ class OracleModel:
     scale: Optional[list] = None              # :39
     shift: Optional[list] = None              # :40
     hidden: set = field(default_factory=set)  # display_layers :99-112
+    # ---- not in the reference: the scene edits of DESIGN.md section 7, restated from its text.  All default to "absent"
+    sources: tuple = ()                       # layer instances: layer layer_num + 1 + j shows performer sources[j] (1..layer_num) again
+    rotation: Optional[list] = None           # per layer of l: None | (m (3,3) = R^T, c (3,) | None = the centre of the layer's edited box)
+    layer_alpha: Optional[list] = None        # per layer of l: None (= 1) | the factor on that layer's fine density; alpha is ignored then
 
     def is_shown_layer(self, i: int) -> bool:
         return i not in self.hidden
+
+    @property
+    def performers(self) -> int:
+        """l - 1: the performers and the instances, each with a box column, a frame-id column and an entry of every per-layer list."""
+        return self.layer_num + len(self.sources)
+
+    def module_of(self, i: int) -> int:
+        """Index into spacenets / spacenets_fine / time_deform_nets of layer i >= 1: its own, or (an instance) its source's."""
+        return (i if i <= self.layer_num else self.sources[i - self.layer_num - 1]) - 1
 
 
 RandFn = Callable[[Tuple[int, int]], Tensor]
@@ -363,8 +387,11 @@ def layer_boxes(m: OracleModel, rays: Tensor):
     for the whole chunk, from ROW 0's frame id, lerped between floor/ceil frame, :195-200,
     :123-127).  Edit (:216-242): pivot = mean of the frame-0 centres of layers 1 and 2 with
     centre.z := corner-1 z; boxes[i] = (boxes[i]-pivot)*scale[i]+pivot; boxes[i] += shift[i].
+    Instances: the box column of every instance's source is appended to the table first, so the ray
+    width, retiming, the pivot ("layers 1 and 2 of the table") and the edits count l = 1 + L + K layers.
     """
-    n, L = rays.shape[0], m.layer_num
+    n, L = rays.shape[0], m.performers
+    table = m.bboxes if not m.sources else torch.cat([m.bboxes] + [m.bboxes[:, s - 1:s] for s in m.sources], 1)
     width = rays.shape[1]
     if width == 7:
         retiming, frame_id = False, rays[:, -1]
@@ -373,15 +400,15 @@ def layer_boxes(m: OracleModel, rays: Tensor):
     else:
         raise ValueError(f"undefined ray format, ray dimension is {width}")  # :161-163 (exit(-1))
     if not retiming:
-        boxes = m.bboxes.index_select(0, frame_id.type(torch.int64) - 1)
+        boxes = table.index_select(0, frame_id.type(torch.int64) - 1)
     else:
         boxes = torch.zeros(n, L, 8, 3, dtype=rays.dtype)
         for i in range(L):
             f = frame_id[0, i + 1] - 1
-            lo, hi = m.bboxes[math.floor(f), i], m.bboxes[math.ceil(f), i]
+            lo, hi = table[math.floor(f), i], table[math.ceil(f), i]
             boxes[:, i] = torch.lerp(lo, hi, f - math.floor(f))
     boxes = torch.cat([m.bkgd_bbox.unsqueeze(0).repeat(n, 1, 1, 1), boxes], 1)
-    first = torch.cat([m.bkgd_bbox, m.bboxes[0, :]], 0)            # (l,8,3) frame-0 boxes
+    first = torch.cat([m.bkgd_bbox, table[0, :]], 0)               # (l,8,3) frame-0 boxes
     centre = torch.mean(first, 1)                                   # (l,3)
     centre[:, 2] = first[:, 1, 2]                                   # :226
     pivot = None
@@ -397,10 +424,58 @@ def layer_boxes(m: OracleModel, rays: Tensor):
     return boxes, pivot, retiming, frame_id
 
 
+def layer_rays(m: OracleModel, rays: Tensor, boxes: Tensor) -> Optional[list]:
+    """Per layer the (n,6) ray [o', d'] that layer sees, or None when the model carries no rotation.  Not in the reference:
+    DESIGN.md section 7 / include/stnerf.h (stnerf_layer_rotation), restated one operation at a time in the dtype of the rays:
+
+        m = R^T, c = centre, q = o - c
+        o'[r] = ((m[r,0] q[0] + m[r,1] q[1]) + m[r,2] q[2]) + c[r]
+        d'[r] =  (m[r,0] d[0] + m[r,1] d[1]) + m[r,2] d[2]                    r = 0, 1, 2
+
+    An entry is None (the layer sees the ray itself) or (m, c): m holds fp32 numbers and c is rounded to fp32 (what the library
+    is handed), both then cast to the dtype of the rays.  c = None: the mean of the 8 corners of the layer's EDITED box of the
+    chunk, boxes[0, i] -- row 0's, as the boxes of a retimed chunk are."""
+    if m.rotation is None:
+        return None
+    if len(m.rotation) != boxes.shape[1]:
+        raise ValueError(f"rotation must have one entry per layer ({boxes.shape[1]}), got {len(m.rotation)}")
+    o, d = rays[:, 0:3], rays[:, 3:6]
+    out = []
+    for i, entry in enumerate(m.rotation):
+        if entry is None:
+            out.append(rays[:, 0:6])
+            continue
+        mat, c = entry
+        mat = torch.as_tensor(mat).to(torch.float32).to(rays.dtype)
+        c = torch.mean(boxes[0, i], 0) if c is None else torch.as_tensor(c, dtype=torch.float32).to(rays.dtype)
+        q = [o[:, j] - c[j] for j in range(3)]
+        cols = [((mat[r, 0] * q[0] + mat[r, 1] * q[1]) + mat[r, 2] * q[2]) + c[r] for r in range(3)]
+        cols += [(mat[r, 0] * d[:, 0] + mat[r, 1] * d[:, 1]) + mat[r, 2] * d[:, 2] for r in range(3)]
+        out.append(torch.stack(cols, dim=1))
+    return out
+
+
+def scene_passes(w_mix: Tensor, order: Tensor, ts: Sequence[Tensor], rgbs: Sequence[Tensor]):
+    """The in-scene layer passes of a merged composite (not in the reference).  w_mix (n, l S[, 1]): the
+    merged composite's weights in merged order; order (n, l S[, 1]): the sort index that merged the concatenated lists;
+    ts[i] (n,S[,1]) and rgbs[i] (n,S,3) raw: layer i's depths and colours.  ->
+    merged_weights (n,l,S): every sample's merged weight back at its source index, and scene: per layer the triple
+    (colour (n,3), depth (n,1), alpha (n,1)) = sum_k w {sigmoid(rgb), t, 1} over that layer's samples -- its share of the
+    mixed image, whose sum over the layers is the mixed triple."""
+    n, l, S = w_mix.shape[0], len(ts), rgbs[0].shape[1]
+    w = torch.zeros(n, l * S, dtype=w_mix.dtype).scatter_(1, order.reshape(n, l * S), w_mix.reshape(n, l * S)).reshape(n, l, S)
+    scene = []
+    for i in range(l):
+        wi = w[:, i].unsqueeze(-1)
+        scene.append((torch.sum(torch.sigmoid(rgbs[i]) * wi, dim=1), torch.sum(wi * ts[i].reshape(n, S, 1), dim=1),
+                      torch.sum(wi, dim=1)))
+    return w, scene
+
+
 def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
                  density_threshold: float = 0.0001, bkgd_density_threshold: float = 0.0,
                  rand: RandFn = _default_rand, trace: Optional[dict] = None, sample_dtype: Optional[torch.dtype] = None,
-                 forced: Optional[dict] = None):
+                 forced: Optional[dict] = None, scene: bool = False):
     """LayeredRFRender.forward for one chunk (BBOX sampling, no pose refinement / view deform /
     background deform, background net without time: the configuration of both shipped ymls).
 
@@ -415,12 +490,25 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
     hit rays or None} -- the reference's own new fine depths (the value of sample_pdf at :460) and the points its performer SpaceNets
     were given (:355-356, :509-510), recorded by tests/golden/make_golden.py --grads --teacher: the networks are evaluated on those
     (the deformation nets keep their place in the graph: value replaced, gradient passed).
+
+    The scene edits of DESIGN.md section 7 (``OracleModel.sources`` / ``rotation`` / ``layer_alpha``; none is in the reference, each
+    is restated from that text): an instance is one more performer on its source's modules and box column; a rotated layer
+    is sampled, given its points and its colour branch's direction on the ray it sees (``layer_rays``); ``layer_alpha[i]``
+    multiplies layer i's FINE density after the threshold cuts, where ``alpha`` acts on layer 2 (the coarse pass and
+    ``only_coarse`` ignore it, and ``alpha`` is ignored while a table is set).  ``scene=True`` appends a sixth entry, the
+    in-scene layer passes of the final stage (``scene_passes``; the coarse stage's under ``only_coarse``), one (colour, depth,
+    alpha) triple per layer; ``trace`` receives them with ``merged_weights`` either way.
     """
-    n, L = rays.shape[0], m.layer_num
+    n, L = rays.shape[0], m.performers
     l, N1, N2 = L + 1, m.n_coarse, m.n_fine
     P = m.params
     boxes, pivot, retiming, frame_id = layer_boxes(m, rays)
     o, d = rays[:, 0:3], rays[:, 3:6]
+    seen = layer_rays(m, rays, boxes)                     # None: every layer sees (o, d)
+    o_of = (lambda i: o) if seen is None else (lambda i: seen[i][:, 0:3])
+    d_of = (lambda i: d) if seen is None else (lambda i: seen[i][:, 3:6])
+    if m.layer_alpha is not None and len(m.layer_alpha) != l:
+        raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(m.layer_alpha)}")
 
     def fid(i):  # per-ray frame id of layer i
         return frame_id[:, i] if retiming else frame_id
@@ -450,7 +538,7 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
             if torch.sum(idx) == 0:
                 continue
             tid = fid(i)[idx].view(-1, 1, 1).repeat(1, ns, 1)
-            flow = motion_net(P, f"time_deform_nets.{i - 1}", torch.cat([x[i][idx], tid], -1))
+            flow = motion_net(P, f"time_deform_nets.{m.module_of(i)}", torch.cat([x[i][idx], tid], -1))
             moved = x[i][idx] + flow
             if given is not None and given[i] is not None:
                 moved = given[i].to(moved.dtype) + (moved - moved.detach())
@@ -467,9 +555,11 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
         # ray i gets the frame id of ray (i S + j) mod n.  Invisible when every ray of the call has the same background frame id (any
         # rendered frame); a training batch with BKGD_USE_SPACE_TIME mixes the ids across rays.  Restated as the reference does it.
         t0 = fid(0).reshape(-1).repeat(ns).reshape(n, ns, 1) if m.use_space_time else None
-        c0, s0 = space_net(P, "bkgd_spacenet" + sfx, x[0], d, t0)
+        c0, s0 = space_net(P, "bkgd_spacenet" + sfx, x[0], d_of(0), t0)
         if fine and retiming:
             s0[s0 < bkgd_density_threshold] = 0                           # :538-547
+        if fine and m.layer_alpha is not None and m.layer_alpha[0] is not None:
+            s0 = s0 * m.layer_alpha[0]                                    # (the table includes layer 0)
         rgbs.append(c0)
         sig.append(s0)
         for i in range(1, l):                                             # :397-418 / :552-576
@@ -479,23 +569,27 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
             if torch.sum(idx) == 0 or not m.is_shown_layer(i):
                 continue
             times = fid(i)[idx].reshape(-1, 1) if m.use_space_time else None
-            ci, si = space_net(P, f"spacenets{sfx}.{i - 1}", x[i][idx], d[idx], times)
+            ci, si = space_net(P, f"spacenets{sfx}.{m.module_of(i)}", x[i][idx], d_of(i)[idx], times)
             rgbs[i][idx] = ci
             sig[i][idx] = si
             if not fine:
                 sig[i][ts[i][:, :, 0] < 0, :] = 0.0                       # :414
             if retiming:
                 sig[i][sig[i] < density_threshold] = 0                    # :416-418 / :564-566
-            if fine and i == 2:
+            if fine and m.layer_alpha is not None:
+                if m.layer_alpha[i] is not None:
+                    sig[i] = sig[i] * m.layer_alpha[i]                    # (where alpha acts, for every layer)
+            elif fine and i == 2:
                 sig[i] = sig[i] * m.alpha                                 # :575-576
         return rgbs, sig
 
     # ---- coarse
     jitter = [rand((n, N1)).to(rays.dtype) for _ in range(l)]
     if sample_dtype is None:
-        ts, xyz, masks = sample_coarse(rays, boxes, N1, jitter)
+        ts, xyz, masks = sample_coarse(rays, boxes, N1, jitter, seen)
     else:
-        ts, xyz, masks = sample_coarse(rays.to(sample_dtype), boxes.to(sample_dtype), N1, [j.to(sample_dtype) for j in jitter])
+        ts, xyz, masks = sample_coarse(rays.to(sample_dtype), boxes.to(sample_dtype), N1, [j.to(sample_dtype) for j in jitter],
+                                       None if seen is None else [r.to(sample_dtype) for r in seen])
         ts, xyz = [t_.to(rays.dtype) for t_ in ts], [x_.to(rays.dtype) for x_ in xyz]
     ts, xyz = [t_.detach() for t_ in ts], [x_.detach() for x_ in xyz]      # :314-315 (only matters under autograd)
     xyz = [unedit(xyz[i], i, False) for i in range(l)]
@@ -513,7 +607,12 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
     pack = lambda c: (c[0], c[1], c[2])
     if only_coarse:                                                       # :684-722
         cl = [pack(c) for c in coarse_layer]
-        return pack(coarse_mixed), pack(coarse_mixed), cl, cl, masks
+        out = (pack(coarse_mixed), pack(coarse_mixed), cl, cl, masks)
+        if scene or trace is not None:
+            merged_w, passes = scene_passes(coarse_mixed[3], order, ts, rgbs)
+            if trace is not None:
+                trace.update(merged_weights=merged_w, scene=passes)
+        return out + (passes,) if scene else out
 
     # ---- fine
     zf, xf, us, zs = [], [], [], []
@@ -524,7 +623,7 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
         if forced and "z" in forced:
             z = forced["z"][i].to(sd_)
         zi, _ = torch.sort(torch.cat([ts[i].squeeze(-1).to(sd_), z], -1), -1)
-        pts = zi.unsqueeze(-1) * d.to(sd_).unsqueeze(1) + o.to(sd_).unsqueeze(1)
+        pts = zi.unsqueeze(-1) * d_of(i).to(sd_).unsqueeze(1) + o_of(i).to(sd_).unsqueeze(1)
         z, zi, pts = z.to(rays.dtype), zi.to(rays.dtype), pts.to(rays.dtype)
         us.append(u)
         zs.append(z)
@@ -542,8 +641,12 @@ def render_chunk(m: OracleModel, rays: Tensor, only_coarse: bool = False,
     if trace is not None:
         trace.update(u=us, z_new=zs, t_fine=zf, xyz_fine=xf, rgb_fine=rgbs, sigma_fine=sig,
                      order_fine=order, jitter=jitter)
-    return (pack(fine_mixed), pack(coarse_mixed), [pack(c) for c in fine_layer],
-            [pack(c) for c in coarse_layer], masks)
+    out = (pack(fine_mixed), pack(coarse_mixed), [pack(c) for c in fine_layer], [pack(c) for c in coarse_layer], masks)
+    if scene or trace is not None:
+        merged_w, passes = scene_passes(fine_mixed[3], order, zf, rgbs)
+        if trace is not None:
+            trace.update(merged_weights=merged_w, scene=passes)
+    return out + (passes,) if scene else out
 
 
 # --------------------------------------------------------------------------------------

@@ -2,8 +2,8 @@
 MERGED composite, stored at its source index, and `scene`, layer i's share of the mixed image (sum_k wM {r, g, b, t, 1}).
 Checked against the CPU oracle's composite of the stably sorted union, between the compositor's three routes bit for bit, for
 neutrality towards the outputs `ops.composite` returns, for exact zeros where a layer has no output / takes no part, for the
-identity sum_i scene[i] == mixed, for overruns, and through the whole pipeline up to `render_pose`.  Needs an MI355X:
-`pytest -m gpu`."""
+identity sum_i scene[i] == mixed, for `scene` layer by layer against the sums over the oracle's weights, for overruns, and
+through the whole pipeline up to `render_pose`.  Needs an MI355X: `pytest -m gpu`."""
 import ctypes as C
 import functools
 import types
@@ -100,10 +100,14 @@ def oracle_case(l, S, fine):
     mix = O.composite(t_mix, rgb_mix, sig_mix)
     want = torch.zeros(n, l * S).scatter_(1, order.squeeze(-1), mix[3].squeeze(-1)).reshape(n, l, S)   # back to the source index
     ok = torch.isfinite(mix[0]).all(-1) & torch.isfinite(mix[2]).all(-1)     # descending rows: inf / NaN in the reference too
+    # scene_out from those weights, in fp64: layer i's sum_k w {sigmoid(rgb), t, 1} over its own samples
+    w64 = want.double()
+    colour = torch.sigmoid(torch.stack(rgb, 1).double())
+    want_scene = torch.cat([(w64.unsqueeze(-1) * colour).sum(2), (w64 * t.double()).sum(2, keepdim=True), w64.sum(2, keepdim=True)], -1)
     got = ops.composite_scene(t.cuda(), raw.cuda(), mask.cuda(), near=NEAR, fine=fine, cut_negative_t=not fine,
                               thresholds=[BTHR if fine else None] + [THR] * (l - 1), evaluated=[2] + [1] * (l - 1),
                               sigma_scale=[1.0] * (l - 1) + [ALPHA if fine else 1.0], want_weights=True)
-    return dict(ok=ok, want=want, got=[None if g is None else g.cpu() for g in got])
+    return dict(ok=ok, want=want, want_scene=want_scene, got=[None if g is None else g.cpu() for g in got])
 
 
 # ---- the routes' configuration: a hidden performer (real depths, no output) as well; every route, raw and activated colours
@@ -224,6 +228,21 @@ def test_the_passes_sum_to_the_mixed_image(ops, l, S, fine):
           f"max |sum wM - acc| {float((mw.sum((1, 2))[ok] - mixed[ok][:, 4]).abs().max()):.3e}")
     torch.testing.assert_close(total[ok], mixed[ok], rtol=2e-5, atol=6e-6)
     torch.testing.assert_close(mw.sum((1, 2))[ok], mixed[ok][:, 4], rtol=2e-5, atol=6e-6)
+
+
+# ---- 6b
+@pytest.mark.parametrize("fine", [False, True])
+@pytest.mark.parametrize("l, S", ORACLE_SHAPES)
+def test_scene_out_matches_the_sums_over_the_oracles_weights(ops, l, S, fine):
+    """scene_out[:, i] against sum_k w {sigmoid(rgb), t, 1} formed in fp64 from the oracle's merged weights (test 1's
+    expectation), layer by layer: the sum over the layers (test 6) does not see two layers' passes swapped, nor a sample credited
+    to the wrong layer.  Bar: test 6's."""
+    c = oracle_case(l, S, fine)
+    ok, sc, want = c["ok"], c["got"][4], c["want_scene"]
+    assert sc.shape == want.shape == (ok.numel(), l, 5)
+    d = (sc[ok].double() - want[ok]).abs()
+    print(f"max |d| colour {float(d[..., :3].max()):.3e}, depth {float(d[..., 3].max()):.3e}, alpha {float(d[..., 4].max()):.3e}")
+    torch.testing.assert_close(sc[ok], want[ok].float(), rtol=2e-5, atol=6e-6)
 
 
 # ---- 7
