@@ -49,8 +49,8 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
 /* Launch profiler: between _begin and _end every kernel launch of the entry points below is bracketed by a
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
- * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw; kind: the net kind
- * for 0/1, to_dense for 6;
+ * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
+ * 8 occupancy_build; kind: the net kind for 0/1, to_dense for 6, dilate for 8;
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
  * tag: the layer a stnerf_render_rays launch belongs to (-1 otherwise); bytes_per_ray: algorithmic HBM bytes
  * per ray for the HBM-bound kernels (2..4), 0 for the networks. */
@@ -655,6 +655,51 @@ int stnerf_render_rays_opacity(const float* rays, int64_t n, const float* boxes,
                                float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
                                float* scene_out, const float* layer_alpha_host, stnerf_stream_t stream);
+
+/* ---- occupancy grids (csrc/occupancy.hip) ---------------------------------------------------------------
+ * One bit per cell of a performer's box, and a cull that drops a (ray, performer) pair when none of its coarse sample points
+ * lies in an occupied cell.  Not in the reference beyond utils/vis_density.py (a density grid of a box).
+ *   Grid.  res = (Rx, Ry, Rz) cells, 1..256 per axis, spanning the axis-aligned bounds lo, hi (fp32) of the 8 corners of the
+ *   layer's UNEDITED box at the layer's frame id.  Cell (x, y, z) is bit c & 31 of word c >> 5, c = (z Ry + y) Rx + x; the table
+ *   has ceil(Rx Ry Rz / 32) uint32 words, the unused high bits of the last word 0.
+ *   Point to cell, per axis a:  c_a = min(max((int)floorf((p_a - lo_a) * inv_a), 0), R_a - 1),  inv_a = (float)R_a / (hi_a - lo_a)
+ *   computed once on the host in fp32; the subtraction and the product are separate fp32 operations (no fused multiply-add).
+ *   A point with a NaN coordinate counts as occupied.
+ *   Build.  sigma_c / sigma_f: fp32 [Rz+1][Ry+1][Rx+1] (either may be NULL), the densities of the layer's coarse / fine SpaceNet at
+ *   the grid's vertices (vertex j of axis a at lo_a + j ((hi_a - lo_a) / R_a) in fp32, vertex R_a at hi_a itself).  A vertex is
+ *   dense when !(sigma <= threshold) in either array (a NaN is dense), a cell occupied when one of its 8 corners is dense; the
+ *   grid is the occupied set grown by `dilate` cells in Chebyshev distance, 0 <= dilate <= 4.
+ *   Cull.  For every layer with a grid (bits != NULL) and every ray whose mask[ray][layer] has bit 0 set: if none of the n1 points
+ *   xyz[ray][layer][k] -- the points the networks would be given: after the ray's rotation and the scale / shift un-edit, before
+ *   the MotionNet -- lies in an occupied cell, bit 0 is cleared.  Nothing else is written: bit 1, the layers without a grid, the
+ *   depths and the points stay as they are.  The pair is then in the state of a ray that grazes the box (bit 0 clear, bit 1 clear,
+ *   depths real): no network runs on it, its depths still take part in the merge and the resampling.
+ *   Layer 0 cannot carry a grid (STNERF_EINVAL): the background runs on every ray whatever its mask.
+ * Host struct; a table has l entries; bits == NULL: the layer is not culled.  Checked on the host before any launch: res in
+ * range, inv_cell finite and positive, bits 4-byte aligned, no grid on layer 0. */
+typedef struct stnerf_occupancy {
+    const uint32_t* bits;   /* device */
+    int32_t res[3];         /* Rx, Ry, Rz */
+    float lo[3];
+    float inv_cell[3];
+} stnerf_occupancy;
+int stnerf_occupancy_build(const float* sigma_c, const float* sigma_f, const int32_t res[3], float threshold, int dilate,
+                           uint32_t* bits, stnerf_stream_t stream);
+/* xyz[n][l][n1][3], mask[n][l]; one launch per layer with a grid, one wave per ray.  counts_or_null: device, int32 [l][2] =
+ * (pairs tested, pairs culled) per layer, ACCUMULATED (one 64-bit add per wave: 8-byte aligned; the caller zeroes it). */
+int stnerf_occupancy_cull(const float* xyz, int64_t n, int l, int n1, const stnerf_occupancy* table_host, uint8_t* mask,
+                          int32_t* counts_or_null, stnerf_stream_t stream);
+/* stnerf_render_rays_opacity with an occupancy table (host array of params->l entries, or NULL = none, which is what the entries
+ * above forward and which makes exactly the launches they made, in a workspace of the same size).  The cull runs after the coarse
+ * sampler and before the ray compaction; both passes, the compositor, the resampler, the scene passes and the returned mask
+ * follow from the mask as they always did.  The stage kernels are untouched: a culled frame is the same kernels on fewer rows. */
+int stnerf_render_rays_occupancy(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                 const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                                 const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                 float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                 const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                                 float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                                 int32_t* counts_or_null, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ SOURCES = [
     ("sampler.hip", ["-ffp-contract=off"]),
     ("composite.hip", ["-ffp-contract=off"]),
     ("resample.hip", ["-ffp-contract=off"]),
+    ("occupancy.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

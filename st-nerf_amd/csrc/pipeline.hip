@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -261,6 +261,22 @@ extern "C" int stnerf_render_rays_opacity(const float* rays, int64_t n, const fl
                                           float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                                           const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
                                           const float* layer_alpha, stnerf_stream_t stream) {
+    return stnerf_render_rays_occupancy(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
+                                        mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, nullptr, nullptr,
+                                        stream);
+}
+
+// occ: per-layer occupancy grids (include/stnerf.h: stnerf_occupancy; host array of p->l entries) or null.  The cull runs between the
+// coarse sampler and the ray compaction and writes nothing but bit 0 of the mask: a culled (ray, performer) pair never reaches a
+// network stage, and the compositor and the resampler treat it as they treat a ray that grazes the box.  counts: [l][2] int32 on the
+// device (pairs tested, pairs culled; accumulated) or null.  Without a table the call launches what it always launched.
+extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                            const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                            const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                            float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                            const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                            const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                            stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -295,6 +311,11 @@ extern "C" int stnerf_render_rays_opacity(const float* rays, int64_t n, const fl
                        "render_rays: background cache buffers must be 16-byte aligned");
     }
     const bool cached = cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
+    if (occ) {
+        const int orc = check_occupancy_table(occ, l, "render_rays");
+        if (orc) return orc;
+        STNERF_REQUIRE(((uintptr_t)counts & 7) == 0, "render_rays: occupancy counts must be 8-byte aligned");
+    }
     if (n == 0) return STNERF_OK;
 
     const Plan pl = make_plan(n, l, n1, n2, p->only_coarse);
@@ -321,6 +342,10 @@ extern "C" int stnerf_render_rays_opacity(const float* rays, int64_t n, const fl
                                   p->ray_index_stripe, p->ray_index_period,
                                   p->has_edits ? p->edits_coarse : nullptr, p->pivot, rot, t_c, xyz_c, mask, stream);
     if (rc) return rc;
+    if (occ) {   // (before the compaction: a culled pair is on no list)
+        rc = stnerf_occupancy_cull(xyz_c, n, l, n1, occ, mask, counts, stream);
+        if (rc) return rc;
+    }
     if (hipMemsetAsync(ray_count, 0, sizeof(int32_t) * pl.count, st) != hipSuccess) {
         set_error("render_rays: hipMemsetAsync failed");
         return STNERF_ELAUNCH;

@@ -68,6 +68,11 @@ class BkgdCache(C.Structure):
     _fields_ = [("raw_coarse", C.c_void_p), ("raw_fine", C.c_void_p), ("mode", C.c_int32)]
 
 
+class Occupancy(C.Structure):
+    """stnerf_occupancy (include/stnerf.h): one layer's bit table (device), its cell counts (Rx, Ry, Rz), lo and R / (hi - lo)."""
+    _fields_ = [("bits", C.c_void_p), ("res", C.c_int32 * 3), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
+
+
 BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
 
@@ -174,6 +179,12 @@ _PROTOS = {
     "stnerf_render_rays_opacity": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
                                              C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
                                              C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.c_void_p]),
+    "stnerf_render_rays_occupancy": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                               C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                               C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
+                                               C.c_void_p]),
+    "stnerf_occupancy_build": (C.c_int, [c_f32p, c_f32p, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "stnerf_occupancy_cull": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(Occupancy), C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,

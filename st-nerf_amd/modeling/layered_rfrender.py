@@ -108,6 +108,7 @@ class LayeredRFRender(nn.Module):
                                            # entries that are not gathered come back as None
         self.shard_group = None            # the process group to shard over (None: the default group)
         self._bkgd_cache = None            # stnerf_amd.BackgroundCache or None (set_background_cache)
+        self._occupancy = None             # stnerf_amd.OccupancyGrids or None (set_occupancy)
         self.view_key = None               # (view identity, background frame id) of the rays in flight (stnerf_amd.bkgd_cache.view_key),
                                            # set and restored around a call by whoever generated the rays from a camera
                                            # (stnerf_amd.parallel.render_view / render_view_share); None: rays of unknown origin,
@@ -163,6 +164,16 @@ class LayeredRFRender(nn.Module):
             return self.bboxes
         return torch.cat([self.bboxes, self.bboxes[:, [s - 1 for s in self._instances]]], 1)
 
+    def _box_table_host(self):
+        """``_box_table()`` as fp32 on the host, copied once per state of ``bboxes`` and of the instances: ``layer_box_at`` runs
+        per culled layer and launch piece, and a copy from the device there would make the host wait for the piece before."""
+        bb = self.bboxes
+        key = (bb.data_ptr(), bb._version, bb.device, tuple(bb.shape), tuple(self._instances))
+        held = getattr(self, "_box_host", None)
+        if held is None or held[0] != key:
+            held = self._box_host = (key, self._box_table().detach().to("cpu", torch.float32).clone())
+        return held[1]
+
     def _layer_alpha_table(self):
         """None (``layer_alpha`` unset: ``alpha`` acts, on layer 2) or l floats for stnerf_render_rays_opacity."""
         if self.layer_alpha is None:
@@ -181,6 +192,8 @@ class LayeredRFRender(nn.Module):
             return "layer instances (add_instance)"
         if self.layer_alpha is not None:
             return "layer_alpha"
+        if getattr(self, "_occupancy", None) is not None:
+            return "occupancy grids (set_occupancy)"
         return None
 
     def set_precision(self, precision: str):
@@ -207,6 +220,83 @@ class LayeredRFRender(nn.Module):
         background sample and nothing could be reused.  Detaching restores the per-call advance."""
         self._bkgd_cache = cache
         return self
+
+    # ---- occupancy grids (not in the reference beyond utils/vis_density.py) ---------------------------------
+    def set_occupancy(self, grids):
+        """Attach a ``stnerf_amd.OccupancyGrids`` (None: detach).  While one is attached every launch culls the (ray, performer)
+        pairs none of whose coarse sample points lies in an occupied cell of the performer's grid, before
+        any network runs; the grids are built from the networks' own densities on first use (``density_grid``) or given by the
+        caller (``OccupancyGrids.set_manual``).  A culled layer needs ONE frame id per chunk group.  Inference only; the
+        background cache's key is unchanged, since grids act on performers."""
+        self._occupancy = grids
+        return self
+
+    def layer_box_at(self, layer_id, frame_id, retiming=True):
+        """The UNEDITED box (8,3), fp32 on the host, of layer ``layer_id`` >= 1 at ``frame_id``: the box table's column of the
+        layer (an instance: its source's), lerped for a fractional id exactly as ``_retimed_boxes`` lerps it; ``retiming=False``:
+        the row rays 7 wide select (``int(frame_id) - 1``)."""
+        if not 1 <= layer_id < self.total_layers:
+            raise ValueError(f"layer_box_at: layer {layer_id!r} is not a performer or an instance (1..{self.total_layers - 1})")
+        bb = self._box_table_host()
+        if not retiming:
+            return bb[int(torch.tensor(float(frame_id), dtype=torch.float32).to(torch.int64)) - 1, layer_id - 1].clone()
+        f = torch.tensor(float(frame_id), dtype=torch.float32) - 1
+        return torch.lerp(bb[math.floor(f), layer_id - 1], bb[math.ceil(f), layer_id - 1], f - math.floor(f))
+
+    def density_grid(self, layer_id, frame_id, res=64, fine=True, direction=(0.0, 0.0, 1.0), retiming=True):
+        """-> (sigma (Rz+1, Ry+1, Rx+1) on the device, lo, hi): the density of layer ``layer_id``'s coarse (``fine=False``) or fine
+        SpaceNet at the vertices of a grid of ``res`` cells (a number or (Rx, Ry, Rz)) over the axis-aligned bounds of the layer's
+        unedited box at ``frame_id`` (``layer_box_at``).  Vertex j of axis a lies at lo_a + j ((hi_a - lo_a) / R_a) in fp32, vertex
+        R_a at hi_a.  The points go through the layer's MotionNet at the frame id under USE_DEFORM_TIME and the time goes to the
+        SpaceNet under USE_SPACE_TIME: what a render does to a sample point at that place, through the op-level entries on the
+        "fp32" packs, so the grid does not depend on the render's arithmetic.  One grid row along x is a "ray" of Rx + 1
+        samples; ``direction`` is any unit vector -- the density head does not see it.  The layered, time-aware counterpart of
+        the reference's utils/vis_density.py.  Layer 0 (the background over ``bkgd_bbox``) is for inspection only."""
+        from stnerf_amd import occupancy as occ
+        rx, ry, rz = occ.normalise_res(res)
+        if not 0 <= layer_id < self.total_layers:
+            raise ValueError(f"density_grid: no layer {layer_id!r} (0..{self.total_layers - 1})")
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("density_grid evaluates the networks on the GPU: call .cuda() first (no CPU fallback)")
+        lo, hi = occ.box_bounds(self.bkgd_bbox if layer_id == 0 else self.layer_box_at(layer_id, frame_id, retiming))
+        vx, vy, vz = (torch.from_numpy(v) for v in occ.vertex_coordinates((rx, ry, rz), lo, hi))
+        pts = torch.stack([vx.view(1, 1, -1).expand(rz + 1, ry + 1, rx + 1), vy.view(1, -1, 1).expand(rz + 1, ry + 1, rx + 1),
+                           vz.view(-1, 1, 1).expand(rz + 1, ry + 1, rx + 1)], -1)
+        rows = (rz + 1) * (ry + 1)
+        xyz = pts.reshape(rows, rx + 1, 3).contiguous().to(dev)
+        times = torch.full((rows,), float(frame_id), dtype=torch.float32, device=dev)
+        dirs = torch.tensor([float(x) for x in direction], dtype=torch.float32, device=dev).reshape(1, 3).repeat(rows, 1)
+        raw = torch.empty(rows, rx + 1, 4, dtype=torch.float32, device=dev)
+        bk, nets = self._nets(fine)
+        if layer_id == 0:
+            if self.bkgd_use_deform_time:
+                ops.motionnet_fwd(self.bkgd_time_deform_net._packed("fp32"), xyz, times, add_to_xyz=True, plain_time=True)
+            ops.spacenet_fwd(bk._packed("fp32"), xyz, dirs, times if (self.bkgd_use_space_time and self.use_space_time) else None, raw)
+        else:
+            j = self._module_index(layer_id)
+            if self.use_deform_time:
+                ops.motionnet_fwd(self.time_deform_nets[j]._packed("fp32"), xyz, times, add_to_xyz=True)
+            ops.spacenet_fwd(nets[j]._packed("fp32"), xyz, dirs, times if self.use_space_time else None, raw)
+        return raw[..., 3].reshape(rz + 1, ry + 1, rx + 1).contiguous(), lo, hi
+
+    def _occupancy_frame_ids(self, rays, groups, retiming):
+        """Per chunk group the frame id of every layer (l floats), after checking that each CULLED layer's frame-id column is
+        constant within the group: a min / max on the device and one device-to-host copy.  A grid at row 0's id applied to rays
+        of another id would cull wrongly and silently."""
+        l = self.total_layers
+        culled = self._occupancy.culled_layers(self)
+        cols = (lambda a, b: rays[a:b, 6:6 + l]) if retiming else (lambda a, b: rays[a:b, 6:7].expand(b - a, l))
+        mm = torch.stack([torch.stack([cols(g[0], g[1]).amin(0), cols(g[0], g[1]).amax(0)]) for g in groups]).cpu()
+        out = []
+        for k, g in enumerate(groups):
+            for i in culled:
+                if float(mm[k, 0, i]) != float(mm[k, 1, i]) or mm[k, 0, i] != mm[k, 0, i]:
+                    raise ValueError(f"occupancy: layer {i} has frame ids {float(mm[k, 0, i])} .. {float(mm[k, 1, i])} among rays {g[0]}..{g[1]} of "
+                                     "one chunk group; a culled layer needs one frame id per group (its grid is made at that id) -- "
+                                     "render one frame id per chunk group, or detach the grids (set_occupancy(None))")
+            out.append([float(x) for x in mm[k, 0]])
+        return out
 
     def background_cache_key(self, view_key, piece, window, retiming, only_coarse, pivot=None):
         """(group, piece): the key of a launch piece's background outputs -- host arithmetic only.  The group covers every input
@@ -435,12 +525,13 @@ class LayeredRFRender(nn.Module):
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
-                       scene=False):
+                       scene=False, occupancy_ids=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
         chunk group, passed only when a layer is rotated.  scene: the in-scene layer passes come back as a sixth tensor (passed
-        only by ``render_rays_scene``)."""
+        only by ``render_rays_scene``).  occupancy_ids: the chunk group's frame id per layer, passed only while occupancy grids
+        are attached: one grid per shown performer layer is looked up or built and the table travels with the call."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.total_layers
         p = hip.RenderParams()
@@ -495,10 +586,17 @@ class LayeredRFRender(nn.Module):
                 entry, mode = cache.reserve(key, n, p.n1, p.n2, only_coarse, rays.device), hip.BKGD_CACHE_CAPTURE
             if entry is not None:
                 cache_arg = (entry[0], entry[1], mode)
+        occ_kw = {}
+        if occupancy_ids is not None:
+            grids = self._occupancy
+            occ_table, held = grids.table(self, occupancy_ids, rays.device, retiming)
+            keep.append(held)
+            if any(e is not None for e in occ_table):
+                occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
         try:
             return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
                                    u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
-                                   **(dict(scene=True) if scene else {}),
+                                   **(dict(scene=True) if scene else {}), **occ_kw,
                                    **(dict(layer_alpha=table) if table is not None else {}))
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
@@ -607,6 +705,10 @@ class LayeredRFRender(nn.Module):
                                           "BKGD_USE_SPACE_TIME): a render-time edit, as rotation is -- call model.eval() or wrap the "
                                           "render in torch.no_grad(), and clear_instances() / layer_alpha = None to train")
         self._layer_alpha_table()          # (its ValueErrors before anything is launched)
+        culling = getattr(self, "_occupancy", None) is not None
+        if culling and self.replay is not None and any(k in self.replay for k in ("xyz_c", "xyz_f")):
+            raise ValueError("occupancy grids with replayed deformed points (replay[\"xyz_c\"] / [\"xyz_f\"]): those lists are per hit "
+                             "ray, and the cull changes which rays hit; replay jitter / u only, or detach the grids")
         self._warn_if_eval_with_grad()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None
@@ -626,6 +728,7 @@ class LayeredRFRender(nn.Module):
             bk = self.bkgd_bbox.to(rays.device).float().unsqueeze(0).expand(N, 1, 8, 3)
             boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
             groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))
+        occ_ids = self._occupancy_frame_ids(rays, groups, retiming) if culling and self._occupancy.culled_layers(self) else None
         outs = []
         cap = self.max_rays_per_launch
         first, stripe, period = self.ray_window
@@ -638,7 +741,7 @@ class LayeredRFRender(nn.Module):
         # the background cache serves calls whose view is known on the host (view_key) and whose draws are the device RNG's
         cacheable = (getattr(self, "_bkgd_cache", None) is not None and getattr(self, "view_key", None) is not None
                      and self.replay is None and not train and not per_sample_bkgd_time)
-        for (g0, g1, boxes, pivot, *rot) in groups:
+        for gi, (g0, g1, boxes, pivot, *rot) in enumerate(groups):
             for s in range(g0, g1, cap):
                 e = min(s + cap, g1)
                 bx = boxes if boxes.dim() == 3 else boxes[s:e].contiguous()
@@ -657,7 +760,8 @@ class LayeredRFRender(nn.Module):
                     # (the piece travels only when the cache may serve it: uncached, the call is the nine-argument one it always was)
                     outs.append(self._render_launch(rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
                                                     bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ()),
-                                                    **(dict(rotations=rot[0]) if rot else {}), **(dict(scene=True) if scene else {})))
+                                                    **(dict(rotations=rot[0]) if rot else {}), **(dict(scene=True) if scene else {}),
+                                                    **(dict(occupancy_ids=occ_ids[gi]) if occ_ids is not None else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range(6 if scene else 5))
         self.advance_seed()

@@ -309,7 +309,8 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
     return pack_net(hip.NET_MOTION, ws, bs, device, precision)
 
 
-PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw")
+PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
+                   "occupancy_build")
 
 
 def profile_begin() -> None:
@@ -629,9 +630,68 @@ def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Te
     return dense if to_dense else raw
 
 
+# ---------------------------------------------------------------------------------------- occupancy grids
+def occupancy_words(res) -> int:
+    """uint32 words of a bit table of res = (Rx, Ry, Rz) cells."""
+    return (int(res[0]) * int(res[1]) * int(res[2]) + 31) // 32
+
+
+def occupancy_build(sigma_c: Optional[Tensor], sigma_f: Optional[Tensor], threshold: float, dilate: int) -> Tensor:
+    """Vertex densities (Rz+1, Ry+1, Rx+1) of the coarse and / or the fine SpaceNet -> the bit table of the (Rx, Ry, Rz) grid
+    (stnerf_occupancy_build; include/stnerf.h states the rule): int32 words holding the uint32 bits, cell c = (z Ry + y) Rx + x
+    at bit c & 31 of word c >> 5."""
+    given = [s for s in (sigma_c, sigma_f) if s is not None]
+    if not given:
+        raise ValueError("occupancy_build: one of sigma_c / sigma_f is required")
+    if any(s.dim() != 3 or s.shape != given[0].shape for s in given):
+        raise ValueError(f"occupancy_build: sigma arrays must be (Rz+1, Ry+1, Rx+1) and alike, got {[tuple(s.shape) for s in given]}")
+    res = (given[0].shape[2] - 1, given[0].shape[1] - 1, given[0].shape[0] - 1)
+    if min(res) < 1:
+        raise ValueError(f"occupancy_build: sigma arrays of shape {tuple(given[0].shape)} hold no cell")
+    bits = torch.empty(occupancy_words(res), dtype=torch.int32, device=given[0].device)
+    hip.check(hip.lib().stnerf_occupancy_build(hip.dptr(sigma_c, name="sigma_c"), hip.dptr(sigma_f, name="sigma_f"), (C.c_int32 * 3)(*res),
+                                               float(threshold), int(dilate), hip.dptr(bits, torch.int32), hip.stream_ptr()),
+              "stnerf_occupancy_build")
+    return bits
+
+
+def _occupancy_table(table, l):
+    """-> hip.Occupancy array of l entries | None.  table: per layer None | (bits int32 device tensor, (Rx, Ry, Rz), lo (3 floats),
+    inv_cell (3 floats)) -- the numbers as they are (``stnerf_amd.occupancy`` computes inv_cell in fp32)."""
+    if table is None:
+        return None
+    if len(table) != l:
+        raise ValueError(f"occupancy table must have one entry per layer ({l}), got {len(table)}")
+    arr = (hip.Occupancy * l)()
+    for i, e in enumerate(table):
+        if e is None:
+            continue
+        bits, res, lo, inv = e
+        if min(res) >= 1 and bits.numel() < occupancy_words(res):
+            raise ValueError(f"occupancy grid of layer {i}: {bits.numel()} words for res {tuple(res)}, need {occupancy_words(res)}")
+        arr[i].bits = hip.dptr(bits, torch.int32, "occupancy bits").value
+        for a in range(3):
+            arr[i].res[a], arr[i].lo[a], arr[i].inv_cell[a] = int(res[a]), float(lo[a]), float(inv[a])
+    return arr
+
+
+def occupancy_cull(xyz: Tensor, mask: Tensor, table, counts: Optional[Tensor] = None) -> Tensor:
+    """Clear bit 0 of mask (n,l) uint8, in place, for every (ray, layer) pair of a layer with a grid none of whose points
+    xyz (n,l,n1,3) lies in an occupied cell (stnerf_occupancy_cull).  table: per layer None | (bits, res, lo, inv_cell);
+    counts: int32 (l,2) device tensor that accumulates (pairs tested, pairs culled), or None."""
+    n, l, n1 = xyz.shape[0], xyz.shape[1], xyz.shape[2]
+    if tuple(mask.shape) != (n, l) or xyz.dim() != 4 or xyz.shape[3] != 3:
+        raise ValueError(f"occupancy_cull: xyz must be (n,l,n1,3) and mask (n,l), got {tuple(xyz.shape)} and {tuple(mask.shape)}")
+    if counts is not None and tuple(counts.shape) != (l, 2):
+        raise ValueError(f"occupancy_cull: counts must be ({l},2) int32, got {tuple(counts.shape)}")
+    hip.check(hip.lib().stnerf_occupancy_cull(hip.dptr(xyz, name="xyz"), n, l, n1, _occupancy_table(table, l), hip.dptr(mask, torch.uint8, "mask"),
+                                              hip.dptr(counts, torch.int32, "counts"), hip.stream_ptr()), "stnerf_occupancy_cull")
+    return mask
+
+
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
                 jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
-                layer_alpha: Optional[Sequence[float]] = None):
+                layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -639,7 +699,9 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     ``rotations``: per layer None | (m, centre), the pairs of ``LayeredRFRender.layer_ray_transforms`` (stnerf_render_rays_rot).
     ``scene``: append the in-scene layer passes of the final stage, (n,l,5) (stnerf_render_rays_scene), to the returned tuple.
     ``layer_alpha``: params.l density factors, one per layer, for the fine composite (stnerf_render_rays_opacity; the library
-    refuses an entry that is negative or not finite); params.alpha is ignored then.  None: params.alpha on layer 2, as ever."""
+    refuses an entry that is negative or not finite); params.alpha is ignored then.  None: params.alpha on layer 2, as ever.
+    ``occupancy``: per layer None | (bits, res, lo, inv_cell), the table of ``occupancy_cull`` (stnerf_render_rays_occupancy): performer
+    pairs whose coarse points all lie in empty cells are dropped before the networks; ``occupancy_counts``: int32 (l,2) | None."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -666,9 +728,17 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
             raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
         bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
-    if layer_alpha is not None:
-        if len(layer_alpha) != l:
-            raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
+    if layer_alpha is not None and len(layer_alpha) != l:
+        raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
+    if occupancy is not None:
+        occ = _occupancy_table(occupancy, l)
+        if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):
+            raise ValueError(f"occupancy_counts must be ({l},2) int32, got {tuple(occupancy_counts.shape)}")
+        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
+        hip.check(hip.lib().stnerf_render_rays_occupancy(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table, occ,
+                                                         hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"), hip.stream_ptr()),
+                  "stnerf_render_rays_occupancy")
+    elif layer_alpha is not None:
         table = (C.c_float * l)(*(float(a) for a in layer_alpha))
         hip.check(hip.lib().stnerf_render_rays_opacity(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
                                                        hip.stream_ptr()), "stnerf_render_rays_opacity")

@@ -226,7 +226,9 @@ def layers_fingerprint(model):
     src = [float(x) for x in getattr(model, "instances", ())]
     alpha = getattr(model, "layer_alpha", None)
     al = [] if alpha is None else [1.0 if a is None else float(a) for a in alpha]
-    return [len(src)] + (src + [0.0] * cap)[:cap] + [-1.0 if alpha is None else len(al)] + (al + [-1.0] * cap)[:cap]
+    grids = getattr(model, "_occupancy", None)                 # (occupancy grids: ranks that cull differently render different images)
+    occ = [0.0] * 9 if grids is None else [1.0] + grids.fingerprint()
+    return [len(src)] + (src + [0.0] * cap)[:cap] + [-1.0 if alpha is None else len(al)] + (al + [-1.0] * cap)[:cap] + occ
 
 
 def rays_fingerprint(rays: torch.Tensor):

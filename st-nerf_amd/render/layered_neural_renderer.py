@@ -33,7 +33,7 @@ class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
-                 layer_alpha=None, s_layer_alpha=None):
+                 layer_alpha=None, s_layer_alpha=None, occupancy=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -71,6 +71,7 @@ class LayeredNeuralRenderer:
         self.model.rotation = self.rotation
         self.model.layer_alpha = self.layer_alpha
         self.cache_background = cache_background
+        self.occupancy = occupancy
         # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
         # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
         # hand the frame's dict to on_frame as the keyword `scene`; not in the reference (keyword-only, off by default)
@@ -147,6 +148,25 @@ class LayeredNeuralRenderer:
         if bool(on) != self.cache_background:
             from stnerf_amd.bkgd_cache import BackgroundCache
             self.model.set_background_cache(BackgroundCache() if on else None)
+
+    @property
+    def occupancy(self):
+        """The ``stnerf_amd.OccupancyGrids`` attached to the model, or None: while one is attached the performer rays that cross
+        only empty cells of their performer's grid are culled before the networks run (``LayeredRFRender.set_occupancy``).
+        Setting True attaches fresh grids with the defaults, an ``OccupancyGrids`` attaches that one, False / None detaches;
+        not in the reference (keyword-only, off by default)."""
+        return getattr(self.model, "_occupancy", None)
+
+    @occupancy.setter
+    def occupancy(self, value):
+        from stnerf_amd.occupancy import OccupancyGrids
+        if isinstance(value, OccupancyGrids):
+            self.model.set_occupancy(value)
+        elif value is None or isinstance(value, bool):
+            if bool(value) != (self.occupancy is not None):
+                self.model.set_occupancy(OccupancyGrids() if value else None)
+        else:
+            raise TypeError(f"occupancy is False, True or an OccupancyGrids, got {type(value).__name__}")
 
     # ---- layer display / knobs (:643-686, :740-741) ----------------------------------------------------
     def hide_layer(self, layer_id):

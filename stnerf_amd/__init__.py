@@ -23,4 +23,7 @@ def __getattr__(name):
     if name == "BackgroundCache":
         from stnerf_amd.bkgd_cache import BackgroundCache
         return BackgroundCache
+    if name == "OccupancyGrids":
+        from stnerf_amd.occupancy import OccupancyGrids
+        return OccupancyGrids
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
