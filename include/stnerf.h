@@ -50,7 +50,8 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
  * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
- * 8 occupancy_build; kind: the net kind for 0/1, to_dense for 6, dilate for 8;
+ * 8 occupancy_build, 9 occupancy_rows; kind: the net kind for 0/1, to_dense for 6, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
+ * 4 the row-list flavour (stnerf_mlp_stage_rows with at least one listed layer);
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
  * tag: the layer a stnerf_render_rays launch belongs to (-1 otherwise); bytes_per_ray: algorithmic HBM bytes
  * per ray for the HBM-bound kernels (2..4), 0 for the networks. */
@@ -298,6 +299,22 @@ typedef struct stnerf_stage_layer {
 int stnerf_mlp_stage(const stnerf_stage_layer* layers_host, int n_layers, int64_t n_rays, int ns, const float* dirs,
                      int64_t dirs_ray_stride, int64_t times_ray_stride, int64_t xyz_ray_stride,
                      int64_t raw_ray_stride, int flags, uint32_t* queue, float* ray_bias, stnerf_stream_t stream);
+/* The same stage with a ROW LIST on some of its layers (the sample cull, below: stnerf_occupancy_rows writes the lists).
+ * rows_host: n_layers entries beside layers_host, or NULL.  Entry i with row_list != NULL: queue slot i has *row_count rows (never
+ * more than n_rays x ns are walked), and row r of it is sample k = v & 255 of ray v >> 8, v = row_list[r] -- instead of
+ * (ray_list[r / ns], r % ns).  Points, outputs, frame ids and the ray-bias row are addressed by (ray, k) as ever, so a listed row
+ * gets the 16 bytes the unlisted launch writes for that sample, and nothing is written for a sample that is on no list.  The
+ * layer's ray_list / ray_count still name the rays its ray-bias rows are made for: every ray of the row list must be on it.
+ * Listed and unlisted layers share one launch.  A list needs ns <= 256 and n_rays <= 2^23 (STNERF_EINVAL).  NULL, or no entry with
+ * a list, is stnerf_mlp_stage: the same kernels.  With a list the row-list flavours run (csrc/mlp_wave_rows.hip,
+ * csrc/mlp_bf16x3_rows.hip: the same kernel text under another name, with this locate step). */
+typedef struct stnerf_stage_rows {
+    const int32_t* row_list;   /* device; NULL: the layer's rows are ray_count x ns */
+    const int32_t* row_count;  /* device */
+} stnerf_stage_rows;
+int stnerf_mlp_stage_rows(const stnerf_stage_layer* layers_host, const stnerf_stage_rows* rows_host, int n_layers, int64_t n_rays, int ns,
+                          const float* dirs, int64_t dirs_ray_stride, int64_t times_ray_stride, int64_t xyz_ray_stride,
+                          int64_t raw_ray_stride, int flags, uint32_t* queue, float* ray_bias, stnerf_stream_t stream);
 
 /* a7 standalone: NeRF positional encoding [x, sin(2^0 x), cos(2^0 x), ..., sin(2^(L-1) x), cos(2^(L-1) x)],
  * each block `dim` wide.  utils/dimension_kernel.py:3-73 (Trigonometric_kernel.__call__).  In the render
@@ -689,6 +706,26 @@ int stnerf_occupancy_build(const float* sigma_c, const float* sigma_f, const int
  * (pairs tested, pairs culled) per layer, ACCUMULATED (one 64-bit add per wave: 8-byte aligned; the caller zeroes it). */
 int stnerf_occupancy_cull(const float* xyz, int64_t n, int l, int n1, const stnerf_occupancy* table_host, uint8_t* mask,
                           int32_t* counts_or_null, stnerf_stream_t stream);
+/*   Sample cull.  For a layer i >= 1 with a grid, a network stage of ns samples (the coarse stage: n1, the fine stage: n1 + n2) and
+ *   every ray on the layer's compacted list (the whole-ray cull above has run): sample k is LISTED when the point xyz[ray][i][k] --
+ *   the point the networks would be given: after rotation and un-edit, before the MotionNet -- lies in an occupied cell or has a
+ *   NaN coordinate, by the point-to-cell rule above, unchanged.  A listed sample is evaluated exactly as without the cull.  A sample
+ *   that is not listed gets raw[ray][i][k] = {0, 0, 0, 0}, four exact zero words, and no network runs on it.  Nothing else changes:
+ *   depths, points, masks, the resampler, the compositor and the scene passes see a `raw` buffer and behave as they always did
+ *   (sigma = 0 gives alpha = 0: a skipped sample weighs nothing, its depth still takes part in the merge).
+ * stnerf_occupancy_rows makes one layer's row list.  ray_list / ray_count: the layer's work list (ray_list NULL: rays 0 .. n-1);
+ * xyz / raw: the LAYER's slices (as in stnerf_stage_layer), with their ray strides in floats; grid_host: the layer's entry.  Writes
+ *   row_list[capacity] int32: one word (ray << 8) | k per listed sample, the rows of one ray contiguous and ascending in k, the
+ *     order of the rays free (it changes from run to run);
+ *   row_count int32 (zeroed by the call itself, on the stream);
+ *   the zero float4 of every not-listed sample of every tested ray into raw -- and nothing else of raw;
+ *   counts_or_null: device, int64 [..][2], row `layer` = (samples tested, samples skipped), ACCUMULATED (the caller zeroes it).
+ * STNERF_EINVAL: ns > 256, n > 2^23, capacity < n * ns, layer 0 (the background is never listed), a bad grid.  One launch: a
+ * persistent grid of at most 2048 workgroups; a wave takes runs of 16 list slots, keeps their ballots in scalar registers and
+ * reserves its range of the list with one atomic add per run. */
+int stnerf_occupancy_rows(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz, int64_t xyz_ray_stride,
+                          int ns, const stnerf_occupancy* grid_host, float* raw, int64_t raw_ray_stride, int32_t* row_list,
+                          int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream);
 /* stnerf_render_rays_opacity with an occupancy table (host array of params->l entries, or NULL = none, which is what the entries
  * above forward and which makes exactly the launches they made, in a workspace of the same size).  The cull runs after the coarse
  * sampler and before the ray compaction; both passes, the compositor, the resampler, the scene passes and the returned mask
@@ -700,6 +737,24 @@ int stnerf_render_rays_occupancy(const float* rays, int64_t n, const float* boxe
                                  const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
                                  float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
                                  int32_t* counts_or_null, stnerf_stream_t stream);
+/* stnerf_render_rays_occupancy with the sample cull.  samples_host: params->l flags (host) or NULL = none, which is what
+ * stnerf_render_rays_occupancy forwards and which makes exactly the launches it made, in a workspace of
+ * stnerf_render_workspace_bytes.  samples_host[i] != 0 needs a grid on layer i (STNERF_EINVAL otherwise) and sample-culls it in both
+ * stages: stnerf_occupancy_rows on the coarse points after the ray cull and the compaction, and on the fine points after the
+ * resampler, each right before its stage, which then walks the row list (stnerf_mlp_stage_rows).  A sample-culled layer's MotionNet
+ * runs fused, inside the stage kernel and on listed rows only (it takes no part in the MotionNet reuse of the split-bf16 stages).
+ * The workspace grows by one row list per sample-culled layer: stnerf_render_workspace_bytes_samples.  params->precision == 2 (one
+ * launch per network) with a sample-culled layer: STNERF_EINVAL.  sample_counts_or_null: device, int64 [l][2] = (samples tested,
+ * samples skipped) per layer over both stages, accumulated. */
+int64_t stnerf_render_workspace_bytes_samples(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples_host);
+int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                               const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                               const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                               float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                               const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                               float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                               int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
+                               stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

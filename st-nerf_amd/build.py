@@ -30,6 +30,9 @@ SOURCES = [
     # three instrumented variants of this file computed wrong, run-to-run varying results on the MI355X -- hipcc 7.2)
     ("mlp_wave.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] if os.environ.get("STNERF_WAVE_VGPR_FORM") else []),
     ("mlp_bf16x3.hip", []),
+    # (the row-list flavours of the two stage kernels: files of their own, so that the two above hold the kernels they always held)
+    ("mlp_wave_rows.hip", []),
+    ("mlp_bf16x3_rows.hip", []),
     ("stage_entry.hip", []),
     ("pipeline.hip", []),
     ("train.hip", []),

@@ -3,6 +3,8 @@
 // their common prologue / epilogue code is mlp_wave_common.h.  (The round-2 organisation with feature-split waves and
 // activations in LDS, mlp_stage.hip, was removed in round 3.)
 #pragma once
+#include <type_traits>
+
 #include "mlp_common.h"
 
 namespace stnerf {
@@ -79,7 +81,27 @@ struct StoreTapArgs {
     int64_t bits_stride;   // uint32 words between two stages' planes
 };
 
-// mlp_wave.hip
+// Row lists (include/stnerf.h: stnerf_stage_rows): the second argument of the row-list flavours of the stage
+// kernels (mlp_wave_rows.hip, mlp_bf16x3_rows.hip).  Queue slot j with row_list[j] != nullptr has *row_count[j] rows, and row r
+// of it is sample k = v & 255 of ray v >> 8, v = row_list[j][r]; a slot without a list has hit rays x ns rows as ever.
+struct StageRowsArgs {
+    const int32_t* row_list[STNERF_MAX_LAYERS];
+    const int32_t* row_count[STNERF_MAX_LAYERS];
+};
+// rows of queue slot j: of its row list (never more than a full layer's n_rays x ns) or of its work list
+template <class TapArgs>
+__device__ __forceinline__ int64_t slot_rows(const StageLayer& ly, const TapArgs& targs, int j, int64_t n_rays, int ns) {
+    if constexpr (std::is_same<TapArgs, StageRowsArgs>::value) {
+        if (targs.row_list[j]) {
+            const int64_t c = *targs.row_count[j], cap = n_rays * ns;
+            return c < 0 ? 0 : (c < cap ? c : cap);
+        }
+    }
+    return layer_rows(ly, n_rays, ns);
+}
+
+// mlp_wave.hip, mlp_wave_rows.hip
+int launch_wave_stage_rows(const StageArgs& a, const StageRowsArgs& r, bool deep_rgb, int cus, hipStream_t stream);
 int launch_wave_stage(const StageArgs& a, bool deep_rgb, int cus, hipStream_t stream);
 int launch_wave_stage_store(const StageArgs& a, float* const (&buf)[8], const int32_t (&ld)[8], float* pe, int32_t ld_pe, uint32_t* bits,
                             int64_t bits_stride, int cus, hipStream_t stream);

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -68,6 +68,23 @@ extern "C" int64_t stnerf_render_workspace_bytes(int64_t n, int l, int n1, int n
     const Plan p = make_plan(n, l, n1, n2, only_coarse);
     const int64_t floats = p.shared() + p.t_f + p.xyz_f + p.raybias;
     return floats * 4 + (p.list + p.count) * 4 + p.flags + 16 * 256;
+}
+
+// The sample cull's share of the workspace: one row list of n x (samples of the larger stage) words per
+// sample-culled layer and the lists' counts.  Nothing without such a layer.
+static int sampled_layers(int l, const int32_t* samples) {
+    int c = 0;
+    for (int i = 0; samples && i < l; ++i) c += samples[i] ? 1 : 0;
+    return c;
+}
+static int64_t row_capacity(int64_t n, int n1, int n2, int only_coarse) { return n * (only_coarse ? n1 : n1 + n2); }
+
+extern "C" int64_t stnerf_render_workspace_bytes_samples(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples) {
+    const int64_t base = stnerf_render_workspace_bytes(n, l, n1, n2, only_coarse);
+    if (base < 0) return base;
+    const int c = sampled_layers(l, samples);
+    if (c == 0) return base;
+    return base + c * ((row_capacity(n, n1, n2, only_coarse) * 4 + 255) & ~int64_t(255)) + STNERF_MAX_LAYERS * 4 + 2 * 256;
 }
 
 // The mask the caller gets back is the reference's ray_mask (0 / 1): the sampler's "missed" hint (bit 1) served the compositor and
@@ -277,6 +294,22 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
                                             const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
                                             const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
                                             stnerf_stream_t stream) {
+    return stnerf_render_rays_samples(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
+                                      layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, nullptr, nullptr, stream);
+}
+
+// samples: per-layer flags (host array of p->l entries) or null.  A flagged layer's stages walk a row list (stnerf_occupancy_rows ->
+// stnerf_mlp_stage_rows): the rows kernel runs right before each stage, on the points that stage is given, and stores the zeros of
+// the samples it does not list.  In the fine pass that is after the resampler and after every MotionNet-reuse launch of the other
+// layers: the zeros go into raw_f, which lies over t_c / xyz_c, and those launches read them.  A flagged layer is never in `reuse`:
+// its MotionNet runs fused, on listed rows only.  Without a flag the call launches what stnerf_render_rays_occupancy always launched.
+extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                          const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                          const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                          float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                          const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                          const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                          const int32_t* samples, int64_t* sample_counts, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -298,7 +331,16 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
         for (int i = 0; i < l; ++i)
             STNERF_REQUIRE(isfinite(layer_alpha[i]) && layer_alpha[i] >= 0.f,
                            "render_rays: layer_alpha[%d] = %g is not a finite, non-negative factor", i, (double)layer_alpha[i]);
-    const int64_t need = stnerf_render_workspace_bytes(n, l, n1, n2, p->only_coarse);
+    const int n_sampled = sampled_layers(l, samples);
+    if (n_sampled) {
+        STNERF_REQUIRE(p->precision != 2, "render_rays: the sample cull is not built for precision 2 (one launch per network)");
+        STNERF_REQUIRE(!samples[0], "render_rays: layer 0 cannot be sample-culled (the background is never listed)");
+        for (int i = 1; i < l; ++i)
+            STNERF_REQUIRE(!samples[i] || (occ && occ[i].bits), "render_rays: layer %d is to be sample-culled but has no occupancy grid", i);
+        STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the sample cull packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
+        STNERF_REQUIRE(((uintptr_t)sample_counts & 7) == 0, "render_rays: sample counts must be 8-byte aligned");
+    }
+    const int64_t need = stnerf_render_workspace_bytes_samples(n, l, n1, n2, p->only_coarse, samples);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
     const int cache_mode = cache ? cache->mode : STNERF_BKGD_CACHE_OFF;
@@ -334,6 +376,14 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
     int32_t* ray_count = ws.take<int32_t>(pl.count);
     uint8_t* ray_flags = ws.take<uint8_t>(pl.flags);
     float* ray_bias = ws.take<float>(pl.raybias);
+    const int64_t row_cap = row_capacity(n, n1, n2, p->only_coarse);
+    int32_t* row_list[STNERF_MAX_LAYERS] = {nullptr};
+    int32_t* row_count = nullptr;
+    if (n_sampled) {
+        for (int i = 1; i < l; ++i)
+            if (samples[i]) row_list[i] = ws.take<int32_t>(row_cap);
+        row_count = ws.take<int32_t>(STNERF_MAX_LAYERS);
+    }
     hipStream_t st = as_stream(stream);
     int rc;
 
@@ -360,7 +410,7 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
         const char* sw = getenv("STNERF_MOTION_REUSE");
         if (!(sw && sw[0] == '0'))
             for (int i = 1; i < l; ++i)
-                if (p->shown[i] && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
+                if (p->shown[i] && !row_list[i] && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
                     reuse |= 1u << i;
     }
     uint32_t* motion_queue = reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
@@ -372,6 +422,8 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
             // exact f32 / bf16x3: ONE persistent launch over every shown layer (csrc/stage_entry.hip); deformed performers
             // first, the background last
             stnerf_stage_layer sl[STNERF_MAX_LAYERS];
+            stnerf_stage_rows sr[STNERF_MAX_LAYERS];
+            memset(sr, 0, sizeof(sr));
             int ns_l = 0;
             for (int pass = 0; pass < 2; ++pass) {
                 for (int i = cached ? 1 : 0; i < l; ++i) {
@@ -390,13 +442,20 @@ extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const 
                     e.use_time = timed ? 1 : 0;
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
                     e.rotation = rot ? rot + i : nullptr;
+                    if (row_list[i]) {   // the sample cull: this layer's rows of this stage, and the zeros of the others
+                        const int r1 = stnerf_occupancy_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, ns, occ + i, e.raw, ws_, row_list[i], row_cap,
+                                                             row_count + i, sample_counts, stream);
+                        if (r1) return r1;
+                        sr[ns_l - 1].row_list = row_list[i];
+                        sr[ns_l - 1].row_count = row_count + i;
+                    }
                 }
             }
             if (ns_l == 0) return STNERF_OK;   // (background from the cache, no performer shown: nothing to evaluate)
             set_launch_tag(fine ? 1 : 0);
-            const int r2 = stnerf_mlp_stage(sl, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
-                                            (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
-                                            reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + (fine ? 1 : 0)), ray_bias, stream);
+            const int r2 = stnerf_mlp_stage_rows(sl, n_sampled ? sr : nullptr, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
+                                                 (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
+                                                 reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + (fine ? 1 : 0)), ray_bias, stream);
             set_launch_tag(-1);
             return r2;
         }

@@ -71,11 +71,33 @@ struct MotionOpArgs {
 extern "C" int stnerf_mlp_stage(const stnerf_stage_layer* layers, int n_layers, int64_t n_rays, int ns, const float* dirs,
                                 int64_t dirs_ray_stride, int64_t times_ray_stride, int64_t xyz_ray_stride,
                                 int64_t raw_ray_stride, int flags, uint32_t* queue, float* ray_bias, stnerf_stream_t stream) {
+    return stnerf_mlp_stage_rows(layers, nullptr, n_layers, n_rays, ns, dirs, dirs_ray_stride, times_ray_stride, xyz_ray_stride, raw_ray_stride,
+                                 flags, queue, ray_bias, stream);
+}
+
+// rows[i]: the row list of queue slot i (include/stnerf.h: stnerf_stage_rows) or a null entry; rows == nullptr, or no entry with
+// a list: the launch stnerf_mlp_stage always made.  Otherwise the row-list flavour of the same kernel (mlp_wave_rows.hip,
+// mlp_bf16x3_rows.hip), listed and unlisted slots side by side in one queue.
+extern "C" int stnerf_mlp_stage_rows(const stnerf_stage_layer* layers, const stnerf_stage_rows* rows, int n_layers, int64_t n_rays, int ns,
+                                     const float* dirs, int64_t dirs_ray_stride, int64_t times_ray_stride, int64_t xyz_ray_stride,
+                                     int64_t raw_ray_stride, int flags, uint32_t* queue, float* ray_bias, stnerf_stream_t stream) {
     STNERF_REQUIRE(layers && dirs && queue && ray_bias, "mlp_stage: null pointer");
     STNERF_REQUIRE(((uintptr_t)ray_bias & 15) == 0, "mlp_stage: ray_bias must be 16-byte aligned");
     STNERF_REQUIRE(n_layers >= 1 && n_layers <= STNERF_MAX_LAYERS && n_rays >= 0 && ns >= 1, "mlp_stage: bad shape");
     STNERF_REQUIRE((raw_ray_stride & 3) == 0, "mlp_stage: raw ray stride must be a multiple of 4 floats");
     STNERF_REQUIRE((flags & ~(STNERF_STAGE_DEEP_RGB | STNERF_STAGE_SIGMOID_RGB | STNERF_STAGE_BF16X3)) == 0, "mlp_stage: unknown flags %d", flags);
+    StageRowsArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    bool listed = false;
+    for (int i = 0; rows && i < n_layers; ++i) {
+        if (!rows[i].row_list) continue;
+        STNERF_REQUIRE(rows[i].row_count, "mlp_stage: layer %d: a row list without its row count", i);
+        STNERF_REQUIRE(ns <= 256 && n_rays <= ((int64_t)1 << 23), "mlp_stage: a row list packs (ray << 8 | k): ns <= 256 and n_rays <= 2^23 (got %d, %lld)",
+                       ns, (long long)n_rays);
+        ra.row_list[i] = rows[i].row_list;
+        ra.row_count[i] = rows[i].row_count;
+        listed = true;
+    }
     if (n_rays == 0) return STNERF_OK;
     const int deep_rgb = (flags & STNERF_STAGE_DEEP_RGB) != 0;
     const bool bf16x3 = (flags & STNERF_STAGE_BF16X3) != 0;
@@ -83,7 +105,7 @@ extern "C" int stnerf_mlp_stage(const stnerf_stage_layer* layers, int n_layers, 
     memset(&a, 0, sizeof(a));
     a.sigmoid_rgb = (flags & STNERF_STAGE_SIGMOID_RGB) != 0;
     // (the profiler's record of the stage covers the per-ray prologues too: their work is part of the networks' FLOPs)
-    LaunchTimer timer(PROF_MLP_STAGE, deep_rgb | (bf16x3 ? 2 : 0), n_rays, ns, 0, as_stream(stream));
+    LaunchTimer timer(PROF_MLP_STAGE, deep_rgb | (bf16x3 ? 2 : 0) | (listed ? 4 : 0), n_rays, ns, 0, as_stream(stream));
     for (int i = 0; i < n_layers; ++i) {
         const stnerf_stage_layer& s = layers[i];
         STNERF_REQUIRE(s.space && s.xyz && s.raw, "mlp_stage: layer %d: null pointer", i);
@@ -115,6 +137,9 @@ extern "C" int stnerf_mlp_stage(const stnerf_stage_layer* layers, int n_layers, 
     a.queue = queue;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (listed)
+        return bf16x3 ? launch_bf16x3_stage_rows(a, ra, deep_rgb != 0, cus, as_stream(stream))
+                      : launch_wave_stage_rows(a, ra, deep_rgb != 0, cus, as_stream(stream));
     return bf16x3 ? launch_bf16x3_stage(a, deep_rgb != 0, cus, as_stream(stream)) : launch_wave_stage(a, deep_rgb != 0, cus, as_stream(stream));
 }
 

@@ -51,6 +51,11 @@ class StageLayer(C.Structure):
                 ("motion_flags", C.c_int32), ("rotation", C.POINTER(LayerRotation))]
 
 
+class StageRows(C.Structure):
+    """stnerf_stage_rows (include/stnerf.h): one stage layer's row list (device int32 words ray << 8 | k) and its count, or NULLs."""
+    _fields_ = [("row_list", C.c_void_p), ("row_count", C.c_void_p)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("l", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("ray_stride", C.c_int32),
                 ("retiming", C.c_int32), ("only_coarse", C.c_int32), ("use_deform_time", C.c_int32),
@@ -128,6 +133,8 @@ _PROTOS = {
                                        c_i64, c_f32p, c_i64, C.c_int, C.c_void_p]),
     "stnerf_mlp_stage": (C.c_int, [C.POINTER(StageLayer), C.c_int, c_i64, C.c_int, c_f32p, c_i64, c_i64, c_i64, c_i64, C.c_int,
                                    C.c_void_p, c_f32p, C.c_void_p]),
+    "stnerf_mlp_stage_rows": (C.c_int, [C.POINTER(StageLayer), C.POINTER(StageRows), C.c_int, c_i64, C.c_int, c_f32p, c_i64, c_i64, c_i64, c_i64,
+                                        C.c_int, C.c_void_p, c_f32p, C.c_void_p]),
     "stnerf_train_linear_fwd": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, C.c_void_p]),
     "stnerf_train_linear_dx": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_i64, C.c_int, C.c_int, c_f32p, c_i64, C.c_int, c_f32p, c_i64,
                                          C.c_void_p]),
@@ -185,6 +192,13 @@ _PROTOS = {
                                                C.c_void_p]),
     "stnerf_occupancy_build": (C.c_int, [c_f32p, c_f32p, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_occupancy_cull": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(Occupancy), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stnerf_occupancy_rows": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64,
+                                        C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stnerf_render_workspace_bytes_samples": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "stnerf_render_rays_samples": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                             C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                             C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
+                                             C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,

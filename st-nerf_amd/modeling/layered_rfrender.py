@@ -227,7 +227,8 @@ class LayeredRFRender(nn.Module):
         pairs none of whose coarse sample points lies in an occupied cell of the performer's grid, before
         any network runs; the grids are built from the networks' own densities on first use (``density_grid``) or given by the
         caller (``OccupancyGrids.set_manual``).  A culled layer needs ONE frame id per chunk group.  Inference only; the
-        background cache's key is unchanged, since grids act on performers."""
+        background cache's key is unchanged, since grids act on performers.  ``OccupancyGrids(samples=True)`` also skips the
+        samples of a kept ray whose point lies in an empty cell, in both network stages (their outputs are exact zeros)."""
         self._occupancy = grids
         return self
 
@@ -572,7 +573,18 @@ class LayeredRFRender(nn.Module):
             if self.use_deform_time:
                 nets.motion[i] = ptr(self.time_deform_nets[j])
         table = self._layer_alpha_table()
-        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse)
+        # the occupancy table comes before the workspace: with the sample cull the workspace grows by the row lists of the gridded
+        # layers, so `need` below depends on it.  (Without grids nothing here runs; the ray cull alone sizes the workspace as ever.)
+        occ_kw = {}
+        if occupancy_ids is not None:
+            grids = self._occupancy
+            occ_table, held = grids.table(self, occupancy_ids, rays.device, retiming)
+            keep.append(held)
+            if any(e is not None for e in occ_table):
+                occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
+                if grids.samples:      # every ray-culled layer is sample-culled too
+                    occ_kw.update(occupancy_samples=[e is not None for e in occ_table], sample_counts=grids.sample_counts(rays.device)[:l])
+        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"))
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != rays.device:
             self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=rays.device)
@@ -586,13 +598,6 @@ class LayeredRFRender(nn.Module):
                 entry, mode = cache.reserve(key, n, p.n1, p.n2, only_coarse, rays.device), hip.BKGD_CACHE_CAPTURE
             if entry is not None:
                 cache_arg = (entry[0], entry[1], mode)
-        occ_kw = {}
-        if occupancy_ids is not None:
-            grids = self._occupancy
-            occ_table, held = grids.table(self, occupancy_ids, rays.device, retiming)
-            keep.append(held)
-            if any(e is not None for e in occ_table):
-                occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
         try:
             return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
                                    u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
@@ -709,6 +714,9 @@ class LayeredRFRender(nn.Module):
         if culling and self.replay is not None and any(k in self.replay for k in ("xyz_c", "xyz_f")):
             raise ValueError("occupancy grids with replayed deformed points (replay[\"xyz_c\"] / [\"xyz_f\"]): those lists are per hit "
                              "ray, and the cull changes which rays hit; replay jitter / u only, or detach the grids")
+        if culling and self._occupancy.samples and self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
+            raise ValueError("occupancy grids with samples=True and mlp_schedule = 'per_net' (one launch per network): the sample cull "
+                             "walks row lists in the persistent stage kernels; use mlp_schedule = 'stage' or OccupancyGrids(samples=False)")
         self._warn_if_eval_with_grad()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None

@@ -85,9 +85,13 @@ class OccupancyGrids:
     zeroes such densities anyway.  profiles/occupancy_ab.md has the sweep behind ``res`` and ``dilate``.
     Built grids are keyed by the module index, the frame id, the bytes of lo / hi, res, threshold, dilate, the parameter versions
     of the layer's three networks and the model flags; at most ``max_grids`` are kept, least recently used first out.
-    ``auto=False``: only layers given a manual grid (``set_manual``) are culled."""
+    ``auto=False``: only layers given a manual grid (``set_manual``) are culled.
+    ``samples=True``: every layer that is ray-culled is sample-culled too -- on a kept ray only the samples whose point lies in
+    an occupied cell reach the networks, in both stages; the others get exact zero outputs (the sample
+    cull).  Off by default: a grid that is right for whole rays (one occupied sample keeps the ray) can still be too tight for
+    single samples, see profiles/sample_cull_ab.md."""
 
-    def __init__(self, res=64, threshold: float = 1e-4, dilate: int = 0, max_grids: int = 64, auto: bool = True):
+    def __init__(self, res=64, threshold: float = 1e-4, dilate: int = 0, max_grids: int = 64, auto: bool = True, samples: bool = False):
         self.res = normalise_res(res)
         self.threshold = float(threshold)
         if self.threshold != self.threshold:
@@ -99,6 +103,11 @@ class OccupancyGrids:
             raise ValueError(f"max_grids must be at least 1, got {max_grids!r}")
         self.max_grids = int(max_grids)
         self.auto = bool(auto)
+        if not isinstance(samples, bool):
+            raise TypeError(f"samples is False or True, got {samples!r}")
+        self.samples = samples
+        self._sample_counts = None   # int64 (MAX_LAYERS, 2) on the device: (samples tested, samples skipped), by the rows kernel
+        self._samples = {}           # layer id -> [tested, skipped]: what stats() has taken off them so far
         self._built: "OrderedDict[tuple, Grid]" = OrderedDict()
         self._manual = {}            # layer id -> (uint32 words (host), res, lo, hi, inv_cell, {device: Grid})
         self._counts = None          # int32 (MAX_LAYERS, 2) on the device: (pairs tested, pairs culled), accumulated by the cull
@@ -188,6 +197,13 @@ class OccupancyGrids:
             self._counts = torch.zeros(hip.MAX_LAYERS, 2, dtype=torch.int32, device=device)
         return self._counts
 
+    def sample_counts(self, device) -> torch.Tensor:
+        """The device counters the sample cull accumulates into: int64 (MAX_LAYERS, 2)."""
+        from stnerf_amd import hip
+        if self._sample_counts is None or self._sample_counts.device != torch.device(device):
+            self._sample_counts = torch.zeros(hip.MAX_LAYERS, 2, dtype=torch.int64, device=device)
+        return self._sample_counts
+
     # ---- bookkeeping ----------------------------------------------------------------------------------
     def __len__(self):
         return len(self._built)
@@ -199,14 +215,18 @@ class OccupancyGrids:
     def reset_stats(self) -> None:
         self.built = self.reused = 0
         self._pairs = {}
+        self._samples = {}
         if self._counts is not None:
             self._counts.zero_()
+        if self._sample_counts is not None:
+            self._sample_counts.zero_()
 
     def stats(self) -> dict:
         """built / reused grid counts and, per layer that was tested, (pairs tested, pairs culled) since the last
         ``reset_stats()``: one device-to-host copy, made only here.  The device counters are 32 bits wide and only the
         statistics depend on them: ``stats()`` moves them into Python integers and zeroes them, so ask (or ``reset_stats()``)
-        before a layer has been tested 2^31 times -- about a thousand 1080p frames of a performer that fills the picture."""
+        before a layer has been tested 2^31 times -- about a thousand 1080p frames of a performer that fills the picture.
+        ``samples``: per layer that was sample-culled, (samples tested, samples skipped) over both stages (64-bit counters)."""
         if self._counts is not None:
             for i, (t, c) in enumerate(self._counts.cpu().tolist()):
                 if t:
@@ -214,14 +234,22 @@ class OccupancyGrids:
                     held[0] += int(t)
                     held[1] += int(c)
             self._counts.zero_()
-        return dict(built=self.built, reused=self.reused, pairs={i: tuple(v) for i, v in sorted(self._pairs.items())})
+        if self._sample_counts is not None:
+            for i, (t, c) in enumerate(self._sample_counts.cpu().tolist()):
+                if t:
+                    held = self._samples.setdefault(i, [0, 0])
+                    held[0] += int(t)
+                    held[1] += int(c)
+            self._sample_counts.zero_()
+        return dict(built=self.built, reused=self.reused, pairs={i: tuple(v) for i, v in sorted(self._pairs.items())},
+                    samples={i: tuple(v) for i, v in sorted(self._samples.items())})
 
     def fingerprint(self):
         """A fixed number of floats for the cross-rank check of a sharded render (``stnerf_amd.parallel``): res, threshold,
-        dilate, auto, and a digest of the manual grids."""
+        dilate, auto | samples << 1, and a digest of the manual grids."""
         h = hashlib.sha256()
         for i in sorted(self._manual):
             words, res, lo, hi, _, _ = self._manual[i]
             h.update(repr((i, res)).encode() + lo.tobytes() + hi.tobytes() + words.tobytes())
         digest = int.from_bytes(h.digest()[:6], "little") if self._manual else 0      # (48 bits: exact in fp64)
-        return [float(x) for x in self.res] + [self.threshold, float(self.dilate), float(self.auto), float(len(self._manual)), float(digest)]
+        return [float(x) for x in self.res] + [self.threshold, float(self.dilate), float(int(self.auto) | int(self.samples) << 1), float(len(self._manual)), float(digest)]

@@ -310,7 +310,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
-                   "occupancy_build")
+                   "occupancy_build", "occupancy_rows")
 
 
 def profile_begin() -> None:
@@ -424,9 +424,14 @@ def mlp_stage(layers: Sequence[dict], dirs: Tensor, ns: int, deep_rgb: bool = Fa
     """One persistent launch over every listed layer (stnerf_mlp_stage).  Each dict: space (PackedNet), motion
     (PackedNet | None), xyz (n,ns,3), raw (n,ns,4) out, times (n,) | None, ray_list / ray_count | None,
     plain_time (bool), rotation (None | (m, centre): the layer's ray-bias launch encodes m @ dir).  Views may be strided as long as all layers share the ray strides.  The arithmetic follows the
-    nets' packing: all "fp32" (exact f32 MFMA) or all "bf16x3" (split-bf16 MFMA)."""
+    nets' packing: all "fp32" (exact f32 MFMA) or all "bf16x3" (split-bf16 MFMA).
+    row_list / row_count (int32 device tensors | None, both or neither): the layer's rows are the first ``row_count`` words
+    ``ray << 8 | k`` of ``row_list`` (``occupancy_rows`` writes them) instead of ray_count x ns; a sample on no list is not
+    written.  With a list on any layer the launch is stnerf_mlp_stage_rows' row-list flavour of the kernel."""
     n = dirs.shape[0]
     arr = (hip.StageLayer * len(layers))()
+    rows = (hip.StageRows * len(layers))()
+    listed = False
     rots = (hip.LayerRotation * len(layers))()       # (outlives the call below)
     strides = None
     precs = set()
@@ -452,13 +457,23 @@ def mlp_stage(layers: Sequence[dict], dirs: Tensor, ns: int, deep_rgb: bool = Fa
         if ly.get("rotation") is not None:
             _rotation_struct(rots[i], ly["rotation"])
             a.rotation = C.pointer(rots[i])
+        if (ly.get("row_list") is None) != (ly.get("row_count") is None):
+            raise ValueError("mlp_stage: a layer's row_list and row_count go together")
+        if ly.get("row_list") is not None:
+            rows[i].row_list = hip.dptr(ly["row_list"], torch.int32, "row_list").value
+            rows[i].row_count = hip.dptr(ly["row_count"], torch.int32, "row_count").value
+            listed = True
     if precs not in ({"fp32"}, {"bf16x3"}):
         raise ValueError(f"mlp_stage: every network of a launch must be packed 'fp32' or every one 'bf16x3' (got {sorted(precs)})")
     bx = 4 if precs == {"bf16x3"} else 0
     queue = torch.zeros(1, dtype=torch.int32, device=dirs.device)
     ray_bias = torch.empty(len(layers), n, 128, dtype=torch.float32, device=dirs.device)   # rgb_net.1 per ray (stnerf_rgb_ray_bias)
-    hip.check(hip.lib().stnerf_mlp_stage(arr, len(layers), n, ns, dp, ds, strides[2], strides[0], strides[1],
-                                         (1 if deep_rgb else 0) | (2 if sigmoid_rgb else 0) | bx,
+    flags = (1 if deep_rgb else 0) | (2 if sigmoid_rgb else 0) | bx
+    if listed:
+        hip.check(hip.lib().stnerf_mlp_stage_rows(arr, rows, len(layers), n, ns, dp, ds, strides[2], strides[0], strides[1], flags,
+                                                  C.c_void_p(queue.data_ptr()), hip.dptr(ray_bias), hip.stream_ptr()), "stnerf_mlp_stage_rows")
+        return
+    hip.check(hip.lib().stnerf_mlp_stage(arr, len(layers), n, ns, dp, ds, strides[2], strides[0], strides[1], flags,
                                          C.c_void_p(queue.data_ptr()), hip.dptr(ray_bias), hip.stream_ptr()), "stnerf_mlp_stage")
 
 
@@ -611,8 +626,16 @@ def fill_edits(dst, edits, l):
             dst[i].scale, dst[i].has_scale = float(sc), 1
 
 
-def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool) -> int:
-    nb = hip.lib().stnerf_render_workspace_bytes(n, l, n1, n2, int(only_coarse))
+def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None) -> int:
+    """Bytes of ``render_rays``'s workspace.  ``occupancy_samples``: the per-layer flags of the sample cull or None -- only
+    with a flag set does the workspace grow, by the flagged layers' row lists (stnerf_render_workspace_bytes_samples)."""
+    if occupancy_samples is not None and any(occupancy_samples):
+        if len(occupancy_samples) != l:
+            raise ValueError(f"occupancy_samples must have one entry per layer ({l}), got {len(occupancy_samples)}")
+        flags = (C.c_int32 * l)(*(int(bool(f)) for f in occupancy_samples))
+        nb = hip.lib().stnerf_render_workspace_bytes_samples(n, l, n1, n2, int(only_coarse), flags)
+    else:
+        nb = hip.lib().stnerf_render_workspace_bytes(n, l, n1, n2, int(only_coarse))
     if nb < 0:
         hip.check(int(nb), "stnerf_render_workspace_bytes")
     return int(nb)
@@ -689,9 +712,39 @@ def occupancy_cull(xyz: Tensor, mask: Tensor, table, counts: Optional[Tensor] = 
     return mask
 
 
+def occupancy_rows(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None,
+                   row_list: Optional[Tensor] = None, row_count: Optional[Tensor] = None, counts: Optional[Tensor] = None):
+    """One layer's row list of the sample cull (stnerf_occupancy_rows; include/stnerf.h states the rule).  xyz (n,ns,3) and raw
+    (n,ns,4) are the layer's slices (strided views whose dim 0 is the ray); grid = (bits, res, lo, inv_cell), the layer's table
+    entry; ray_list / ray_count: its work list or None (every ray).  Writes one int32 word ``ray << 8 | k`` per listed sample of
+    the listed rays into ``row_list`` (at least n x ns words; made here when None), their number into ``row_count`` (1,), and four
+    zero words into raw at every sample of those rays that is NOT listed.  counts: int64 (>= layer + 1, 2) | None accumulates
+    (samples tested, samples skipped) in row ``layer``.  -> (row_list, row_count)."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
+        raise ValueError(f"occupancy_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
+    n, ns = xyz.shape[0], xyz.shape[1]
+    if grid is None:
+        raise ValueError("occupancy_rows: the layer's grid (bits, res, lo, inv_cell) is required")
+    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
+    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
+    if row_list is None:
+        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
+    if row_count is None:
+        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
+    if counts is not None and (counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] <= int(layer)):
+        raise ValueError(f"occupancy_rows: counts must be int64 (> {int(layer)}, 2), got {tuple(counts.shape)}")
+    entry = _occupancy_table([grid], 1)
+    lp, cp = _worklist(ray_list, ray_count)
+    hip.check(hip.lib().stnerf_occupancy_rows(lp, cp, n, int(layer), xp, xs, ns, entry, rp, rs, hip.dptr(row_list, torch.int32, "row_list"),
+                                              row_list.numel(), hip.dptr(row_count, torch.int32, "row_count"),
+                                              hip.dptr(counts, torch.int64, "counts"), hip.stream_ptr()), "stnerf_occupancy_rows")
+    return row_list, row_count
+
+
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
                 jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
-                layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None):
+                layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None,
+                occupancy_samples=None, sample_counts: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -701,7 +754,10 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     ``layer_alpha``: params.l density factors, one per layer, for the fine composite (stnerf_render_rays_opacity; the library
     refuses an entry that is negative or not finite); params.alpha is ignored then.  None: params.alpha on layer 2, as ever.
     ``occupancy``: per layer None | (bits, res, lo, inv_cell), the table of ``occupancy_cull`` (stnerf_render_rays_occupancy): performer
-    pairs whose coarse points all lie in empty cells are dropped before the networks; ``occupancy_counts``: int32 (l,2) | None."""
+    pairs whose coarse points all lie in empty cells are dropped before the networks; ``occupancy_counts``: int32 (l,2) | None.
+    ``occupancy_samples``: per layer a flag, or None -- a flagged layer (it needs a grid) is sample-culled too: both stages evaluate
+    only the samples whose point lies in an occupied cell, the others get zero outputs (stnerf_render_rays_samples; the workspace is
+    ``render_workspace_bytes(..., occupancy_samples=...)``); ``sample_counts``: int64 (l,2) | None = (samples tested, skipped)."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -730,7 +786,20 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
     if layer_alpha is not None and len(layer_alpha) != l:
         raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
-    if occupancy is not None:
+    if occupancy_samples is not None and any(occupancy_samples):
+        if occupancy is None or len(occupancy_samples) != l:
+            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
+        if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):
+            raise ValueError(f"occupancy_counts must be ({l},2) int32, got {tuple(occupancy_counts.shape)}")
+        if sample_counts is not None and tuple(sample_counts.shape) != (l, 2):
+            raise ValueError(f"sample_counts must be ({l},2) int64, got {tuple(sample_counts.shape)}")
+        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
+        flags = (C.c_int32 * l)(*(int(bool(f)) for f in occupancy_samples))
+        hip.check(hip.lib().stnerf_render_rays_samples(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
+                                                       _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
+                                                       flags, hip.dptr(sample_counts, torch.int64, "sample_counts"), hip.stream_ptr()),
+                  "stnerf_render_rays_samples")
+    elif occupancy is not None:
         occ = _occupancy_table(occupancy, l)
         if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):
             raise ValueError(f"occupancy_counts must be ({l},2) int32, got {tuple(occupancy_counts.shape)}")

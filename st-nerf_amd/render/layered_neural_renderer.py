@@ -153,8 +153,9 @@ class LayeredNeuralRenderer:
     def occupancy(self):
         """The ``stnerf_amd.OccupancyGrids`` attached to the model, or None: while one is attached the performer rays that cross
         only empty cells of their performer's grid are culled before the networks run (``LayeredRFRender.set_occupancy``).
-        Setting True attaches fresh grids with the defaults, an ``OccupancyGrids`` attaches that one, False / None detaches;
-        not in the reference (keyword-only, off by default)."""
+        Setting True attaches fresh grids with the defaults, ``"samples"`` fresh grids with ``samples=True`` (kept rays skip the
+        samples in empty cells too), an ``OccupancyGrids`` attaches that one, False / None detaches; not in the reference
+        (keyword-only, off by default)."""
         return getattr(self.model, "_occupancy", None)
 
     @occupancy.setter
@@ -165,8 +166,11 @@ class LayeredNeuralRenderer:
         elif value is None or isinstance(value, bool):
             if bool(value) != (self.occupancy is not None):
                 self.model.set_occupancy(OccupancyGrids() if value else None)
+        elif isinstance(value, str) and value == "samples":
+            if self.occupancy is None or not self.occupancy.samples:
+                self.model.set_occupancy(OccupancyGrids(samples=True))
         else:
-            raise TypeError(f"occupancy is False, True or an OccupancyGrids, got {type(value).__name__}")
+            raise TypeError(f"occupancy is False, True, \"samples\" or an OccupancyGrids, got {type(value).__name__}")
 
     # ---- layer display / knobs (:643-686, :740-741) ----------------------------------------------------
     def hide_layer(self, layer_id):
