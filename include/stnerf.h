@@ -756,6 +756,62 @@ int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes,
                                int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
                                stnerf_stream_t stream);
 
+/* ---- early ray termination (csrc/termination.hip) -------------------------------------------------------
+ * Opt-in, inference only, the FINE stage only: fine samples that the coarse pass shows to lie behind enough opacity get zero
+ * outputs instead of a network evaluation.  Not in the reference.
+ *   Stop depth.  One ray after the coarse composite: t[l][n1] its coarse depths, wM[l][n1] its coarse MERGED weights at source
+ *   index (stnerf_composite_scene's merged_weights, after the coarse density edits).  The l n1 samples are merged by depth,
+ *   stably, ties broken by the source index layer n1 + k -- the compositor's `order`; every layer's depths ascend, so this is an
+ *   l-way merge in which the lower layer wins a tie.  The merged list is walked j = 0, 1, .. with ONE fp32 accumulator and one
+ *   fp32 add per step, in this order: A <- A + wM[src(j)].  j* is the first j with !(1.0f - A > tau) -- a NaN stops the walk.
+ *   t_stop is the depth of merged sample j* + 1 (sample j's weight belongs to the interval that ends at the next merged depth);
+ *   t_stop = +inf when there is no such j or j* is the last sample.  tau: fp32 in [0, 1).  Depths are never NaN.
+ *   Hidden sample.  Sample k of layer i of the fine stage is HIDDEN when t_f[ray][i][k] > t_stop[ray]; a NaN depth is not
+ *   hidden.  A hidden sample gets raw_f[ray][i][k] = {0, 0, 0, 0}, four exact zero words; no network and no MotionNet runs on it.
+ *   A sample that is not hidden is evaluated exactly as without termination.  Nothing else changes: depths, points, masks, the
+ *   compositor and the scene passes see a `raw` buffer and behave as they always did.
+ *   With a sample-culling grid on the layer a sample is LISTED when it is listed by the grid rule above AND not hidden.
+ * stnerf_ray_stop: t[n][l][n1], merged_weights[n][l][n1] -> t_stop[n].  One launch, one lane per ray (an l-way merge in
+ * registers).  STNERF_EINVAL: a null pointer, l outside 1..STNERF_MAX_LAYERS, n1 < 1, tau outside [0, 1) or NaN. */
+int stnerf_ray_stop(const float* t, const float* merged_weights, int64_t n, int l, int n1, float tau, float* t_stop,
+                    stnerf_stream_t stream);
+/* stnerf_visibility_rows makes one layer's row list under this rule: stnerf_occupancy_rows' contract (the rows of a ray
+ * contiguous and ascending in k, the order of the rays free, row_count zeroed by the call, the zero float4 of every not-listed
+ * sample of every tested ray and nothing else of raw, counts_or_null row `layer` += (samples tested, samples not listed)) with
+ *   t: the LAYER's slice of the stage's depths, ray stride t_ray_stride floats; t_stop[n] indexed by the ray;
+ *   grid_host_or_null: the layer's grid, or NULL (or bits == NULL) = no grid: every sample that is not hidden is listed, and xyz
+ *     is not read (it may be NULL);
+ *   layer 0 allowed (without a grid; ray_list NULL = rays 0 .. n-1).
+ * STNERF_EINVAL: ns > 256, n > 2^23, capacity < n * ns, a grid on layer 0, a bad grid, a grid without xyz. */
+int stnerf_visibility_rows(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz,
+                           int64_t xyz_ray_stride, const float* t, int64_t t_ray_stride, const float* t_stop, int ns,
+                           const stnerf_occupancy* grid_host_or_null, float* raw, int64_t raw_ray_stride, int32_t* row_list,
+                           int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream);
+/* stnerf_render_rays_samples with early ray termination.  terminate_host: params->l flags (host) or NULL = none, which is what
+ * stnerf_render_rays_samples forwards and which -- like a table of zeros, or only_coarse -- makes exactly the launches it made, in
+ * a workspace of stnerf_render_workspace_bytes_samples.  With a flag set: the coarse composite also writes its merged weights
+ * (into the region of the fine points, unwritten until the resampler runs), stnerf_ray_stop follows it, and after the
+ * resampler and the MotionNet-reuse launches of the other layers each flagged layer's fine row list is made by
+ * stnerf_visibility_rows (with the layer's grid where it is sample-culled too, in place of stnerf_occupancy_rows); the fine stage
+ * walks the lists.  Layer 0 may be flagged (it needs no grid); it is NOT terminated while cache_host is in CAPTURE or REUSE mode
+ * (its raw outputs would depend on the performers).  A flagged performer's MotionNet runs fused, as a sample-culled layer's.
+ * STNERF_EINVAL before any launch: tau outside [0, 1); params->precision == 2; opacity that differs between the two composites
+ * (params->alpha != 1 with l > 2, or a layer_alpha_host entry != 1: the coarse composite ignores them, so its stop depth would
+ * be wrong); n1 + n2 > 256 or n > 2^23; misaligned counters.  The workspace grows by n floats (t_stop) and one row list per flagged
+ * layer that is not sample-culled: stnerf_render_workspace_bytes_terminated.  visibility_counts_or_null: device, int64 [l][2] =
+ * (fine samples tested, not listed) per terminated layer, accumulated. */
+int64_t stnerf_render_workspace_bytes_terminated(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples_host,
+                                                 const int32_t* terminate_host);
+int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                  const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                                  const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                  float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                  const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                                  float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                                  int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
+                                  float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
+                                  stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

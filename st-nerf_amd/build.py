@@ -23,6 +23,7 @@ SOURCES = [
     ("composite.hip", ["-ffp-contract=off"]),
     ("resample.hip", ["-ffp-contract=off"]),
     ("occupancy.hip", ["-ffp-contract=off"]),
+    ("termination.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

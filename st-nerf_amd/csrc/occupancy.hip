@@ -9,34 +9,11 @@
 #include <algorithm>
 
 #include "common.h"
+#include "occupancy_grid.h"   // OccGrid, cell_of, point_occupied: the point -> cell rule, shared with termination.hip
 
 using namespace stnerf;
 
 namespace {
-
-// One grid by value (wave-uniform -> SGPRs).
-struct OccGrid {
-    const uint32_t* bits;
-    int32_t rx, ry, rz;
-    float lo[3], inv[3];
-};
-
-// c_a = min(max((int)floorf((p_a - lo_a) inv_a), 0), R_a - 1); the clamp is taken on the floor's float, which gives the same
-// cell for every finite value and for +-inf and keeps the conversion in range.
-__device__ __forceinline__ int cell_of(float p, float lo, float inv, int r) {
-    const float d = p - lo;
-    const float f = floorf(d * inv);
-    return (int)fminf(fmaxf(f, 0.f), (float)(r - 1));
-}
-
-__device__ __forceinline__ bool point_occupied(const OccGrid& g, float x, float y, float z) {
-    if (x != x || y != y || z != z) return true;   // a NaN coordinate counts as occupied
-    const int cx = cell_of(x, g.lo[0], g.inv[0], g.rx);
-    const int cy = cell_of(y, g.lo[1], g.inv[1], g.ry);
-    const int cz = cell_of(z, g.lo[2], g.inv[2], g.rz);
-    const int c = (cz * g.ry + cy) * g.rx + cx;    // < 2^24
-    return (g.bits[c >> 5] >> (c & 31) & 1u) != 0;
-}
 
 // One wave per ray of `layer` at a time: lanes take the pair's points k = lane, lane + 64, ... (12-byte points, contiguous), the
 // wave stops at the first trip with a hit, then goes on to the ray a whole grid of waves further.  counts (or null): [l][2] =

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -85,6 +85,24 @@ extern "C" int64_t stnerf_render_workspace_bytes_samples(int64_t n, int l, int n
     const int c = sampled_layers(l, samples);
     if (c == 0) return base;
     return base + c * ((row_capacity(n, n1, n2, only_coarse) * 4 + 255) & ~int64_t(255)) + STNERF_MAX_LAYERS * 4 + 2 * 256;
+}
+
+// Early ray termination's share (nothing under only_coarse or without a flag): the stop depths, n floats that
+// live from the coarse composite to the fine stage, and a fine row list per flagged layer that the sample cull has not given one.
+static bool any_flag(int l, const int32_t* flags) {
+    for (int i = 0; flags && i < l; ++i)
+        if (flags[i]) return true;
+    return false;
+}
+
+extern "C" int64_t stnerf_render_workspace_bytes_terminated(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
+                                                            const int32_t* terminate) {
+    const int64_t base = stnerf_render_workspace_bytes_samples(n, l, n1, n2, only_coarse, samples);
+    if (base < 0 || only_coarse || !any_flag(l, terminate)) return base;
+    int extra = 0;
+    for (int i = 0; i < l; ++i) extra += terminate[i] && !(samples && samples[i]) ? 1 : 0;
+    const int64_t counts = sampled_layers(l, samples) ? 0 : STNERF_MAX_LAYERS * 4 + 2 * 256;   // (the sample cull's size has them)
+    return base + extra * ((row_capacity(n, n1, n2, 0) * 4 + 255) & ~int64_t(255)) + counts + ((n * 4 + 255) & ~int64_t(255)) + 256;
 }
 
 // The mask the caller gets back is the reference's ray_mask (0 / 1): the sampler's "missed" hint (bit 1) served the compositor and
@@ -310,6 +328,27 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
                                           const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
                                           const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
                                           const int32_t* samples, int64_t* sample_counts, stnerf_stream_t stream) {
+    return stnerf_render_rays_terminated(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
+                                         layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
+                                         0.f, nullptr, nullptr, stream);
+}
+
+// terminate: per-layer flags (host array of p->l entries) or null; tau: the transmittance under which a ray counts as opaque
+// (include/stnerf.h: early ray termination).  With a flag set -- and a fine stage to apply it to -- the coarse composite also writes
+// its merged weights, into xyz_f's region, which nobody writes before the resampler; stnerf_ray_stop turns them into t_stop (a region
+// of its own: it must survive to the fine stage), and a flagged layer's fine row list comes from stnerf_visibility_rows, at the place
+// and time stnerf_occupancy_rows makes a sample-culled layer's: after the resampler and the MotionNet-reuse launches of the other
+// layers.  The coarse stage is untouched.  Layer 0 is listed with ray_list == NULL (every ray): the row-list stage kernels address
+// points, outputs and the ray-bias row by the word's ray, and the ray-bias launch of a layer without a list fills every ray's row.
+// Without a flag, or with only_coarse, the call launches what stnerf_render_rays_samples always launched.
+extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                             const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                             const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                             const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                             const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                             const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
+                                             int64_t* visibility_counts, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -340,7 +379,21 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
         STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the sample cull packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
         STNERF_REQUIRE(((uintptr_t)sample_counts & 7) == 0, "render_rays: sample counts must be 8-byte aligned");
     }
-    const int64_t need = stnerf_render_workspace_bytes_samples(n, l, n1, n2, p->only_coarse, samples);
+    const bool flagged = any_flag(l, terminate);
+    if (flagged) {
+        STNERF_REQUIRE(tau >= 0.f && tau < 1.f, "render_rays: termination with tau = %g outside [0, 1)", (double)tau);
+        STNERF_REQUIRE(p->precision != 2, "render_rays: termination is not built for precision 2 (one launch per network)");
+        STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: termination packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
+        STNERF_REQUIRE(((uintptr_t)visibility_counts & 7) == 0, "render_rays: visibility counts must be 8-byte aligned");
+        if (!p->only_coarse) {   // (only_coarse ignores both opacities and terminates nothing)
+            STNERF_REQUIRE(layer_alpha || l <= 2 || p->alpha == 1.f,
+                           "render_rays: termination with alpha = %g: the coarse composite ignores it, so its stop depth would be wrong", (double)p->alpha);
+            for (int i = 0; layer_alpha && i < l; ++i)
+                STNERF_REQUIRE(layer_alpha[i] == 1.f, "render_rays: termination with layer_alpha[%d] = %g: the coarse composite ignores it, so its stop depth would be wrong",
+                               i, (double)layer_alpha[i]);
+        }
+    }
+    const int64_t need = stnerf_render_workspace_bytes_terminated(n, l, n1, n2, p->only_coarse, samples, terminate);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
     const int cache_mode = cache ? cache->mode : STNERF_BKGD_CACHE_OFF;
@@ -353,6 +406,12 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
                        "render_rays: background cache buffers must be 16-byte aligned");
     }
     const bool cached = cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
+    // bit i: layer i's fine stage is terminated.  Not the background's while its raw outputs go to or come from the cache (they would
+    // depend on the performers), not a hidden performer's (it is in no stage).
+    uint32_t term = 0;
+    if (flagged && !p->only_coarse)
+        for (int i = 0; i < l; ++i)
+            if (terminate[i] && (i == 0 ? cache_mode == STNERF_BKGD_CACHE_OFF : p->shown[i] != 0)) term |= 1u << i;
     if (occ) {
         const int orc = check_occupancy_table(occ, l, "render_rays");
         if (orc) return orc;
@@ -379,10 +438,13 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
     const int64_t row_cap = row_capacity(n, n1, n2, p->only_coarse);
     int32_t* row_list[STNERF_MAX_LAYERS] = {nullptr};
     int32_t* row_count = nullptr;
-    if (n_sampled) {
-        for (int i = 1; i < l; ++i)
-            if (samples[i]) row_list[i] = ws.take<int32_t>(row_cap);
+    float* t_stop = nullptr;
+    const bool lists = flagged && !p->only_coarse;   // (the carve follows the flags, as the size query does)
+    if (n_sampled || lists) {
+        for (int i = 0; i < l; ++i)
+            if ((samples && samples[i]) || (lists && terminate[i])) row_list[i] = ws.take<int32_t>(row_cap);
         row_count = ws.take<int32_t>(STNERF_MAX_LAYERS);
+        if (lists) t_stop = ws.take<float>(n);
     }
     hipStream_t st = as_stream(stream);
     int rc;
@@ -425,6 +487,7 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
             stnerf_stage_rows sr[STNERF_MAX_LAYERS];
             memset(sr, 0, sizeof(sr));
             int ns_l = 0;
+            bool any_list = false;
             for (int pass = 0; pass < 2; ++pass) {
                 for (int i = cached ? 1 : 0; i < l; ++i) {
                     if (i > 0 && !p->shown[i]) continue;
@@ -442,18 +505,27 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
                     e.use_time = timed ? 1 : 0;
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
                     e.rotation = rot ? rot + i : nullptr;
-                    if (row_list[i]) {   // the sample cull: this layer's rows of this stage, and the zeros of the others
+                    const bool culled = samples && samples[i];
+                    if (fine && (term >> i & 1)) {   // termination: the rows that are not hidden (and, sample-culled too, in an occupied cell)
+                        const int r1 = stnerf_visibility_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, t_f + (int64_t)i * ns, (int64_t)l * ns, t_stop, ns,
+                                                              culled ? occ + i : nullptr, e.raw, ws_, row_list[i], row_cap, row_count + i,
+                                                              visibility_counts, stream);
+                        if (r1) return r1;
+                    } else if (culled) {   // the sample cull: this layer's rows of this stage, and the zeros of the others
                         const int r1 = stnerf_occupancy_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, ns, occ + i, e.raw, ws_, row_list[i], row_cap,
                                                              row_count + i, sample_counts, stream);
                         if (r1) return r1;
-                        sr[ns_l - 1].row_list = row_list[i];
-                        sr[ns_l - 1].row_count = row_count + i;
+                    } else {
+                        continue;
                     }
+                    sr[ns_l - 1].row_list = row_list[i];
+                    sr[ns_l - 1].row_count = row_count + i;
+                    any_list = true;
                 }
             }
             if (ns_l == 0) return STNERF_OK;   // (background from the cache, no performer shown: nothing to evaluate)
             set_launch_tag(fine ? 1 : 0);
-            const int r2 = stnerf_mlp_stage_rows(sl, n_sampled ? sr : nullptr, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
+            const int r2 = stnerf_mlp_stage_rows(sl, any_list ? sr : nullptr, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
                                                  (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
                                                  reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + (fine ? 1 : 0)), ray_bias, stream);
             set_launch_tag(-1);
@@ -527,10 +599,15 @@ extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const fl
         cp.threshold[i] = p->density_threshold;
     }
     const bool scene_coarse = scene_out && p->only_coarse;   // (xyz_c is dead: the coarse networks have run)
+    // (termination: the merged weights go where the fine points will be -- scene_coarse is only_coarse, which terminates nothing)
     rc = stnerf_composite_scene(t_c, raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w_c,
-                                nullptr, ray_flags, scene_coarse ? xyz_c : nullptr, scene_coarse ? scene_out : nullptr, stream);
+                                nullptr, ray_flags, scene_coarse ? xyz_c : (term ? xyz_f : nullptr), scene_coarse ? scene_out : nullptr, stream);
     if (rc) return rc;
     if (p->only_coarse) return clear_mask_hints(mask, n * l, as_stream(stream));
+    if (term) {   // (before the resampler overwrites the weights with the fine points)
+        rc = stnerf_ray_stop(t_c, xyz_f, n, l, n1, tau, t_stop, stream);
+        if (rc) return rc;
+    }
 
     // ---- resample + fine points (:459-475), fine networks, fine composite (:538-606)
     rc = stnerf_resample_rot(t_c, w_c, n, l, n1, n2, u, p->seed, p->ray_index_base, p->ray_index_stripe, p->ray_index_period,

@@ -20,6 +20,11 @@ from stnerf_amd.modeling.spacenet import SpaceNet
 Tensor = torch.Tensor
 
 
+def _alpha_acts(model):
+    """``alpha`` acts on layer 2 of the fine composite: there is such a layer and the factor is not 1."""
+    return model.total_layers > 2 and float(model.alpha) != 1.0
+
+
 class LayeredRFRender(nn.Module):
     """modeling/layered_rfrender.py:19-741 -- same constructor, attributes and forward signature."""
 
@@ -109,6 +114,7 @@ class LayeredRFRender(nn.Module):
         self.shard_group = None            # the process group to shard over (None: the default group)
         self._bkgd_cache = None            # stnerf_amd.BackgroundCache or None (set_background_cache)
         self._occupancy = None             # stnerf_amd.OccupancyGrids or None (set_occupancy)
+        self._termination = None           # stnerf_amd.termination.Termination or None (set_termination)
         self.view_key = None               # (view identity, background frame id) of the rays in flight (stnerf_amd.bkgd_cache.view_key),
                                            # set and restored around a call by whoever generated the rays from a camera
                                            # (stnerf_amd.parallel.render_view / render_view_share); None: rays of unknown origin,
@@ -194,6 +200,8 @@ class LayeredRFRender(nn.Module):
             return "layer_alpha"
         if getattr(self, "_occupancy", None) is not None:
             return "occupancy grids (set_occupancy)"
+        if getattr(self, "_termination", None) is not None:
+            return "early ray termination (set_termination)"
         return None
 
     def set_precision(self, precision: str):
@@ -231,6 +239,26 @@ class LayeredRFRender(nn.Module):
         samples of a kept ray whose point lies in an empty cell, in both network stages (their outputs are exact zeros)."""
         self._occupancy = grids
         return self
+
+    # ---- early ray termination (not in the reference) ---------------------------------------------------------
+    def set_termination(self, tau=1e-4, layers=None, background=True):
+        """Skip the fine samples the coarse pass shows are hidden (``stnerf_amd.termination``): once the
+        coarse composite's merged transmittance along a ray has fallen to ``tau`` (fp32 in [0, 1)), the fine samples behind
+        that depth get exact zero outputs and no network evaluation.  ``layers``: the performer / instance layers to terminate
+        (None: every shown one); ``background``: layer 0 too (left alone while a background cache captures or serves it).
+        ``tau=None``, or a ``Termination`` in its place, detaches / attaches one.  The fine stage only; inference only; needs
+        ``alpha == 1`` and no ``layer_alpha`` entry other than 1 (the coarse pass ignores both) and the "stage" schedule."""
+        from stnerf_amd.termination import Termination
+        if tau is None or isinstance(tau, Termination):
+            self._termination = tau
+        else:
+            self._termination = Termination(tau, layers, background)
+        return self
+
+    @property
+    def termination(self):
+        """The attached ``stnerf_amd.termination.Termination`` (tau, layers, background, ``stats()``) or None."""
+        return getattr(self, "_termination", None)
 
     def layer_box_at(self, layer_id, frame_id, retiming=True):
         """The UNEDITED box (8,3), fp32 on the host, of layer ``layer_id`` >= 1 at ``frame_id``: the box table's column of the
@@ -584,7 +612,13 @@ class LayeredRFRender(nn.Module):
                 occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
                 if grids.samples:      # every ray-culled layer is sample-culled too
                     occ_kw.update(occupancy_samples=[e is not None for e in occ_table], sample_counts=grids.sample_counts(rays.device)[:l])
-        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"))
+        term = getattr(self, "_termination", None)
+        if term is not None and not only_coarse:
+            flags = term.flags(self)
+            if any(flags):
+                occ_kw.update(terminate=flags, tau=term.tau, visibility_counts=term.counts(rays.device)[:l])
+        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"),
+                                          **(dict(terminate=occ_kw["terminate"]) if "terminate" in occ_kw else {}))
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != rays.device:
             self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=rays.device)
@@ -708,7 +742,7 @@ class LayeredRFRender(nn.Module):
             if what is not None:
                 raise NotImplementedError(f"{what} on the op-by-op path (training, and batches that mix background frame ids under "
                                           "BKGD_USE_SPACE_TIME): a render-time edit, as rotation is -- call model.eval() or wrap the "
-                                          "render in torch.no_grad(), and clear_instances() / layer_alpha = None to train")
+                                          "render in torch.no_grad(), and clear_instances() / layer_alpha = None / set_termination(None) to train")
         self._layer_alpha_table()          # (its ValueErrors before anything is launched)
         culling = getattr(self, "_occupancy", None) is not None
         if culling and self.replay is not None and any(k in self.replay for k in ("xyz_c", "xyz_f")):
@@ -717,6 +751,16 @@ class LayeredRFRender(nn.Module):
         if culling and self._occupancy.samples and self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
             raise ValueError("occupancy grids with samples=True and mlp_schedule = 'per_net' (one launch per network): the sample cull "
                              "walks row lists in the persistent stage kernels; use mlp_schedule = 'stage' or OccupancyGrids(samples=False)")
+        term = getattr(self, "_termination", None)
+        if term is not None and not only_coarse and any(term.flags(self)):     # (what the library refuses too, before the first piece)
+            if self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
+                raise ValueError("early ray termination with mlp_schedule = 'per_net' (one launch per network): the fine stage walks row "
+                                 "lists in the persistent stage kernels; use mlp_schedule = 'stage' or set_termination(None)")
+            table = self._layer_alpha_table()
+            if (table is None and _alpha_acts(self)) or (table is not None and any(a != 1.0 for a in table)):
+                raise ValueError(f"early ray termination with alpha = {self.alpha} / layer_alpha = {self.layer_alpha}: the coarse composite "
+                                 "ignores both opacities, so its stop depth would be wrong for a layer made transparent in the fine "
+                                 "composite; leave them at 1 or set_termination(None)")
         self._warn_if_eval_with_grad()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None

@@ -310,7 +310,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
-                   "occupancy_build", "occupancy_rows")
+                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows")
 
 
 def profile_begin() -> None:
@@ -626,10 +626,21 @@ def fill_edits(dst, edits, l):
             dst[i].scale, dst[i].has_scale = float(sc), 1
 
 
-def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None) -> int:
+def _layer_flags(flags, l, name):
+    if len(flags) != l:
+        raise ValueError(f"{name} must have one entry per layer ({l}), got {len(flags)}")
+    return (C.c_int32 * l)(*(int(bool(f)) for f in flags))
+
+
+def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None, terminate=None) -> int:
     """Bytes of ``render_rays``'s workspace.  ``occupancy_samples``: the per-layer flags of the sample cull or None -- only
-    with a flag set does the workspace grow, by the flagged layers' row lists (stnerf_render_workspace_bytes_samples)."""
-    if occupancy_samples is not None and any(occupancy_samples):
+    with a flag set does the workspace grow, by the flagged layers' row lists (stnerf_render_workspace_bytes_samples).
+    ``terminate``: the per-layer flags of early ray termination or None -- with a flag set (and a fine stage) the workspace grows
+    by the stop depths and the flagged layers' fine row lists (stnerf_render_workspace_bytes_terminated)."""
+    if terminate is not None:       # (no flag set: the entry returns stnerf_render_workspace_bytes_samples' value)
+        sam = None if occupancy_samples is None or not any(occupancy_samples) else _layer_flags(occupancy_samples, l, "occupancy_samples")
+        nb = hip.lib().stnerf_render_workspace_bytes_terminated(n, l, n1, n2, int(only_coarse), sam, _layer_flags(terminate, l, "terminate"))
+    elif occupancy_samples is not None and any(occupancy_samples):
         if len(occupancy_samples) != l:
             raise ValueError(f"occupancy_samples must have one entry per layer ({l}), got {len(occupancy_samples)}")
         flags = (C.c_int32 * l)(*(int(bool(f)) for f in occupancy_samples))
@@ -741,10 +752,55 @@ def occupancy_rows(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Opt
     return row_list, row_count
 
 
+def ray_stop(t: Tensor, merged_weights: Tensor, tau: float) -> Tensor:
+    """The stop depth of early ray termination (stnerf_ray_stop; include/stnerf.h states the rule): t (n,l,n1) coarse depths and
+    merged_weights (n,l,n1), ``composite_scene``'s coarse merged weights, -> t_stop (n,): the depth of the merged sample after the
+    first one at which 1 - (running sum of the merged weights) is no longer above ``tau``; +inf where the ray never gets there."""
+    if t.dim() != 3 or tuple(merged_weights.shape) != tuple(t.shape):
+        raise ValueError(f"ray_stop: t and merged_weights must be (n,l,n1) alike, got {tuple(t.shape)} and {tuple(merged_weights.shape)}")
+    n, l, n1 = t.shape
+    out = torch.empty(n, dtype=torch.float32, device=t.device)
+    hip.check(hip.lib().stnerf_ray_stop(hip.dptr(t, name="t"), hip.dptr(merged_weights, name="merged_weights"), n, l, n1, float(tau),
+                                        hip.dptr(out), hip.stream_ptr()), "stnerf_ray_stop")
+    return out
+
+
+def visibility_rows(t: Tensor, t_stop: Tensor, raw: Tensor, xyz: Optional[Tensor] = None, grid=None, layer: int = 1,
+                    ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None, row_list: Optional[Tensor] = None,
+                    row_count: Optional[Tensor] = None, counts: Optional[Tensor] = None):
+    """One layer's fine row list under early ray termination (stnerf_visibility_rows): ``occupancy_rows`` with the hidden-sample
+    test.  t (n,ns) and raw (n,ns,4) are the layer's slices (strided views whose dim 0 is the ray), t_stop (n,) ``ray_stop``'s
+    output.  Sample k of a listed ray is listed when ``not t[ray, k] > t_stop[ray]`` and -- with ``grid`` = (bits, res, lo,
+    inv_cell) and the layer's points xyz (n,ns,3) -- its point lies in an occupied cell; the others get four zero words in raw.
+    ``layer`` 0 is allowed (without a grid).  counts: int64 (>= layer + 1, 2) | None.  -> (row_list, row_count)."""
+    if t.dim() != 2 or raw.dim() != 3 or tuple(raw.shape) != (t.shape[0], t.shape[1], 4) or tuple(t_stop.shape) != (t.shape[0],):
+        raise ValueError(f"visibility_rows: t must be (n,ns), raw (n,ns,4) and t_stop (n,), got {tuple(t.shape)}, {tuple(raw.shape)}, {tuple(t_stop.shape)}")
+    n, ns = t.shape
+    if grid is not None and (xyz is None or tuple(xyz.shape) != (n, ns, 3)):
+        raise ValueError(f"visibility_rows: a grid needs the layer's points xyz ({n},{ns},3)")
+    tp, ts = _strided_view_ptr(t, (ns,), "t")
+    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
+    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz") if grid is not None else (C.c_void_p(0), 0)
+    if row_list is None:
+        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=t.device)
+    if row_count is None:
+        row_count = torch.zeros(1, dtype=torch.int32, device=t.device)
+    if counts is not None and (counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] <= int(layer)):
+        raise ValueError(f"visibility_rows: counts must be int64 (> {int(layer)}, 2), got {tuple(counts.shape)}")
+    entry = None if grid is None else _occupancy_table([grid], 1)
+    lp, cp = _worklist(ray_list, ray_count)
+    hip.check(hip.lib().stnerf_visibility_rows(lp, cp, n, int(layer), xp, xs, tp, ts, hip.dptr(t_stop, name="t_stop"), ns, entry, rp, rs,
+                                               hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
+                                               hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+                                               hip.stream_ptr()), "stnerf_visibility_rows")
+    return row_list, row_count
+
+
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,
                 jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
                 layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None,
-                occupancy_samples=None, sample_counts: Optional[Tensor] = None):
+                occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
+                visibility_counts: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -757,7 +813,12 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     pairs whose coarse points all lie in empty cells are dropped before the networks; ``occupancy_counts``: int32 (l,2) | None.
     ``occupancy_samples``: per layer a flag, or None -- a flagged layer (it needs a grid) is sample-culled too: both stages evaluate
     only the samples whose point lies in an occupied cell, the others get zero outputs (stnerf_render_rays_samples; the workspace is
-    ``render_workspace_bytes(..., occupancy_samples=...)``); ``sample_counts``: int64 (l,2) | None = (samples tested, skipped)."""
+    ``render_workspace_bytes(..., occupancy_samples=...)``); ``sample_counts``: int64 (l,2) | None = (samples tested, skipped).
+    ``terminate``: per layer a flag, or None -- early ray termination of the flagged layers' FINE stage (stnerf_render_rays_terminated;
+    include/stnerf.h states the rule): fine samples behind the depth at which the coarse pass leaves a transmittance of at most
+    ``tau`` get zero outputs and no network evaluation.  Layer 0 may be flagged.  The workspace is
+    ``render_workspace_bytes(..., terminate=...)``; ``visibility_counts``: int64 (l,2) | None = (fine samples tested, not listed).
+    The library refuses (ValueError, before any launch) tau outside [0, 1), alpha != 1, a layer_alpha entry != 1, precision 2."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -786,7 +847,22 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
     if layer_alpha is not None and len(layer_alpha) != l:
         raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
-    if occupancy_samples is not None and any(occupancy_samples):
+    if terminate is not None:       # (no flag set: the entry makes stnerf_render_rays_samples' launches)
+        sampled = occupancy_samples is not None and any(occupancy_samples)
+        if sampled and (occupancy is None or len(occupancy_samples) != l):
+            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
+        for name, c in (("occupancy_counts", occupancy_counts), ("sample_counts", sample_counts), ("visibility_counts", visibility_counts)):
+            if c is not None and tuple(c.shape) != (l, 2):
+                raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
+        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
+        hip.check(hip.lib().stnerf_render_rays_terminated(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
+                                                          _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
+                                                          _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
+                                                          hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
+                                                          _layer_flags(terminate, l, "terminate"),
+                                                          hip.dptr(visibility_counts, torch.int64, "visibility_counts"), hip.stream_ptr()),
+                  "stnerf_render_rays_terminated")
+    elif occupancy_samples is not None and any(occupancy_samples):
         if occupancy is None or len(occupancy_samples) != l:
             raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
         if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):

@@ -228,7 +228,9 @@ def layers_fingerprint(model):
     al = [] if alpha is None else [1.0 if a is None else float(a) for a in alpha]
     grids = getattr(model, "_occupancy", None)                 # (occupancy grids: ranks that cull differently render different images)
     occ = [0.0] * 9 if grids is None else [1.0] + grids.fingerprint()
-    return [len(src)] + (src + [0.0] * cap)[:cap] + [-1.0 if alpha is None else len(al)] + (al + [-1.0] * cap)[:cap] + occ
+    term = getattr(model, "_termination", None)                # (early ray termination: tau and the flags change the fine image)
+    trm = [0.0] * 4 if term is None else [1.0] + term.fingerprint()
+    return [len(src)] + (src + [0.0] * cap)[:cap] + [-1.0 if alpha is None else len(al)] + (al + [-1.0] * cap)[:cap] + occ + trm
 
 
 def rays_fingerprint(rays: torch.Tensor):

@@ -33,7 +33,7 @@ class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
-                 layer_alpha=None, s_layer_alpha=None, occupancy=False):
+                 layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -72,6 +72,7 @@ class LayeredNeuralRenderer:
         self.model.layer_alpha = self.layer_alpha
         self.cache_background = cache_background
         self.occupancy = occupancy
+        self.terminate = terminate
         # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
         # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
         # hand the frame's dict to on_frame as the keyword `scene`; not in the reference (keyword-only, off by default)
@@ -171,6 +172,28 @@ class LayeredNeuralRenderer:
                 self.model.set_occupancy(OccupancyGrids(samples=True))
         else:
             raise TypeError(f"occupancy is False, True, \"samples\" or an OccupancyGrids, got {type(value).__name__}")
+
+    @property
+    def terminate(self):
+        """The ``stnerf_amd.termination.Termination`` attached to the model, or None: while one is attached the fine samples that
+        the coarse pass shows to lie behind an opaque stretch of the ray get zero outputs instead of a network evaluation
+        (``LayeredRFRender.set_termination``).  Setting True attaches one with the defaults (tau 1e-4, every layer, the background
+        too), a number one with that tau, a ``Termination`` attaches that one, False / None detaches; not in the reference
+        (keyword-only, off by default)."""
+        return getattr(self.model, "_termination", None)
+
+    @terminate.setter
+    def terminate(self, value):
+        from stnerf_amd.termination import Termination
+        if isinstance(value, Termination):
+            self.model.set_termination(value)
+        elif value is None or isinstance(value, bool):
+            if bool(value) != (self.terminate is not None):
+                self.model.set_termination(1e-4 if value else None)
+        elif isinstance(value, float):
+            self.model.set_termination(value)
+        else:
+            raise TypeError(f"terminate is False, True, a tau or a Termination, got {type(value).__name__}")
 
     # ---- layer display / knobs (:643-686, :740-741) ----------------------------------------------------
     def hide_layer(self, layer_id):

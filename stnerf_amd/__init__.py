@@ -26,4 +26,7 @@ def __getattr__(name):
     if name == "OccupancyGrids":
         from stnerf_amd.occupancy import OccupancyGrids
         return OccupancyGrids
+    if name == "Termination":
+        from stnerf_amd.termination import Termination
+        return Termination
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
