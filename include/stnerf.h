@@ -50,7 +50,7 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
  * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
- * 8 occupancy_build, 9 occupancy_rows; kind: the net kind for 0/1, to_dense for 6, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
+ * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop); kind: the net kind for 0/1, to_dense for 6, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
  * 4 the row-list flavour (stnerf_mlp_stage_rows with at least one listed layer);
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
  * tag: the layer a stnerf_render_rays launch belongs to (-1 otherwise); bytes_per_ray: algorithmic HBM bytes
@@ -811,6 +811,60 @@ int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* box
                                   int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
                                   float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
                                   stnerf_stream_t stream);
+
+/* ---- the background's occupancy grid (csrc/background_rows.hip) ------------------------------------------
+ * Opt-in, inference only: the samples of the background that cross empty cells of a grid over its box get zero outputs instead of
+ * a network evaluation.  Not in the reference.  The ray cull's rule "layer 0 cannot carry a grid" stands (a whole-ray cull of a
+ * layer that runs on every ray saves nothing); this grid is an argument of its own and culls samples only.
+ *   Grid.  A stnerf_occupancy entry as defined above: the same bit layout and the same point-to-cell rule (a NaN coordinate counts
+ *   as occupied; subtraction and product separate fp32 operations), 1..256 cells per axis, spanning the axis-aligned fp32 bounds of
+ *   the 8 corners of the UNEDITED bkgd_bbox.
+ *   Build.  The build above, unchanged: the densities of bkgd_net and bkgd_net_fine at the grid's vertices (through the "fp32"
+ *   packs, after bkgd_time_deform_net where it is used), stnerf_occupancy_build with threshold and dilate.
+ *   Background sample cull.  In a network stage of ns samples (the coarse stage: n1, the fine stage: n1 + n2) and for EVERY ray
+ *   0 .. n-1 -- no mask bit is consulted: the background is evaluated mask or not, evaluated[0] == 2 -- sample k is LISTED when the
+ *   point xyz[ray][0][k] lies in an occupied cell or has a NaN coordinate.  That point is the one the background networks would be
+ *   given: after layer 0's rotation and un-edit, before bkgd_time_deform_net.  A listed sample is evaluated exactly as without the
+ *   cull.  A sample that is not listed gets raw[ray][0][k] = {0, 0, 0, 0}, four exact zero words; no SpaceNet and no MotionNet runs
+ *   on it.  Nothing else changes: depths, points, masks, the resampler, the compositor and the scene passes see a `raw` buffer.
+ *   With early ray termination on layer 0 a fine sample is listed when it is listed by the grid AND not hidden.
+ * stnerf_background_rows makes layer 0's row list of one stage: stnerf_occupancy_rows' output contract -- one word (ray << 8) | k per
+ * listed sample, the rows of a ray contiguous and ascending in k, the order of the rays free, row_count zeroed by the call, the zero
+ * float4 of every not-listed sample written and nothing else of raw -- with
+ *   the slot being the ray: rays 0 .. n-1, no ray list, no device-side count;
+ *   xyz / raw (and t): LAYER 0's slices with their ray strides in floats; grid_host: mandatory, with bits;
+ *   t_or_null / t_stop_or_null: the stage's depths and stnerf_ray_stop's output [n]; with t_stop a sample with t > t_stop[ray] is
+ *     not listed (a NaN depth is not hidden); t_stop NULL: the grid alone, t is not read;
+ *   counts_or_null: device, int64 [2] += (samples tested, samples not listed).
+ * STNERF_EINVAL: ns outside 1..256, n > 2^23, capacity < n * ns, a bad grid or a grid without bits, t_stop without t, raw not
+ * 16-byte aligned (or its stride no multiple of 4 floats), counts not 8-byte aligned.  One launch: a persistent grid of at most
+ * 2048 workgroups of 256; a wave takes runs of 16 rays, keeps their ballots in scalar registers and reserves its range of the list
+ * with one atomic add per run. */
+int stnerf_background_rows(int64_t n, const float* xyz, int64_t xyz_ray_stride, int ns, const stnerf_occupancy* grid_host,
+                           const float* t_or_null, int64_t t_ray_stride, const float* t_stop_or_null, float* raw, int64_t raw_ray_stride,
+                           int32_t* row_list, int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream);
+/* stnerf_render_rays_terminated with the background's grid.  bkgd_grid_host: one entry (host) or NULL (or bits == NULL) = none,
+ * which is what stnerf_render_rays_terminated forwards and which makes exactly the launches it made, in a workspace of
+ * stnerf_render_workspace_bytes_terminated.  occupancy_host[0] and samples_host[0] stay refused.  With a grid: stnerf_background_rows
+ * on the coarse points after the compaction and on the fine points after the resampler and every MotionNet-reuse launch, each right
+ * before its stage, which walks layer 0's row list; only_coarse culls the coarse stage.  Where layer 0's fine stage is terminated
+ * the same launch takes t_f / t_stop in place of stnerf_visibility_rows, and the two share layer 0's one row list.  Background
+ * cache: a REUSE frame makes no rows launch (layer 0 is in no stage); a CAPTURE frame is culled by the grid and, as ever, not
+ * terminated, so the cached raw is the culled one, a function of view and grid only -- the caller keys the cache by the grid.
+ * params->precision == 2: STNERF_EINVAL; so are n1 + n2 > 256, n > 2^23 and misaligned counters.
+ * stnerf_render_workspace_bytes_background: `background` != 0 = a grid with bits will be given; the workspace grows by layer 0's
+ * row list unless termination has given it one.  bkgd_counts_or_null: device, int64 [2] += (samples tested, not listed). */
+int64_t stnerf_render_workspace_bytes_background(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples_host,
+                                                 const int32_t* terminate_host, int background);
+int stnerf_render_rays_background(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                  const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                                  const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                  float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                  const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                                  float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                                  int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
+                                  float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
+                                  const stnerf_occupancy* bkgd_grid_host, int64_t* bkgd_counts_or_null, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

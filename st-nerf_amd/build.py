@@ -24,6 +24,7 @@ SOURCES = [
     ("resample.hip", ["-ffp-contract=off"]),
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),
+    ("background_rows.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated | _background]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -103,6 +103,18 @@ extern "C" int64_t stnerf_render_workspace_bytes_terminated(int64_t n, int l, in
     for (int i = 0; i < l; ++i) extra += terminate[i] && !(samples && samples[i]) ? 1 : 0;
     const int64_t counts = sampled_layers(l, samples) ? 0 : STNERF_MAX_LAYERS * 4 + 2 * 256;   // (the sample cull's size has them)
     return base + extra * ((row_capacity(n, n1, n2, 0) * 4 + 255) & ~int64_t(255)) + counts + ((n * 4 + 255) & ~int64_t(255)) + 256;
+}
+
+// The background grid's share: layer 0 takes ONE row list of row_capacity words, the one termination gives it
+// when both are on, and the lists' counts when no other cull has brought them.  Nothing without a grid.
+extern "C" int64_t stnerf_render_workspace_bytes_background(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
+                                                            const int32_t* terminate, int background) {
+    const int64_t base = stnerf_render_workspace_bytes_terminated(n, l, n1, n2, only_coarse, samples, terminate);
+    if (base < 0 || !background) return base;
+    const bool lists = !only_coarse && any_flag(l, terminate);
+    const int64_t list0 = lists && terminate[0] ? 0 : (row_capacity(n, n1, n2, only_coarse) * 4 + 255) & ~int64_t(255);
+    const int64_t counts = sampled_layers(l, samples) || lists ? 0 : STNERF_MAX_LAYERS * 4 + 2 * 256;
+    return base + list0 + counts;
 }
 
 // The mask the caller gets back is the reference's ray_mask (0 / 1): the sampler's "missed" hint (bit 1) served the compositor and
@@ -349,6 +361,28 @@ extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const
                                              const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
                                              const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
                                              int64_t* visibility_counts, stnerf_stream_t stream) {
+    return stnerf_render_rays_background(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
+                                         layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
+                                         tau, terminate, visibility_counts, nullptr, nullptr, stream);
+}
+
+// bkgd_grid: the background's own occupancy grid (include/stnerf.h: "Background sample cull"; host, one entry) or null.  With bits,
+// layer 0 is sample-culled in every stage it is evaluated in: stnerf_background_rows runs over EVERY ray (no mask bit is consulted:
+// evaluated[0] == 2) on the points the stage is given -- xyz_c after the compaction, xyz_f after the resampler and every
+// MotionNet-reuse launch, since the zeros land in raw_f over t_c / xyz_c -- and the stage walks layer 0's row list.  Where layer 0's
+// fine stage is terminated too the same launch takes t_f / t_stop, in place of stnerf_visibility_rows, and the two share the list.
+// A background cache REUSE frame makes no rows launch (layer 0 is in no stage); a CAPTURE frame is culled by the grid and still not
+// terminated, so the cached raw is a function of view and grid only.  The grid is an argument of its own: occ[0] / samples[0] stay
+// refused.  Without bits the call launches what stnerf_render_rays_terminated always launched, in its workspace.
+extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                             const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                             const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                             const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                             const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                             const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
+                                             int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
+                                             stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -393,7 +427,15 @@ extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const
                                i, (double)layer_alpha[i]);
         }
     }
-    const int64_t need = stnerf_render_workspace_bytes_terminated(n, l, n1, n2, p->only_coarse, samples, terminate);
+    const bool bg = bkgd_grid && bkgd_grid->bits;
+    if (bg) {
+        const int brc = check_background_grid(bkgd_grid, "render_rays");
+        if (brc) return brc;
+        STNERF_REQUIRE(p->precision != 2, "render_rays: the background grid is not built for precision 2 (one launch per network)");
+        STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the background grid packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
+        STNERF_REQUIRE(((uintptr_t)bkgd_counts & 7) == 0, "render_rays: background counts must be 8-byte aligned");
+    }
+    const int64_t need = stnerf_render_workspace_bytes_background(n, l, n1, n2, p->only_coarse, samples, terminate, bg ? 1 : 0);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
     const int cache_mode = cache ? cache->mode : STNERF_BKGD_CACHE_OFF;
@@ -440,9 +482,9 @@ extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const
     int32_t* row_count = nullptr;
     float* t_stop = nullptr;
     const bool lists = flagged && !p->only_coarse;   // (the carve follows the flags, as the size query does)
-    if (n_sampled || lists) {
+    if (n_sampled || lists || bg) {
         for (int i = 0; i < l; ++i)
-            if ((samples && samples[i]) || (lists && terminate[i])) row_list[i] = ws.take<int32_t>(row_cap);
+            if ((samples && samples[i]) || (lists && terminate[i]) || (bg && i == 0)) row_list[i] = ws.take<int32_t>(row_cap);
         row_count = ws.take<int32_t>(STNERF_MAX_LAYERS);
         if (lists) t_stop = ws.take<float>(n);
     }
@@ -506,7 +548,12 @@ extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
                     e.rotation = rot ? rot + i : nullptr;
                     const bool culled = samples && samples[i];
-                    if (fine && (term >> i & 1)) {   // termination: the rows that are not hidden (and, sample-culled too, in an occupied cell)
+                    if (i == 0 && bg) {   // the background's grid: every ray; with termination the same launch drops the hidden samples
+                        const bool stop = fine && (term & 1);
+                        const int r1 = stnerf_background_rows(n, e.xyz, xs, ns, bkgd_grid, stop ? t_f : nullptr, (int64_t)l * ns, stop ? t_stop : nullptr,
+                                                              e.raw, ws_, row_list[0], row_cap, row_count, bkgd_counts, stream);
+                        if (r1) return r1;
+                    } else if (fine && (term >> i & 1)) {   // termination: the rows that are not hidden (and, sample-culled too, in an occupied cell)
                         const int r1 = stnerf_visibility_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, t_f + (int64_t)i * ns, (int64_t)l * ns, t_stop, ns,
                                                               culled ? occ + i : nullptr, e.raw, ws_, row_list[i], row_cap, row_count + i,
                                                               visibility_counts, stream);

@@ -207,6 +207,15 @@ _PROTOS = {
                                                 C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
                                                 C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
                                                 C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "stnerf_background_rows": (C.c_int, [c_i64, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64, c_f32p, c_f32p, c_i64,
+                                         C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stnerf_render_workspace_bytes_background": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                         C.c_int]),
+    "stnerf_render_rays_background": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                                C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                                C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
+                                                C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
+                                                C.POINTER(Occupancy), C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,

@@ -236,7 +236,11 @@ class LayeredRFRender(nn.Module):
         any network runs; the grids are built from the networks' own densities on first use (``density_grid``) or given by the
         caller (``OccupancyGrids.set_manual``).  A culled layer needs ONE frame id per chunk group.  Inference only; the
         background cache's key is unchanged, since grids act on performers.  ``OccupancyGrids(samples=True)`` also skips the
-        samples of a kept ray whose point lies in an empty cell, in both network stages (their outputs are exact zeros)."""
+        samples of a kept ray whose point lies in an empty cell, in both network stages (their outputs are exact zeros).
+        ``OccupancyGrids(background=True)`` (or a manual background grid) sample-culls the background too, on every ray, with a
+        grid over the unedited ``bkgd_bbox``; then -- and only then -- the background cache's key gains the grid's identity, so a
+        cache never serves un-culled outputs to a culled render or the reverse.  Under BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME a
+        culled background needs ONE background frame id per chunk group."""
         self._occupancy = grids
         return self
 
@@ -327,6 +331,19 @@ class LayeredRFRender(nn.Module):
             out.append([float(x) for x in mm[k, 0]])
         return out
 
+    def _background_frame_ids(self, rays, groups):
+        """Per chunk group the background's frame id (column 6), for its occupancy grid; where the background flags make the id an
+        input of the density it must be constant within the group (the min / max check of ``_occupancy_frame_ids``): a grid made
+        at row 0's id applied to rays of another id would cull wrongly and silently."""
+        mm = torch.stack([torch.stack([rays[g[0]:g[1], 6].amin(0), rays[g[0]:g[1], 6].amax(0)]) for g in groups]).cpu()
+        if self._occupancy.background_timed(self):
+            for k, g in enumerate(groups):
+                if float(mm[k, 0]) != float(mm[k, 1]) or mm[k, 0] != mm[k, 0]:
+                    raise ValueError(f"occupancy: the background has frame ids {float(mm[k, 0])} .. {float(mm[k, 1])} among rays {g[0]}..{g[1]} of "
+                                     "one chunk group; under BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME its grid is made at one id -- "
+                                     "render one background frame id per chunk group, or drop the background's grid")
+        return [float(mm[k, 0]) for k in range(len(groups))]
+
     def background_cache_key(self, view_key, piece, window, retiming, only_coarse, pivot=None):
         """(group, piece): the key of a launch piece's background outputs -- host arithmetic only.  The group covers every input
         of layer 0's raw outputs: the view (camera, h, w), the seed, n1 / n2 / only_coarse, the arithmetic and its schedule, the
@@ -335,7 +352,9 @@ class LayeredRFRender(nn.Module):
         BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME make it an input -- the background's frame id.  The piece part is the ray
         range and its ray window.  Deliberately absent: performer frame ids, boxes, edits and shown flags, alpha and the two
         density thresholds -- they act on other layers or after the networks, and a sweep over them must hit.  Of ``rotation`` the
-        group holds layer 0's (m, c) alone: a sweep over the performers' rotations hits."""
+        group holds layer 0's (m, c) alone: a sweep over the performers' rotations hits.  While the attached occupancy grids cull
+        the background (and only then) the group ends with the grid's identity: res / threshold / dilate of a built grid, the
+        digest of a manual one -- the cached outputs are the culled ones."""
         from stnerf_amd.modeling._packed import _params_fingerprint
         view, bkgd_frame = view_key
         l = self.total_layers
@@ -371,6 +390,10 @@ class LayeredRFRender(nn.Module):
                  None if pivot is None else tuple(float(x) for x in pivot.tolist()), float(self.near), float(self.boarder_weight),
                  (bool(self.bkgd_use_deform_time), bool(self.bkgd_use_space_time), bool(self.use_space_time), bool(self.deep_rgb)),
                  tuple(_params_fingerprint(m) for m in nets), bkgd_frame if timed else None, rot0)
+        grids = getattr(self, "_occupancy", None)
+        ident = grids.background_identity() if grids is not None else None
+        if ident is not None:
+            group = group + (ident,)
         return group, (int(piece[0]), int(piece[1]), tuple(int(x) for x in window))
 
     # ---- reference API -----------------------------------------------------------------------
@@ -554,13 +577,15 @@ class LayeredRFRender(nn.Module):
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
-                       scene=False, occupancy_ids=None):
+                       scene=False, occupancy_ids=None, background_id=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
         chunk group, passed only when a layer is rotated.  scene: the in-scene layer passes come back as a sixth tensor (passed
         only by ``render_rays_scene``).  occupancy_ids: the chunk group's frame id per layer, passed only while occupancy grids
-        are attached: one grid per shown performer layer is looked up or built and the table travels with the call."""
+        are attached: one grid per shown performer layer is looked up or built and the table travels with the call.
+        background_id: the chunk group's background frame id, passed only while the attached grids cull the background: its grid
+        is looked up or built and travels with the call as an argument of its own."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.total_layers
         p = hip.RenderParams()
@@ -612,13 +637,18 @@ class LayeredRFRender(nn.Module):
                 occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
                 if grids.samples:      # every ray-culled layer is sample-culled too
                     occ_kw.update(occupancy_samples=[e is not None for e in occ_table], sample_counts=grids.sample_counts(rays.device)[:l])
+        if background_id is not None:
+            bg = self._occupancy.background_grid(self, background_id, rays.device)
+            keep.append(bg)
+            occ_kw.update(background_grid=bg.entry(), background_counts=self._occupancy.background_counts(rays.device))
         term = getattr(self, "_termination", None)
         if term is not None and not only_coarse:
             flags = term.flags(self)
             if any(flags):
                 occ_kw.update(terminate=flags, tau=term.tau, visibility_counts=term.counts(rays.device)[:l])
         need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"),
-                                          **(dict(terminate=occ_kw["terminate"]) if "terminate" in occ_kw else {}))
+                                          **(dict(terminate=occ_kw["terminate"]) if "terminate" in occ_kw else {}),
+                                          **(dict(background=True) if "background_grid" in occ_kw else {}))
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != rays.device:
             self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=rays.device)
@@ -751,6 +781,10 @@ class LayeredRFRender(nn.Module):
         if culling and self._occupancy.samples and self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
             raise ValueError("occupancy grids with samples=True and mlp_schedule = 'per_net' (one launch per network): the sample cull "
                              "walks row lists in the persistent stage kernels; use mlp_schedule = 'stage' or OccupancyGrids(samples=False)")
+        bg_culling = culling and self._occupancy.has_background()
+        if bg_culling and self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
+            raise ValueError("occupancy grids with a background grid and mlp_schedule = 'per_net' (one launch per network): the cull "
+                             "walks row lists in the persistent stage kernels; use mlp_schedule = 'stage' or drop the background's grid")
         term = getattr(self, "_termination", None)
         if term is not None and not only_coarse and any(term.flags(self)):     # (what the library refuses too, before the first piece)
             if self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
@@ -781,6 +815,7 @@ class LayeredRFRender(nn.Module):
             boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
             groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))
         occ_ids = self._occupancy_frame_ids(rays, groups, retiming) if culling and self._occupancy.culled_layers(self) else None
+        bg_ids = self._background_frame_ids(rays, groups) if bg_culling else None
         outs = []
         cap = self.max_rays_per_launch
         first, stripe, period = self.ray_window
@@ -813,7 +848,8 @@ class LayeredRFRender(nn.Module):
                     outs.append(self._render_launch(rays[s:e], bx, pivot, retiming, only_coarse, density_threshold,
                                                     bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ()),
                                                     **(dict(rotations=rot[0]) if rot else {}), **(dict(scene=True) if scene else {}),
-                                                    **(dict(occupancy_ids=occ_ids[gi]) if occ_ids is not None else {})))
+                                                    **(dict(occupancy_ids=occ_ids[gi]) if occ_ids is not None else {}),
+                                                    **(dict(background_id=bg_ids[gi]) if bg_ids is not None else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range(6 if scene else 5))
         self.advance_seed()

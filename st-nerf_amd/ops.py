@@ -310,7 +310,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
-                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows")
+                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows")
 
 
 def profile_begin() -> None:
@@ -632,12 +632,19 @@ def _layer_flags(flags, l, name):
     return (C.c_int32 * l)(*(int(bool(f)) for f in flags))
 
 
-def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None, terminate=None) -> int:
+def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None, terminate=None,
+                           background: bool = False) -> int:
     """Bytes of ``render_rays``'s workspace.  ``occupancy_samples``: the per-layer flags of the sample cull or None -- only
     with a flag set does the workspace grow, by the flagged layers' row lists (stnerf_render_workspace_bytes_samples).
     ``terminate``: the per-layer flags of early ray termination or None -- with a flag set (and a fine stage) the workspace grows
-    by the stop depths and the flagged layers' fine row lists (stnerf_render_workspace_bytes_terminated)."""
-    if terminate is not None:       # (no flag set: the entry returns stnerf_render_workspace_bytes_samples' value)
+    by the stop depths and the flagged layers' fine row lists (stnerf_render_workspace_bytes_terminated).
+    ``background``: a background grid will be given -- the workspace grows by layer 0's row list unless termination has given it one
+    (stnerf_render_workspace_bytes_background)."""
+    if background:
+        sam = None if occupancy_samples is None or not any(occupancy_samples) else _layer_flags(occupancy_samples, l, "occupancy_samples")
+        ter = None if terminate is None else _layer_flags(terminate, l, "terminate")
+        nb = hip.lib().stnerf_render_workspace_bytes_background(n, l, n1, n2, int(only_coarse), sam, ter, 1)
+    elif terminate is not None:       # (no flag set: the entry returns stnerf_render_workspace_bytes_samples' value)
         sam = None if occupancy_samples is None or not any(occupancy_samples) else _layer_flags(occupancy_samples, l, "occupancy_samples")
         nb = hip.lib().stnerf_render_workspace_bytes_terminated(n, l, n1, n2, int(only_coarse), sam, _layer_flags(terminate, l, "terminate"))
     elif occupancy_samples is not None and any(occupancy_samples):
@@ -752,6 +759,38 @@ def occupancy_rows(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Opt
     return row_list, row_count
 
 
+def background_rows(xyz: Tensor, raw: Tensor, grid, t: Optional[Tensor] = None, t_stop: Optional[Tensor] = None,
+                    row_list: Optional[Tensor] = None, row_count: Optional[Tensor] = None, counts: Optional[Tensor] = None):
+    """Layer 0's row list of one stage under the background's grid (stnerf_background_rows; include/stnerf.h states the rule).
+    xyz (n,ns,3) and raw (n,ns,4) are layer 0's slices (strided views whose dim 0 is the ray); grid = (bits, res, lo, inv_cell),
+    mandatory.  EVERY ray 0..n-1 is tested: sample k is listed when its point lies in an occupied cell (or has a NaN coordinate)
+    and -- with t (n,ns) and t_stop (n,), ``ray_stop``'s output -- ``not t[ray, k] > t_stop[ray]``; the others get four zero words
+    in raw.  counts: int64 (2,) | None accumulates (samples tested, not listed).  -> (row_list, row_count)."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
+        raise ValueError(f"background_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
+    n, ns = xyz.shape[0], xyz.shape[1]
+    if grid is None:
+        raise ValueError("background_rows: the background's grid (bits, res, lo, inv_cell) is required")
+    if t is not None and tuple(t.shape) != (n, ns):
+        raise ValueError(f"background_rows: t must be ({n},{ns}), got {tuple(t.shape)}")
+    if t_stop is not None and tuple(t_stop.shape) != (n,):
+        raise ValueError(f"background_rows: t_stop must be ({n},), got {tuple(t_stop.shape)}")
+    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
+    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
+    tp, ts = _strided_view_ptr(t, (ns,), "t") if t is not None else (C.c_void_p(0), 0)
+    if row_list is None:
+        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
+    if row_count is None:
+        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
+    if counts is not None and tuple(counts.shape) != (2,):
+        raise ValueError(f"background_rows: counts must be int64 (2,), got {tuple(counts.shape)}")
+    hip.check(hip.lib().stnerf_background_rows(n, xp, xs, ns, _occupancy_table([grid], 1), tp, ts, hip.dptr(t_stop, name="t_stop"), rp, rs,
+                                               hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
+                                               hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+                                               hip.stream_ptr()), "stnerf_background_rows")
+    return row_list, row_count
+
+
 def ray_stop(t: Tensor, merged_weights: Tensor, tau: float) -> Tensor:
     """The stop depth of early ray termination (stnerf_ray_stop; include/stnerf.h states the rule): t (n,l,n1) coarse depths and
     merged_weights (n,l,n1), ``composite_scene``'s coarse merged weights, -> t_stop (n,): the depth of the merged sample after the
@@ -800,7 +839,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
                 layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None,
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
-                visibility_counts: Optional[Tensor] = None):
+                visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -818,7 +857,12 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     include/stnerf.h states the rule): fine samples behind the depth at which the coarse pass leaves a transmittance of at most
     ``tau`` get zero outputs and no network evaluation.  Layer 0 may be flagged.  The workspace is
     ``render_workspace_bytes(..., terminate=...)``; ``visibility_counts``: int64 (l,2) | None = (fine samples tested, not listed).
-    The library refuses (ValueError, before any launch) tau outside [0, 1), alpha != 1, a layer_alpha entry != 1, precision 2."""
+    The library refuses (ValueError, before any launch) tau outside [0, 1), alpha != 1, a layer_alpha entry != 1, precision 2.
+    ``background_grid``: None | (bits, res, lo, inv_cell), the background's own grid (stnerf_render_rays_background; include/stnerf.h
+    states the rule): in every stage layer 0 is evaluated in, only its samples in occupied cells reach the networks, the others get
+    zero outputs.  The workspace is ``render_workspace_bytes(..., background=True)``; ``background_counts``: int64 (2,) | None =
+    (samples tested, not listed).  The library refuses precision 2.  An entry whose bits are None is no grid: the call makes
+    stnerf_render_rays_terminated's launches."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -847,7 +891,26 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
     if layer_alpha is not None and len(layer_alpha) != l:
         raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
-    if terminate is not None:       # (no flag set: the entry makes stnerf_render_rays_samples' launches)
+    if background_grid is not None:
+        sampled = occupancy_samples is not None and any(occupancy_samples)
+        if sampled and (occupancy is None or len(occupancy_samples) != l):
+            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
+        for name, c in (("occupancy_counts", occupancy_counts), ("sample_counts", sample_counts), ("visibility_counts", visibility_counts)):
+            if c is not None and tuple(c.shape) != (l, 2):
+                raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
+        if background_counts is not None and tuple(background_counts.shape) != (2,):
+            raise ValueError(f"background_counts must be int64 (2,), got {tuple(background_counts.shape)}")
+        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
+        hip.check(hip.lib().stnerf_render_rays_background(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
+                                                          _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
+                                                          _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
+                                                          hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
+                                                          None if terminate is None else _layer_flags(terminate, l, "terminate"),
+                                                          hip.dptr(visibility_counts, torch.int64, "visibility_counts"),
+                                                          (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1),
+                                                          hip.dptr(background_counts, torch.int64, "background_counts"), hip.stream_ptr()),
+                  "stnerf_render_rays_background")
+    elif terminate is not None:       # (no flag set: the entry makes stnerf_render_rays_samples' launches)
         sampled = occupancy_samples is not None and any(occupancy_samples)
         if sampled and (occupancy is None or len(occupancy_samples) != l):
             raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")

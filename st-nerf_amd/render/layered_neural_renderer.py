@@ -155,8 +155,9 @@ class LayeredNeuralRenderer:
         """The ``stnerf_amd.OccupancyGrids`` attached to the model, or None: while one is attached the performer rays that cross
         only empty cells of their performer's grid are culled before the networks run (``LayeredRFRender.set_occupancy``).
         Setting True attaches fresh grids with the defaults, ``"samples"`` fresh grids with ``samples=True`` (kept rays skip the
-        samples in empty cells too), an ``OccupancyGrids`` attaches that one, False / None detaches; not in the reference
-        (keyword-only, off by default)."""
+        samples in empty cells too), ``"background"`` fresh grids with ``background=True`` (the background skips its samples in
+        empty cells of a grid over ``bkgd_bbox``), ``"samples+background"`` both, an ``OccupancyGrids`` attaches that one,
+        False / None detaches; not in the reference (keyword-only, off by default)."""
         return getattr(self.model, "_occupancy", None)
 
     @occupancy.setter
@@ -170,8 +171,13 @@ class LayeredNeuralRenderer:
         elif isinstance(value, str) and value == "samples":
             if self.occupancy is None or not self.occupancy.samples:
                 self.model.set_occupancy(OccupancyGrids(samples=True))
+        elif isinstance(value, str) and value in ("background", "samples+background"):
+            want = value == "samples+background"
+            if self.occupancy is None or not self.occupancy.background or self.occupancy.samples != want:
+                self.model.set_occupancy(OccupancyGrids(samples=want, background=True))
         else:
-            raise TypeError(f"occupancy is False, True, \"samples\" or an OccupancyGrids, got {type(value).__name__}")
+            raise TypeError("occupancy is False, True, \"samples\", \"background\", \"samples+background\" or an OccupancyGrids, "
+                            f"got {value!r}")
 
     @property
     def terminate(self):
