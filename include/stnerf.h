@@ -50,7 +50,8 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
  * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
- * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop); kind: the net kind for 0/1, to_dense for 6, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
+ * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop), 13 copy_layer_raw_listed;
+ * kind: the net kind for 0/1, to_dense for 6 and 13, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
  * 4 the row-list flavour (stnerf_mlp_stage_rows with at least one listed layer);
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
  * tag: the layer a stnerf_render_rays launch belongs to (-1 otherwise); bytes_per_ray: algorithmic HBM bytes
@@ -865,6 +866,73 @@ int stnerf_render_rays_background(const float* rays, int64_t n, const float* box
                                   int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
                                   float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
                                   const stnerf_occupancy* bkgd_grid_host, int64_t* bkgd_counts_or_null, stnerf_stream_t stream);
+
+/* ---- the layer cache (csrc/layer_cache.hip) ---------------------------------------------------------------
+ * The background cache's argument holds for every performer: the resampler works per layer, the device RNG is keyed by (seed, global
+ * ray index, layer, stream, sample), and a layer's sample points depend on the rays and on that layer's own box, edit, rotation and
+ * frame id only.  So layer i's slices of raw_c / raw_f are a function of the view and of layer i's own inputs, whatever the other
+ * layers, the opacities, the background's density threshold and the shown flags of the others do.  (params->density_threshold is
+ * different with retiming: the coarse composite applies it to the performers before it writes the weights the resampler reads, so a
+ * performer's FINE depths, points and raw outputs follow it: it belongs to the caller's key.)  A performer covers a fraction of the view:
+ * its cached slices follow its HIT RAYS instead of being dense.  The CALLER decides when "nothing changed" holds and how large
+ * an entry must be (stnerf_amd.LayerCache keys and sizes it on the host); the library only moves the data.
+ *
+ * stnerf_copy_layer_raw_listed is the compact sibling of stnerf_copy_layer_raw: slot j of dense[capacity][ns][4] <-> raw[rays[j]][layer].
+ *   to_dense != 0 (capture): ray_list / ray_count = the frame's list of the layer (stnerf_compact_rays; device).  With c = *ray_count:
+ *     c <= capacity: *count = c, rays[j] = ray_list[j] and dense[j] = raw[ray_list[j]][layer] for j < c;
+ *     c >  capacity: *count = -1 and nothing else is written (so is a c outside 0 .. n, which stnerf_compact_rays never produces).
+ *     ray_list may BE rays and ray_count BE count (a second slice captured under the list the first one kept): both stay as they are.
+ *   to_dense == 0 (restore): with c = *count: raw[rays[j]][layer] = dense[j] for j < c; a negative c (or one above capacity) copies
+ *     nothing.  No other byte of raw is written.  ray_list is not read.  mismatch_or_null: device int64, += 1 when ray_count is given
+ *     and *ray_count (the frame's own count) differs from c -- a guard the caller reads only when asked.
+ * One wave moves one slot (ns contiguous float4 on both sides), the ray index loaded once per slot, 64-bit indices; a persistent grid
+ * of at most 2048 workgroups of 256 strides over the slots and reads the count on the device: no host sync.  HBM-bound: 32 ns + 4
+ * bytes per slot.  STNERF_EINVAL before any launch: layer 0 (the background has the dense cache) or >= l, ns < 1, negative capacity,
+ * a null pointer, raw / dense not 16-byte aligned, the counter not 8-byte aligned. */
+int stnerf_copy_layer_raw_listed(float* raw, int64_t n, int l, int layer, int ns, const int32_t* ray_list, const int32_t* ray_count,
+                                 float* dense, int32_t* rays, int32_t* count, int64_t capacity, int to_dense, int64_t* mismatch_or_null,
+                                 stnerf_stream_t stream);
+/* One layer's entry of the table stnerf_render_rays_layers takes (host struct; every pointer a device pointer).
+ *   raw_coarse[capacity][n1][4], raw_fine[capacity][n1+n2][4] (NULL with only_coarse): 16-byte aligned; rays[capacity], count[1].
+ *   mode: STNERF_LAYER_CACHE_OFF / _CAPTURE / _REUSE, as the background's modes. */
+#define STNERF_LAYER_CACHE_OFF 0
+#define STNERF_LAYER_CACHE_CAPTURE 1
+#define STNERF_LAYER_CACHE_REUSE 2
+typedef struct stnerf_layer_cache {
+    float* raw_coarse;
+    float* raw_fine;
+    int32_t* rays;
+    int32_t* count;
+    int64_t capacity;
+    int32_t mode;
+} stnerf_layer_cache;
+/* stnerf_render_rays_background with a layer cache.  layers_host: params->l entries (host) or NULL = none, which is what
+ * stnerf_render_rays_background forwards; NULL, or every mode OFF, makes exactly the launches that entry made, in a workspace of the
+ * same size.  Entry 0 must be OFF (the background keeps its own cache, cache_host; both may be in use in one call); a hidden layer's
+ * entry is ignored.  mismatch_or_null: the restore copies' counter, as above.
+ *   A layer in REUSE is left out of both network stages (with precision 2: out of both per-network loops); it gets no stand-alone
+ *   MotionNet launch and no MotionNet-reuse fill, no ray-bias launch and no row-list launch (the captured slice already holds the
+ *   zeros those kernels store).  Its slices are restored where the background's are: the coarse one right after the coarse stage,
+ *   before the compositor reads raw_c; the fine one where the fine stage runs, after every MotionNet-reuse launch of the other
+ *   layers has read t_c / xyz_c.  Sampler, ray cull, compaction, compositor, resampler and scene passes run for every layer in
+ *   every mode, so a REUSE frame is bit-identical to the frame rendered without a cache.
+ *   A layer in CAPTURE renders as usual; its slices are copied out after each stage, rays / count written by the coarse copy and
+ *   walked by the fine one.
+ *   A performer in CAPTURE or REUSE is NOT terminated, exactly as layer 0 under the background cache: its raw outputs would depend
+ *   on the other layers otherwise.  (stnerf_amd clears the terminate flag of every shown performer while a layer cache is attached, from
+ *   a key's first frame on, so that the uncached, the capture and the reuse frames of a run agree.)
+ *   When every evaluated layer comes from a cache no stage is launched at all.
+ * Checked on the host before anything is launched: the modes, entry 0, the pointers and their alignment, the capacity. */
+int stnerf_render_rays_layers(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                              const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                              const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                              float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                              const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                              float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                              int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
+                              float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
+                              const stnerf_occupancy* bkgd_grid_host, int64_t* bkgd_counts_or_null,
+                              const stnerf_layer_cache* layers_host, int64_t* mismatch_or_null, stnerf_stream_t stream);
 
 #ifdef __cplusplus
 }

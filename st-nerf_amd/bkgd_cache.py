@@ -109,7 +109,21 @@ def tag_view_rays(rays, K, T, h: int, w: int, frame_ids=None):
     """Mark `rays` as the untouched rays of the whole view (K, T, h, w) -- for callers that generate them from a camera and hand
     the TENSOR on (the drop-in's device ray generation: the reference's render_pose passes it to layered_batchify_ray)."""
     rays.stnerf_view_key = (view_key(K, T, h, w, frame_ids), rays._version, tuple(rays.shape))
+    rays.stnerf_view_frame_ids = view_frame_ids(frame_ids)
     return rays
+
+
+def view_frame_ids(frame_ids):
+    """The host values a view's frame-id columns were generated with, as a tuple of floats (None without any) -> the value of
+    ``LayeredRFRender.view_frame_ids``: what the layer cache reads a layer's frame id from (no device read per frame)."""
+    if frame_ids is None or len(frame_ids) == 0:
+        return None
+    return tuple(float(f) for f in frame_ids)
+
+
+def tagged_view_frame_ids(rays):
+    """The frame ids `tag_view_rays` put on this very tensor (None where ``tagged_view_key`` gives None)."""
+    return getattr(rays, "stnerf_view_frame_ids", None) if tagged_view_key(rays) is not None else None
 
 
 def tagged_view_key(rays):

@@ -37,6 +37,7 @@ SOURCES = [
     ("mlp_bf16x3_rows.hip", []),
     ("stage_entry.hip", []),
     ("pipeline.hip", []),
+    ("layer_cache.hip", []),
     ("train.hip", []),
     ("train_dw.hip", []),
     ("render_bwd.hip", []),

@@ -1,4 +1,4 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated | _background]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated | _background | _layers]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
@@ -383,6 +383,27 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
                                              const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
                                              int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
                                              stnerf_stream_t stream) {
+    return stnerf_render_rays_layers(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
+                                     layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
+                                     tau, terminate, visibility_counts, bkgd_grid, bkgd_counts, nullptr, nullptr, stream);
+}
+
+// layers: the layer cache's table (include/stnerf.h: stnerf_layer_cache; host, p->l entries) or null.  A performer's raw outputs are a
+// function of the view and of its own inputs, as the background's are, so a layer in REUSE is in no network stage: no stage item, no
+// stand-alone MotionNet or MotionNet-reuse fill (its `reuse` bit is cleared), no ray-bias and no rows launch -- its slices are copied
+// in by stnerf_copy_layer_raw_listed where the background's are, for the rays the slice was captured on.  A layer in CAPTURE renders
+// as usual and is copied out after each stage; the coarse copy keeps the frame's ray list, the fine one walks the kept list.  Neither
+// is terminated (its `term` bit is cleared: the raw outputs would depend on the other layers).  Everything else runs for every layer
+// in every mode.  Without a table, or with every mode OFF, the call launches what stnerf_render_rays_background always launched.
+extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                         const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                         const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                         float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                         const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                         const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                         const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
+                                         int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
+                                         const stnerf_layer_cache* layers, int64_t* mismatch, stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -448,12 +469,31 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
                        "render_rays: background cache buffers must be 16-byte aligned");
     }
     const bool cached = cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
+    // the layer cache: bit i of lcap / lreuse = performer i's slices go to / come from its entry (a hidden layer's entry is ignored)
+    uint32_t lcap = 0, lreuse = 0;
+    if (layers) {
+        STNERF_REQUIRE(layers[0].mode == STNERF_LAYER_CACHE_OFF, "render_rays: layer cache entry 0 must be OFF (the background has its own cache)");
+        STNERF_REQUIRE(((uintptr_t)mismatch & 7) == 0, "render_rays: the layer cache's mismatch counter must be 8-byte aligned");
+        for (int i = 1; i < l; ++i) {
+            const stnerf_layer_cache& e = layers[i];
+            STNERF_REQUIRE(e.mode == STNERF_LAYER_CACHE_OFF || e.mode == STNERF_LAYER_CACHE_CAPTURE || e.mode == STNERF_LAYER_CACHE_REUSE,
+                           "render_rays: unknown layer cache mode %d of layer %d", e.mode, i);
+            if (e.mode == STNERF_LAYER_CACHE_OFF || !p->shown[i]) continue;
+            STNERF_REQUIRE(e.raw_coarse && e.rays && e.count, "render_rays: layer cache entry %d without raw_coarse / rays / count", i);
+            STNERF_REQUIRE(p->only_coarse || e.raw_fine, "render_rays: layer cache entry %d without raw_fine (required unless only_coarse)", i);
+            STNERF_REQUIRE(((uintptr_t)e.raw_coarse & 15) == 0 && (p->only_coarse || ((uintptr_t)e.raw_fine & 15) == 0),
+                           "render_rays: layer cache buffers of layer %d must be 16-byte aligned", i);
+            STNERF_REQUIRE(e.capacity >= 0, "render_rays: layer cache entry %d with a negative capacity", i);
+            (e.mode == STNERF_LAYER_CACHE_REUSE ? lreuse : lcap) |= 1u << i;
+        }
+    }
     // bit i: layer i's fine stage is terminated.  Not the background's while its raw outputs go to or come from the cache (they would
-    // depend on the performers), not a hidden performer's (it is in no stage).
+    // depend on the performers), not a performer's while they go to or come from the layer cache, not a hidden performer's (it is
+    // in no stage).
     uint32_t term = 0;
     if (flagged && !p->only_coarse)
         for (int i = 0; i < l; ++i)
-            if (terminate[i] && (i == 0 ? cache_mode == STNERF_BKGD_CACHE_OFF : p->shown[i] != 0)) term |= 1u << i;
+            if (terminate[i] && (i == 0 ? cache_mode == STNERF_BKGD_CACHE_OFF : p->shown[i] != 0 && !((lcap | lreuse) >> i & 1))) term |= 1u << i;
     if (occ) {
         const int orc = check_occupancy_table(occ, l, "render_rays");
         if (orc) return orc;
@@ -514,7 +554,7 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
         const char* sw = getenv("STNERF_MOTION_REUSE");
         if (!(sw && sw[0] == '0'))
             for (int i = 1; i < l; ++i)
-                if (p->shown[i] && !row_list[i] && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
+                if (p->shown[i] && !row_list[i] && !(lreuse >> i & 1) && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
                     reuse |= 1u << i;
     }
     uint32_t* motion_queue = reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
@@ -532,7 +572,7 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
             bool any_list = false;
             for (int pass = 0; pass < 2; ++pass) {
                 for (int i = cached ? 1 : 0; i < l; ++i) {
-                    if (i > 0 && !p->shown[i]) continue;
+                    if (i > 0 && (!p->shown[i] || (lreuse >> i & 1))) continue;   // (hidden, or from the layer cache)
                     const bool deform = i == 0 ? p->bkgd_use_deform_time != 0 : p->use_deform_time != 0;
                     if ((pass == 0) != deform) continue;
                     const bool timed = (i > 0 ? 1 : p->bkgd_use_space_time) && p->use_space_time;
@@ -570,7 +610,7 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
                     any_list = true;
                 }
             }
-            if (ns_l == 0) return STNERF_OK;   // (background from the cache, no performer shown: nothing to evaluate)
+            if (ns_l == 0) return STNERF_OK;   // (every evaluated layer comes from a cache: nothing to evaluate)
             set_launch_tag(fine ? 1 : 0);
             const int r2 = stnerf_mlp_stage_rows(sl, any_list ? sr : nullptr, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
                                                  (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
@@ -582,7 +622,7 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
         // network by network (the deformed points go back to xyz in between)
         for (int i = cached ? 1 : 0; i < l; ++i) {
             if (i == 0 ? !p->bkgd_use_deform_time : !p->use_deform_time) continue;
-            if (i > 0 && !p->shown[i]) continue;  // a hidden layer's points are never consumed
+            if (i > 0 && (!p->shown[i] || (lreuse >> i & 1))) continue;  // a hidden layer's points are never consumed, a cached layer's neither
             set_launch_tag(i);
             // performers: time_deform_nets[i-1] on the hit rays, fractional frame ids lerp the encodings (:340-356);
             // background: bkgd_time_deform_net on every ray, MotionNet(input_time=False) (:358-367)
@@ -595,7 +635,7 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
             if (r2) return r2;
         }
         for (int i = cached ? 1 : 0; i < l; ++i) {
-            if (i > 0 && !p->shown[i]) continue;
+            if (i > 0 && (!p->shown[i] || (lreuse >> i & 1))) continue;
             set_launch_tag(i);
             const void* net = i == 0 ? (fine ? nets->bkgd_fine : nets->bkgd) : (fine ? nets->space_fine[i] : nets->space[i]);
             const bool timed = (i > 0 ? 1 : p->bkgd_use_space_time) && p->use_space_time;
@@ -617,15 +657,31 @@ extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const
         rc = motion_rows(nets, p, rays, n, i, n1, n1, xyz_c, ray_list, ray_count, nullptr, 0, motion_queue + 2 * i, st);
         if (rc) return rc;
     }
-    // The stage followed by the background cache's copy of layer 0's slice: out of `raw` after a capture frame's stage, into it
-    // in place of the stage's layer-0 items in a reuse frame.
+    // The stage followed by the caches' copies: layer 0's slice (the background cache) and the cached performers' (the layer cache,
+    // compact: the hit rays only) out of `raw` after a capture frame's stage, into it in place of the stage's items in a reuse frame.
     auto stage_and_cache = [&](float* xyz, float* raw, int ns, bool fine, float* kept) -> int {
         const int r2 = stage(xyz, raw, ns, fine, reuse);
-        if (r2 || cache_mode == STNERF_BKGD_CACHE_OFF) return r2;
-        set_launch_tag(0);
-        const int r3 = stnerf_copy_layer_raw(raw, n, l, 0, ns, kept, cache_mode == STNERF_BKGD_CACHE_CAPTURE, stream);
-        set_launch_tag(-1);
-        return r3;
+        if (r2) return r2;
+        if (cache_mode != STNERF_BKGD_CACHE_OFF) {
+            set_launch_tag(0);
+            const int r3 = stnerf_copy_layer_raw(raw, n, l, 0, ns, kept, cache_mode == STNERF_BKGD_CACHE_CAPTURE, stream);
+            set_launch_tag(-1);
+            if (r3) return r3;
+        }
+        for (int i = 1; i < l; ++i) {
+            if (!((lcap | lreuse) >> i & 1)) continue;
+            const stnerf_layer_cache& e = layers[i];
+            const bool capture = lcap >> i & 1;
+            // (the fine capture walks the list the coarse one kept: list and count alias the entry's and stay as they are)
+            const int32_t* lst = capture && fine ? e.rays : ray_list + (int64_t)i * n;
+            const int32_t* cnt = capture && fine ? e.count : ray_count + i;
+            set_launch_tag(i);
+            const int r3 = stnerf_copy_layer_raw_listed(raw, n, l, i, ns, lst, cnt, fine ? e.raw_fine : e.raw_coarse, e.rays, e.count, e.capacity,
+                                                        capture ? 1 : 0, capture ? nullptr : mismatch, stream);
+            set_launch_tag(-1);
+            if (r3) return r3;
+        }
+        return STNERF_OK;
     };
     // (raw_f lies over the whole coarse block: the coarse slice is copied here, before the compositor reads raw_c)
     rc = stage_and_cache(xyz_c, raw_c, n1, false, cache ? cache->raw_coarse : nullptr);

@@ -73,12 +73,20 @@ class BkgdCache(C.Structure):
     _fields_ = [("raw_coarse", C.c_void_p), ("raw_fine", C.c_void_p), ("mode", C.c_int32)]
 
 
+class LayerCache(C.Structure):
+    """stnerf_layer_cache (include/stnerf.h): one performer's compact raw outputs (slot j = hit ray rays[j]), the list, its length
+    (device) and capacity, and what to do with them."""
+    _fields_ = [("raw_coarse", C.c_void_p), ("raw_fine", C.c_void_p), ("rays", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_int64),
+                ("mode", C.c_int32)]
+
+
 class Occupancy(C.Structure):
     """stnerf_occupancy (include/stnerf.h): one layer's bit table (device), its cell counts (Rx, Ry, Rz), lo and R / (hi - lo)."""
     _fields_ = [("bits", C.c_void_p), ("res", C.c_int32 * 3), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
 
 
 BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
+LAYER_CACHE_OFF, LAYER_CACHE_CAPTURE, LAYER_CACHE_REUSE = 0, 1, 2   # STNERF_LAYER_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
 
 
@@ -216,6 +224,13 @@ _PROTOS = {
                                                 C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
                                                 C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
                                                 C.POINTER(Occupancy), C.c_void_p, C.c_void_p]),
+    "stnerf_render_rays_layers": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                            C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                            C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
+                                            C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
+                                            C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, C.c_void_p]),
+    "stnerf_copy_layer_raw_listed": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
+                                               C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_resample": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_uint64, c_i64, c_i64, c_i64, c_f32p,
                                   C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.c_void_p, c_f32p, c_f32p, c_f32p,

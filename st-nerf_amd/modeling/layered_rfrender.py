@@ -7,6 +7,7 @@ interpolation/edit on l x 8 x 3 numbers, chunk bookkeeping and output packing.
 """
 from __future__ import annotations
 
+import hashlib
 import math
 from typing import Optional
 
@@ -113,12 +114,16 @@ class LayeredRFRender(nn.Module):
                                            # entries that are not gathered come back as None
         self.shard_group = None            # the process group to shard over (None: the default group)
         self._bkgd_cache = None            # stnerf_amd.BackgroundCache or None (set_background_cache)
+        self._layer_cache = None           # stnerf_amd.LayerCache or None (set_layer_cache)
         self._occupancy = None             # stnerf_amd.OccupancyGrids or None (set_occupancy)
         self._termination = None           # stnerf_amd.termination.Termination or None (set_termination)
         self.view_key = None               # (view identity, background frame id) of the rays in flight (stnerf_amd.bkgd_cache.view_key),
                                            # set and restored around a call by whoever generated the rays from a camera
                                            # (stnerf_amd.parallel.render_view / render_view_share); None: rays of unknown origin,
                                            # never cached
+        self.view_frame_ids = None         # the host frame ids those rays were generated with (a tuple of floats, one per frame-id
+                                           # column), set and restored beside view_key: where the layer cache reads a layer's
+                                           # frame id from (stnerf_amd.bkgd_cache.view_frame_ids)
 
     FRESH_DRAWS_DEFAULT = False   # what a new model's fresh_draws_per_call starts as (dropin.patch_reference: True)
     SHARD_VIEWS_DEFAULT = False   # what a new model's shard_views starts as (the dropin launcher under torch.distributed.run: True)
@@ -228,6 +233,94 @@ class LayeredRFRender(nn.Module):
         background sample and nothing could be reused.  Detaching restores the per-call advance."""
         self._bkgd_cache = cache
         return self
+
+    def set_layer_cache(self, cache):
+        """Attach a ``stnerf_amd.LayerCache`` (None: detach).  While one is attached, frames of a view whose camera the caller
+        names (``view_key`` / ``view_frame_ids``: ``stnerf_amd.parallel.render_view`` / ``render_view_share``, tagged rays) keep
+        every shown performer's and instance's raw network outputs on the device, compact over the layer's hit rays, and copy
+        them in instead of evaluating the layer for as long as ``layer_cache_key`` of that layer stays the same: nudging,
+        retiming, rotating, fading or hiding ANOTHER layer, any ``layer_alpha``, ``bkgd_density_threshold``.  (With retiming
+        ``density_threshold`` is an input of a performer's fine samples and so part of its key: a sweep over it re-evaluates the
+        performers.)  Bit-identical frames.
+        A key is captured at its second sighting and reused from its third, so a performer that moves every frame costs nothing.
+        A cached performer is not terminated (``set_termination``): its outputs would depend on the other layers.  Calls with
+        caller-made rays, ``replay``, the training path and the per-sample background time path are never cached.  Both caches may
+        be attached at once.  While either is attached ``advance_seed()`` is a no-op (one jitter pattern for a cached run).
+        While a layer cache is attached and the view is known, NO shown performer is terminated -- also one that moves every frame
+        and is never captured --, so that all frames of a run agree; the background's termination stays."""
+        self._layer_cache = cache
+        return self
+
+    def layer_cache_key(self, i, view_key, piece, window, retiming, only_coarse, pivot=None, frame_ids=None, density_threshold=None):
+        """(group, piece): the key of performer / instance ``i``'s raw outputs of a launch piece -- host arithmetic only (the box
+        table's host copy is made once per tensor version, ``_box_table_host``).  The group reads every item of
+        ``background_cache_key`` for layer i: the layer, the view (camera, h, w), the seed, n1 / n2 / only_coarse, the arithmetic
+        and its schedule, the retiming flag and the ray width, the layer's EDITED box at its frame id, its coarse and fine point
+        un-edit with the pivot they use, its (m, c) ray transform with the default centre it would get, near and border, the
+        performer model flags, the parameter versions of spacenets / spacenets_fine / time_deform_nets at ``_module_index(i)``,
+        the layer's frame id (always: its networks take it) and, while occupancy grids are attached, the layer's grid identity
+        and the sample flag.  ``frame_ids``: the host values the view was generated with (default ``view_frame_ids``).
+        ``density_threshold``: the render call's, in the group -- and required -- only with retiming and a fine stage: there the
+        COARSE composite zeroes a performer's densities below it before it writes the layer's weights (layered_rfrender.py:416-418),
+        the resampler draws the layer's fine depths from those weights, so the layer's fine points and fine raw outputs follow the
+        threshold (the coarse ones do not; width-7 rays apply no threshold).  Deliberately absent: everything about other layers,
+        ``display_layers``, ``alpha`` / ``layer_alpha``, ``bkgd_density_threshold`` (they act on other layers or in the fine
+        composite, after the networks) and the termination settings (a cached layer is not terminated)."""
+        from stnerf_amd.modeling._packed import _params_fingerprint
+        l = self.total_layers
+        if isinstance(i, bool) or not isinstance(i, int) or not 1 <= i < l:
+            raise ValueError(f"layer_cache_key: layer {i!r} is not a performer or an instance (1..{l - 1}); the background has its own cache")
+        frame_ids = self.view_frame_ids if frame_ids is None else frame_ids
+        want = l if retiming else 1
+        if frame_ids is None or len(frame_ids) != want:
+            raise ValueError(f"layer_cache_key: the view's frame ids must be {want} host values, got {frame_ids!r}")
+        fid = float(frame_ids[i] if retiming else frame_ids[0])
+        thr = None
+        if retiming and not only_coarse:
+            if density_threshold is None:
+                raise ValueError("layer_cache_key: with retiming and a fine stage the layer's fine samples depend on density_threshold; pass it")
+            thr = float(density_threshold)
+        view = view_key[0]
+        box = self.layer_box_at(i, fid, retiming).clone()
+        if self.scale is not None and pivot is None:
+            pivot = self._pivot()
+        if self.scale is not None and i < len(self.scale):
+            box = (box - pivot) * self.scale[i] + pivot
+        if self.shift is not None and i < len(self.shift) and self.shift[i] is not None:
+            box = box + torch.tensor(self.shift[i], dtype=torch.float32)
+        rot = None
+        if self.rotation is not None:                     # the layer's ray transform (its default centre: the edited box's)
+            sp = self._rotation_specs()
+            if sp is not None and sp[i] is not None:
+                m = sp[i][0].T.contiguous()
+                c = sp[i][1] if sp[i][1] is not None else torch.mean(box, 0)
+                rot = (m.numpy().tobytes(), c.numpy().tobytes())
+        def edit(fine):
+            e = self._point_edits(l, fine)
+            if e is None:
+                return None
+            sh, sc = e[i]
+            return (None if sh is None else tuple(float(x) for x in sh), None if sc is None else float(sc))
+        j = self._module_index(i)
+        nets = [self.spacenets[j], self.spacenets_fine[j]] + ([self.time_deform_nets[j]] if self.use_deform_time else [])
+        prec = self.bkgd_spacenet.precision
+        grid = None
+        grids = getattr(self, "_occupancy", None)
+        if grids is not None:
+            # a built grid: what it is made of beyond this key (res / threshold / dilate; box, frame id, flags and parameter
+            # versions are above); a manual one: the digest of its words and bounds
+            if i in grids._manual:
+                words, res, lo, hi = grids._manual[i][:4]
+                grid = ("manual", res, lo.tobytes(), hi.tobytes(), hashlib.sha256(words.tobytes()).digest()[:8])
+            elif grids.auto:
+                grid = ("built", grids.res, grids.threshold, grids.dilate)
+            grid = None if grid is None else grid + (bool(grids.samples),)
+        group = ("layer", int(i), view, int(self.seed) & 0xFFFFFFFFFFFFFFFF, int(self.coarse_ray_sample), int(self.fine_ray_sample),
+                 bool(only_coarse), prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), 6 + want,
+                 box.numpy().tobytes(), edit(False), edit(True), None if pivot is None else tuple(float(x) for x in pivot.tolist()),
+                 float(self.near), float(self.boarder_weight), (bool(self.use_deform_time), bool(self.use_space_time), bool(self.deep_rgb)),
+                 j, tuple(_params_fingerprint(m) for m in nets), fid, rot, grid, thr)
+        return group, (int(piece[0]), int(piece[1]), tuple(int(x) for x in window))
 
     # ---- occupancy grids (not in the reference beyond utils/vis_density.py) ---------------------------------
     def set_occupancy(self, grids):
@@ -580,7 +673,7 @@ class LayeredRFRender(nn.Module):
                        scene=False, occupancy_ids=None, background_id=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
-        the call's ray tensor when the background cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
+        the call's ray tensor when the background cache or the layer cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
         chunk group, passed only when a layer is rotated.  scene: the in-scene layer passes come back as a sixth tensor (passed
         only by ``render_rays_scene``).  occupancy_ids: the chunk group's frame id per layer, passed only while occupancy grids
         are attached: one grid per shown performer layer is looked up or built and the table travels with the call.
@@ -641,9 +734,14 @@ class LayeredRFRender(nn.Module):
             bg = self._occupancy.background_grid(self, background_id, rays.device)
             keep.append(bg)
             occ_kw.update(background_grid=bg.entry(), background_counts=self._occupancy.background_counts(rays.device))
+        # the layer cache: every shown performer / instance of a piece whose view is known on the host
+        lcache, lkeys = (self._layer_cache if piece is not None else None), {}
+        if lcache is not None and self.view_frame_ids is not None and len(self.view_frame_ids) == (l if retiming else 1):
+            lkeys = {i: self.layer_cache_key(i, self.view_key, piece, window, retiming, only_coarse, pivot, density_threshold=thr)
+                     for i in range(1, l) if self.is_shown_layer(i)}
         term = getattr(self, "_termination", None)
         if term is not None and not only_coarse:
-            flags = term.flags(self)
+            flags = [0 if i in lkeys else f for i, f in enumerate(term.flags(self))]   # (a cached performer is not terminated)
             if any(flags):
                 occ_kw.update(terminate=flags, tau=term.tau, visibility_counts=term.counts(rays.device)[:l])
         need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"),
@@ -662,15 +760,29 @@ class LayeredRFRender(nn.Module):
                 entry, mode = cache.reserve(key, n, p.n1, p.n2, only_coarse, rays.device), hip.BKGD_CACHE_CAPTURE
             if entry is not None:
                 cache_arg = (entry[0], entry[1], mode)
+        # per cached layer: from its entry (third sighting on), into a fresh one (second sighting, room in the budget), or neither
+        lc_kw, wanted, capturing = {}, [], []
+        if lkeys:
+            plans = {i: lcache.plan(k, p.n1, p.n2, only_coarse, rays.device) for i, k in lkeys.items()}
+            wanted = [i for i, k in lkeys.items() if plans[i][1] is None and lcache.wants_count(k)]
+            capturing = [lkeys[i] for i, (mode, _) in plans.items() if mode == hip.LAYER_CACHE_CAPTURE]
+            if any(e is not None for _, e in plans.values()):
+                lc_kw = dict(layer_caches=[plans[i][1].arg(plans[i][0]) if i in plans and plans[i][1] is not None else None for i in range(l)],
+                             layer_mismatch=lcache.mismatch_counter(rays.device))
         try:
-            return ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
-                                   u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
-                                   **(dict(scene=True) if scene else {}), **occ_kw,
-                                   **(dict(layer_alpha=table) if table is not None else {}))
+            out = ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
+                                  u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
+                                  **(dict(scene=True) if scene else {}), **occ_kw, **lc_kw,
+                                  **(dict(layer_alpha=table) if table is not None else {}))
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
                 cache.discard(key)             # (never filled)
+            for k in capturing:
+                lcache.discard(k)
             raise
+        for i in wanted:                       # first sighting: the layer's hit count stays on the device (no sync)
+            lcache.sighted(lkeys[i], out[4][:, i].sum(dtype=torch.int32))
+        return out
 
     def render_rays(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
                     ref_chunk: Optional[int] = None):
@@ -724,8 +836,10 @@ class LayeredRFRender(nn.Module):
     def advance_seed(self):
         """What a finished call does to ``seed`` (``fresh_draws_per_call``; a rank that owns no ray of a sharded view
         calls this too, so that every rank's stream stays the same).  A no-op while a background cache is attached
-        (``set_background_cache``: one jitter pattern for all the frames of a cached run)."""
-        if self.fresh_draws_per_call and self.replay is None and getattr(self, "_bkgd_cache", None) is None:
+        or a layer cache is attached (``set_background_cache`` / ``set_layer_cache``: one jitter pattern for all the frames of a
+        cached run)."""
+        if self.fresh_draws_per_call and self.replay is None and getattr(self, "_bkgd_cache", None) is None \
+                and getattr(self, "_layer_cache", None) is None:
             self.seed = (int(self.seed) + 1) & 0xFFFFFFFFFFFFFFFF   # the next call draws new jitter / resampling numbers
 
     def render_rays_raw(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
@@ -826,7 +940,8 @@ class LayeredRFRender(nn.Module):
                                  "(frame ids that change inside the view: render it unstriped)")
         window_at = (lambda s: (first + s, 0, 0)) if stripe <= 0 else (lambda s: (first + s // stripe * period, stripe, period))
         # the background cache serves calls whose view is known on the host (view_key) and whose draws are the device RNG's
-        cacheable = (getattr(self, "_bkgd_cache", None) is not None and getattr(self, "view_key", None) is not None
+        cacheable = ((getattr(self, "_bkgd_cache", None) is not None or getattr(self, "_layer_cache", None) is not None)
+                     and getattr(self, "view_key", None) is not None
                      and self.replay is None and not train and not per_sample_bkgd_time)
         for gi, (g0, g1, boxes, pivot, *rot) in enumerate(groups):
             for s in range(g0, g1, cap):

@@ -310,7 +310,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
-                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows")
+                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows", "copy_layer_raw_listed")
 
 
 def profile_begin() -> None:
@@ -672,6 +672,58 @@ def copy_layer_raw(raw: Tensor, layer: int, dense: Tensor, to_dense: bool) -> Te
 
 
 # ---------------------------------------------------------------------------------------- occupancy grids
+def copy_layer_raw_listed(raw: Tensor, layer: int, dense: Tensor, rays: Tensor, count: Tensor, to_dense: bool,
+                          ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None, mismatch: Optional[Tensor] = None) -> Tensor:
+    """The compact sibling of ``copy_layer_raw`` (stnerf_copy_layer_raw_listed; include/stnerf.h states the rule): slot j of dense
+    (capacity,ns,4) <-> raw (n,l,ns,4)[rays[j], layer], for a performer ``layer`` >= 1.  ``to_dense`` (capture): ``ray_list`` (int32,
+    at least *ray_count entries) and ``ray_count`` (int32, one element) are the frame's list of the layer; ``rays`` (capacity,) int32 and
+    ``count`` (one int32) receive the list and its length, or count = -1 and nothing else when it exceeds the capacity.  Otherwise
+    (restore) ``rays`` / ``count`` are read and raw[rays[j], layer] = dense[j] for j < count; ``mismatch`` (one int64) += 1 when
+    ``ray_count`` is given and differs from count.  Returns the destination.  No host sync: the counts are read on the device."""
+    if raw.dim() != 4 or raw.shape[3] != 4 or dense.dim() != 3 or tuple(dense.shape[1:]) != (raw.shape[2], 4):
+        raise ValueError(f"copy_layer_raw_listed: raw must be (n,l,ns,4) and dense (capacity,ns,4), got {tuple(raw.shape)} and {tuple(dense.shape)}")
+    n, l, ns, capacity = raw.shape[0], raw.shape[1], raw.shape[2], dense.shape[0]
+    if rays.numel() < capacity or count.numel() < 1:
+        raise ValueError(f"copy_layer_raw_listed: rays must hold {capacity} entries and count one, got {rays.numel()} and {count.numel()}")
+    if to_dense and (ray_list is None or ray_count is None or ray_list.numel() < min(n, capacity)):
+        # (the kernel reads ray_list[j] for j < *ray_count only when that count is at most min(n, capacity))
+        raise ValueError(f"copy_layer_raw_listed: a capture needs ray_count and a ray_list of at least min(n, capacity) = {min(n, capacity)} entries")
+    for name, c in (("ray_count", ray_count), ("mismatch", mismatch)):
+        if c is not None and c.numel() < 1:
+            raise ValueError(f"copy_layer_raw_listed: {name} is empty")
+    # (an empty tensor has no storage and the library refuses null pointers: a capacity of 0 travels with a 16-byte stand-in that
+    # is never dereferenced; so does the raw of n = 0 rays)
+    spare = torch.empty(4, dtype=torch.float32, device=count.device) if capacity == 0 or n == 0 else None
+    as_ptr = lambda t, dtype, name: hip.dptr(t if t.numel() else spare.view(dtype), dtype, name)
+    hip.check(hip.lib().stnerf_copy_layer_raw_listed(as_ptr(raw, torch.float32, "raw"), n, l, int(layer), ns,
+                                                     None if ray_list is None else as_ptr(ray_list, torch.int32, "ray_list"),
+                                                     hip.dptr(ray_count, torch.int32, "ray_count"), as_ptr(dense, torch.float32, "dense"),
+                                                     as_ptr(rays, torch.int32, "rays"), hip.dptr(count, torch.int32, "count"), capacity,
+                                                     int(bool(to_dense)), hip.dptr(mismatch, torch.int64, "mismatch"), hip.stream_ptr()),
+              "stnerf_copy_layer_raw_listed")
+    return dense if to_dense else raw
+
+
+def _layer_cache_table(layer_caches, l, n1, n2, only_coarse):
+    """-> hip.LayerCache array of l entries.  layer_caches: per layer None | (raw_coarse (capacity,n1,4), raw_fine (capacity,n1+n2,4) |
+    None, rays (capacity,) int32, count (1,) int32, mode)."""
+    if len(layer_caches) != l:
+        raise ValueError(f"layer_caches must have one entry per layer ({l}), got {len(layer_caches)}")
+    arr = (hip.LayerCache * l)()
+    for i, e in enumerate(layer_caches):
+        if e is None:
+            continue
+        raw_c, raw_f, rays, count, mode = e
+        cap = raw_c.shape[0]
+        if tuple(raw_c.shape) != (cap, n1, 4) or (raw_f is not None and tuple(raw_f.shape) != (cap, n1 + n2, 4)) or rays.numel() < cap \
+                or count.numel() < 1 or (raw_f is None and not only_coarse):
+            raise ValueError(f"render_rays: layer cache entry {i} of capacity {cap} must be ({cap},{n1},4), ({cap},{n1 + n2},4), {cap} rays and one count")
+        arr[i] = hip.LayerCache(hip.dptr(raw_c, name="layer cache raw_coarse").value, hip.dptr(raw_f, name="layer cache raw_fine").value,
+                                hip.dptr(rays, torch.int32, "layer cache rays").value, hip.dptr(count, torch.int32, "layer cache count").value,
+                                cap, int(mode))
+    return arr
+
+
 def occupancy_words(res) -> int:
     """uint32 words of a bit table of res = (Rx, Ry, Rz) cells."""
     return (int(res[0]) * int(res[1]) * int(res[2]) + 31) // 32
@@ -839,7 +891,8 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 jitter: Optional[Tensor] = None, u: Optional[Tensor] = None, cache=None, rotations=None, scene: bool = False,
                 layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None,
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
-                visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None):
+                visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None,
+                layer_caches=None, layer_mismatch: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -862,7 +915,11 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     states the rule): in every stage layer 0 is evaluated in, only its samples in occupied cells reach the networks, the others get
     zero outputs.  The workspace is ``render_workspace_bytes(..., background=True)``; ``background_counts``: int64 (2,) | None =
     (samples tested, not listed).  The library refuses precision 2.  An entry whose bits are None is no grid: the call makes
-    stnerf_render_rays_terminated's launches."""
+    stnerf_render_rays_terminated's launches.
+    ``layer_caches``: per layer None | (raw_coarse (capacity,n1,4), raw_fine (capacity,n1+n2,4) | None, rays (capacity,) int32, count (1,)
+    int32, mode), the layer cache's table (stnerf_render_rays_layers; include/stnerf.h states the rules): hip.LAYER_CACHE_CAPTURE fills
+    the entry from the layer's hit rays, hip.LAYER_CACHE_REUSE leaves the layer out of the network stages and copies the slices in.
+    Entry 0 must be None.  ``layer_mismatch``: int64 (1,) | None, += 1 per restore whose frame has another hit count than the entry."""
     n, l = rays.shape[0], params.l
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
@@ -891,7 +948,9 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
     if layer_alpha is not None and len(layer_alpha) != l:
         raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
-    if background_grid is not None:
+    if layer_caches is not None or background_grid is not None:
+        # (the two widest entries share their argument checks and tables; stnerf_render_rays_layers is stnerf_render_rays_background
+        # plus the layer cache's table)
         sampled = occupancy_samples is not None and any(occupancy_samples)
         if sampled and (occupancy is None or len(occupancy_samples) != l):
             raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
@@ -900,16 +959,25 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
         if background_counts is not None and tuple(background_counts.shape) != (2,):
             raise ValueError(f"background_counts must be int64 (2,), got {tuple(background_counts.shape)}")
+        if layer_mismatch is not None and layer_mismatch.numel() < 1:
+            raise ValueError("layer_mismatch must hold one int64")
         table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
-        hip.check(hip.lib().stnerf_render_rays_background(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
-                                                          _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
-                                                          _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
-                                                          hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
-                                                          None if terminate is None else _layer_flags(terminate, l, "terminate"),
-                                                          hip.dptr(visibility_counts, torch.int64, "visibility_counts"),
-                                                          (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1),
-                                                          hip.dptr(background_counts, torch.int64, "background_counts"), hip.stream_ptr()),
-                  "stnerf_render_rays_background")
+        bg = None
+        if background_grid is not None:
+            bg = (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1)
+        shared = (*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
+                  _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
+                  _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
+                  hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
+                  None if terminate is None else _layer_flags(terminate, l, "terminate"),
+                  hip.dptr(visibility_counts, torch.int64, "visibility_counts"), bg,
+                  hip.dptr(background_counts, torch.int64, "background_counts"))
+        if layer_caches is not None:
+            hip.check(hip.lib().stnerf_render_rays_layers(*shared, _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse)),
+                                                          hip.dptr(layer_mismatch, torch.int64, "layer_mismatch"), hip.stream_ptr()),
+                      "stnerf_render_rays_layers")
+        else:
+            hip.check(hip.lib().stnerf_render_rays_background(*shared, hip.stream_ptr()), "stnerf_render_rays_background")
     elif terminate is not None:       # (no flag set: the entry makes stnerf_render_rays_samples' launches)
         sampled = occupancy_samples is not None and any(occupancy_samples)
         if sampled and (occupancy is None or len(occupancy_samples) != l):

@@ -373,11 +373,20 @@ def render_rays_sharded(model, rays, chuncks: int, density_threshold=0.0, bkgd_d
 
 
 def _view_key(model, K, T, h, w, frame_ids):
-    """The view key of rays generated from this camera, for a model with a background cache attached (else None: no cost)."""
-    if getattr(model, "_bkgd_cache", None) is None:
+    """The view key of rays generated from this camera, for a model with a background cache or a layer cache attached (else None:
+    no cost)."""
+    if getattr(model, "_bkgd_cache", None) is None and getattr(model, "_layer_cache", None) is None:
         return None
     from stnerf_amd.bkgd_cache import view_key
     return view_key(K, T, h, w, frame_ids)
+
+
+def _view_frame_ids(model, frame_ids):
+    """The host frame ids of the view, set beside the view key (``LayeredRFRender.view_frame_ids``; None without a cache)."""
+    if getattr(model, "_bkgd_cache", None) is None and getattr(model, "_layer_cache", None) is None:
+        return None
+    from stnerf_amd.bkgd_cache import view_frame_ids
+    return view_frame_ids(frame_ids)
 
 
 def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, bkgd_density_threshold=0.0,
@@ -394,9 +403,9 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     n_total = h * w
     if act is None or n_total < chuncks:
         rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device)
-        saved_key = getattr(model, "view_key", None)
+        saved_key, saved_ids = getattr(model, "view_key", None), getattr(model, "view_frame_ids", None)
         try:
-            model.view_key = _view_key(model, K, T, h, w, frame_ids)
+            model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids), _view_frame_ids(model, frame_ids)
             with torch.no_grad():
                 if scene:   # (layered_batchify_ray's two cases: a view of less than one chunk renders with the model's defaults)
                     if n_total < chuncks:
@@ -405,7 +414,7 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
                 return layered_batchify_ray(model, rays, None, None, chuncks=chuncks, density_threshold=density_threshold,
                                             bkgd_density_threshold=bkgd_density_threshold)
         finally:
-            model.view_key = saved_key
+            model.view_key, model.view_frame_ids = saved_key, saved_ids
     if scene:
         raise RuntimeError("render_view(scene=True) on a view sharded over more than one rank: a \"scene\" gather mode is out of scope; "
                            "render the in-scene layer passes on one rank (model.shard_views = False)")
@@ -439,13 +448,14 @@ def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: 
         return torch.zeros((0, packed_width(l, mode)), dtype=torch.float32, device=device)
     rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, first_ray=window[0], n=n_local, device=device, stripe=stripe,
                              period=window[2])
-    saved, saved_key = model.ray_window, getattr(model, "view_key", None)
+    saved, saved_key, saved_ids = model.ray_window, getattr(model, "view_key", None), getattr(model, "view_frame_ids", None)
     try:
         model.ray_window, model.view_key = window, _view_key(model, K, T, h, w, frame_ids)
+        model.view_frame_ids = _view_frame_ids(model, frame_ids)
         with torch.no_grad():
             return pack_outputs(model.render_rays_raw(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks), mode)
     finally:
-        model.ray_window, model.view_key = saved, saved_key
+        model.ray_window, model.view_key, model.view_frame_ids = saved, saved_key, saved_ids
 
 
 def init_from_env(backend: Optional[str] = None, single_device: bool = False):

@@ -33,7 +33,7 @@ class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
-                 layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False):
+                 layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -71,6 +71,7 @@ class LayeredNeuralRenderer:
         self.model.rotation = self.rotation
         self.model.layer_alpha = self.layer_alpha
         self.cache_background = cache_background
+        self.cache_layers = cache_layers
         self.occupancy = occupancy
         self.terminate = terminate
         # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
@@ -149,6 +150,22 @@ class LayeredNeuralRenderer:
         if bool(on) != self.cache_background:
             from stnerf_amd.bkgd_cache import BackgroundCache
             self.model.set_background_cache(BackgroundCache() if on else None)
+
+    @property
+    def cache_layers(self):
+        """True while the model keeps the performers' network outputs of a fixed view across frames
+        (``LayeredRFRender.set_layer_cache``: from one camera, a performer whose own inputs did not change since its last two
+        frames is copied in instead of evaluated -- nudging, retiming, fading or hiding ANOTHER layer, any ``layer_alpha``,
+        ``bkgd_density_threshold`` (with retiming ``density_threshold`` is an input of a performer's fine samples: a sweep over it
+        re-evaluates the performers); no performer is terminated while it is attached; the frames are bit-identical to uncached ones and share one jitter pattern).  Setting it attaches a
+        fresh ``stnerf_amd.LayerCache`` to the model or detaches it; not in the reference (keyword-only, off by default)."""
+        return getattr(self.model, "_layer_cache", None) is not None
+
+    @cache_layers.setter
+    def cache_layers(self, on):
+        if bool(on) != self.cache_layers:
+            from stnerf_amd.layer_cache import LayerCache
+            self.model.set_layer_cache(LayerCache() if on else None)
 
     @property
     def occupancy(self):

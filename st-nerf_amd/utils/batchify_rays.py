@@ -13,13 +13,14 @@ def layered_batchify_ray(model, rays, labels, bboxes, chuncks=512 * 7, near_far=
     all-gathered, so every rank returns what the single-GPU call returns, bit for bit (stnerf_amd.parallel)."""
     N = rays.size(0)
     # rays this package generated from a camera and tagged with their view (the drop-in's device ray generation) may be served
-    # by the model's background cache; any other tensor has no view key and is never cached
+    # by the model's background cache and layer cache; any other tensor has no view key and is never cached
     key = None
-    if getattr(model, "_bkgd_cache", None) is not None and getattr(model, "view_key", None) is None:
-        from stnerf_amd.bkgd_cache import tagged_view_key
+    if (getattr(model, "_bkgd_cache", None) is not None or getattr(model, "_layer_cache", None) is not None) \
+            and getattr(model, "view_key", None) is None:
+        from stnerf_amd.bkgd_cache import tagged_view_frame_ids, tagged_view_key
         key = tagged_view_key(rays)
     if key is not None:
-        model.view_key = key
+        model.view_key, model.view_frame_ids = key, tagged_view_frame_ids(rays)
     try:
         if N < chuncks:
             return model(rays, labels, bboxes, near_far=near_far, near_far_points=near_far_points)
@@ -30,4 +31,4 @@ def layered_batchify_ray(model, rays, labels, bboxes, chuncks=512 * 7, near_far=
         return model.render_rays(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks)
     finally:
         if key is not None:
-            model.view_key = None
+            model.view_key = model.view_frame_ids = None

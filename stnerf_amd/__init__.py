@@ -23,6 +23,9 @@ def __getattr__(name):
     if name == "BackgroundCache":
         from stnerf_amd.bkgd_cache import BackgroundCache
         return BackgroundCache
+    if name == "LayerCache":
+        from stnerf_amd.layer_cache import LayerCache
+        return LayerCache
     if name == "OccupancyGrids":
         from stnerf_amd.occupancy import OccupancyGrids
         return OccupancyGrids
