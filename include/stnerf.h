@@ -934,6 +934,75 @@ int stnerf_render_rays_layers(const float* rays, int64_t n, const float* boxes, 
                               const stnerf_occupancy* bkgd_grid_host, int64_t* bkgd_counts_or_null,
                               const stnerf_layer_cache* layers_host, int64_t* mismatch_or_null, stnerf_stream_t stream);
 
+/* ---- depth-tested occluder compositing (csrc/occluder.hip; DESIGN.md sections 4.2 and 7) -----------------------------------------
+ * Opt-in, inference only, not in the reference: an element that is NOT a radiance field -- a CG prop, a title card on a plane, a
+ * live-action plate with a z-buffer -- put into the scene, hiding what lies behind it and hidden by what lies in front of it.  The
+ * scene passes are sums over whole rays and cannot supply that in post; the merged weight of every sample can.
+ *   Occluder.  occluder[n][5], fp32 on the device, one row {r, g, b, a, z} per ray of the call.  z is a RAY PARAMETER, in the units
+ *   of the depths t the sampler produces (the `depth` output before a caller divides it by far).  a' = a clamped to [0, 1]; a NaN a
+ *   counts as 0.  The row is PRESENT when a' > 0 and z is finite, ABSENT otherwise (a' == 0, z NaN, z +-inf).
+ *   Front and behind.  Defined for the FINAL stage of the render (fine, or coarse with only_coarse) and one present ray with S samples
+ *   per layer: t[l][S] the stage's depths, wM[l][S] its merged weights at source index exactly as stnerf_composite_scene defines
+ *   merged_weights, c_k = {r, g, b} the colours the compositor used (sigmoid(rgb), or raw's own with rgb_activated).  Sample k of
+ *   layer i is BEHIND when t[i][k] >= z, IN FRONT otherwise; a NaN depth is in front.
+ *     front[i][5]  = sum_{k in front} wM {r, g, b, t, 1}          behind[i][5] = the same sum over the samples behind
+ *   A layer without network output on the ray (the layers scene_out zeroes: hidden, missed, a grazing hit) gets five exact zeros in
+ *   both.  The samples are NOT clipped: a sample that starts in front of z keeps its whole weight, although its interval may reach
+ *   behind z (clipping the interval that contains z is out of scope).
+ *   Arithmetic: that of scene_out.  Lane j of the ray's wave takes the samples k = j, j + 64, .. ascending, each step acc = acc + w x
+ *   with the product and the sum separate fp32 operations, and the five sums go through the same in-place wave scan; the one
+ *   difference is that w is replaced by +0.0f on the side the sample does not belong to.  So, bit for bit: a present ray whose z
+ *   exceeds every depth has front == scene_out and behind == +0; one whose z is below every depth has behind == scene_out and
+ *   front == +0.
+ *   Mix, for one present ray; every product, sum and difference is one fp32 operation in the order written:
+ *     Af        = ((front[0][4] + front[1][4]) + ..) + front[l-1][4]
+ *     T         = 1 - Af where that is > 0, else 0 (a NaN gives 0)
+ *     s         = a' T                      q = 1 - a'
+ *     pass_i[c] = front_i[c] + q behind_i[c]                        c = 0..4
+ *     share     = {s r, s g, s b, s z, s}
+ *     occluded_mixed[c] = (((pass_0[c] + pass_1[c]) + ..) + pass_{l-1}[c]) + share[c]
+ *   Outputs, {colour(3), depth, acc} as everywhere: occluded_mixed[n][5]; occluded_scene[n][l][5] = pass_i, layer i's share with the
+ *   occluder in the scene; occluder_share[n][5] = share, the occluder's own premultiplied share; front_out / behind_out[n][l][5].
+ *   On an ABSENT ray occluded_mixed is the bits of mixed_in, occluded_scene and front_out the bits of scene_in, share and behind_out
+ *   zeros, and no sample is read.
+ * stnerf_scene_occluder: t[n][l][S], raw[n][l][S][4], mask[n][l] (NULL = all set), merged_weights[n][l][S] and params_host
+ *   (rgb_activated and evaluated are read) as stnerf_composite_scene took and left them; scene_in[n][l][5] / mixed_in[n][5] its
+ *   scene_out / mixed_out.  occluded_mixed is required, the other four outputs may be NULL.  One launch: one wave per ray over a
+ *   persistent grid, no LDS; a present ray moves the scene pass's 24 B per sample.  STNERF_EINVAL before any launch: a null input
+ *   or occluded_mixed, l outside 1..STNERF_MAX_LAYERS, S < 1, l * S > 65535, raw not 16-byte aligned. */
+int stnerf_scene_occluder(const float* t, const float* raw, const uint8_t* mask, const float* merged_weights, int64_t n, int l, int S,
+                          const stnerf_composite_params* params_host, const float* scene_in, const float* mixed_in,
+                          const float* occluder, float* occluded_mixed, float* occluded_scene, float* occluder_share,
+                          float* front_out, float* behind_out, stnerf_stream_t stream);
+/*   Occluder stop.  An OPAQUE occluder is also a stop depth of early ray termination: after stnerf_ray_stop,
+ *     t_stop[ray] = (present && a' >= 1 && z < t_stop[ray]) ? z : t_stop[ray]
+ *   The hidden-sample rule is unchanged (t_f > t_stop), so everything it hides lies behind the occluder and is multiplied by
+ *   q = 1 - 1 = +0 in the mix, and the merged weight of a sample in front depends only on samples at or before it and on depths:
+ *   with the stop on, occluded_mixed, occluded_scene and occluder_share are BIT-IDENTICAL to the same render with the stop off, on
+ *   every ray.  The plain outputs (mixed_fine, layer_fine, scene_out) become those of the terminated scene, as under termination.
+ * stnerf_occluder_stop: occluder[n][5], t_stop[n] in place.  One launch, one lane per ray.  STNERF_EINVAL: a null pointer. */
+int stnerf_occluder_stop(const float* occluder, int64_t n, float* t_stop, stnerf_stream_t stream);
+/* stnerf_render_rays_layers with an occluder.  occluder: [n][5] on the device or NULL = none, which is what stnerf_render_rays_layers
+ * forwards (with occluder_stops = 0 and three NULL outputs) and which makes exactly the launches that entry made; the workspace size
+ * is the same with or without one.  With an occluder scene_out and occluded_mixed are required (the merged weights exist only with
+ * the scene passes); occluded_scene[n][l][5] and occluder_share[n][5] may be NULL.  stnerf_scene_occluder's launch follows the final
+ * stage's scene pass on the same stream, while that stage's t, raw and merged weights are live.
+ * occluder_stops != 0: stnerf_occluder_stop follows stnerf_ray_stop.  It needs at least one flag of terminate_host set
+ * (STNERF_EINVAL otherwise) and is, with only_coarse, the no-op termination is; what termination refuses stays refused (opacity
+ * other than 1, precision 2) and what it leaves alone stays alone (layer 0 under the background cache, a cached performer). */
+int stnerf_render_rays_occluded(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                                const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                const stnerf_bkgd_cache* cache_host, const stnerf_layer_rotation* rotations_host,
+                                float* scene_out, const float* layer_alpha_host, const stnerf_occupancy* occupancy_host,
+                                int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
+                                float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
+                                const stnerf_occupancy* bkgd_grid_host, int64_t* bkgd_counts_or_null,
+                                const stnerf_layer_cache* layers_host, int64_t* mismatch_or_null, const float* occluder,
+                                int32_t occluder_stops, float* occluded_mixed, float* occluded_scene, float* occluder_share,
+                                stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

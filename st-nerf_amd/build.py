@@ -21,6 +21,7 @@ SOURCES = [
     ("lib.hip", []),
     ("sampler.hip", ["-ffp-contract=off"]),
     ("composite.hip", ["-ffp-contract=off"]),
+    ("occluder.hip", ["-ffp-contract=off"]),
     ("resample.hip", ["-ffp-contract=off"]),
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),

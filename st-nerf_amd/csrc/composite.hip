@@ -25,11 +25,7 @@ namespace stnerf {
 //   delta_k = t_{k+1}-t_k, last = border;  alpha = 1-exp(-relu(sigma) delta);
 //   T_k = prod_{j<k} (1-alpha_j+1e-10);  w = alpha T;  color = sum w sigmoid(rgb); depth = sum w t.
 // ---------------------------------------------------------------------------------------------
-// Running state of one composite: the transmittance carried from block to block and the five weighted sums.
-struct CompositeAcc {
-    float carry = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, cd = 0.f, ca = 0.f;
-};
-
+// (CompositeAcc, the running state of one composite, and composite_store5 are in composite_rules.h)
 // One block of 64 samples (lane = sample): weight of the lane's sample, sums updated.  Every composite of this file is a loop
 // over this function (the kernels are compared bit for bit).  `ok`: the lane holds a sample; an idle lane (ALL = false
 // only) passes finite values, contributes the factor 1 to the transmittance and weight 0 to the sums.
@@ -52,16 +48,6 @@ __device__ __forceinline__ float composite_block(CompositeAcc& A, float sigma, f
     A.cd += w * t;
     A.ca += w;
     return w;
-}
-
-// the five sums over the wave, stored by lane 63 (which holds the totals of the in-place scans)
-__device__ __forceinline__ void composite_store5(const CompositeAcc& A, float* dst, float* dst2, unsigned lane) {
-    const float o0 = wave_scan_add(A.cr), o1 = wave_scan_add(A.cg), o2 = wave_scan_add(A.cb), o3 = wave_scan_add(A.cd),
-                o4 = wave_scan_add(A.ca);
-    if (lane == 63u) {
-        if (dst) { dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3; dst[4] = o4; }
-        if (dst2) { dst2[0] = o0; dst2[1] = o1; dst2[2] = o2; dst2[3] = o3; dst2[4] = o4; }
-    }
 }
 
 // `count` samples read through accessor functors, in index order.  raw_at(k) returns the edited sample

@@ -1,5 +1,6 @@
 // The compositor's rules that its forward (composite.hip) and its backward (render_bwd.hip) must state alike: the
-// post-network density edits of a sample, and which layers of a ray have network output.
+// post-network density edits of a sample, and which layers of a ray have network output; and the weighted sums its forward
+// shares with the occluder split of the merged weights (occluder.hip).
 #pragma once
 #include <math.h>
 
@@ -59,6 +60,33 @@ __device__ __forceinline__ void build_edit_table(float* tab, const stnerf_compos
             tab[i] = p.use_threshold[i] != 0 ? p.threshold[i] : -INFINITY;
             tab[16 + i] = p.sigma_scale[i];
         }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The weighted sums of a composite, shared by the compositor (composite.hip) and the occluder split of its merged weights
+// (occluder.hip): each lane accumulates acc = acc + w x over its samples, the wave's totals come from in-place prefix scans.
+// ---------------------------------------------------------------------------------------------
+// Running state of one composite: the transmittance carried from block to block and the five weighted sums.
+struct CompositeAcc {
+    float carry = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, cd = 0.f, ca = 0.f;
+};
+
+// the five sums over the wave, stored by lane 63 (which holds the totals of the in-place scans)
+__device__ __forceinline__ void composite_store5(const CompositeAcc& A, float* dst, float* dst2, unsigned lane) {
+    const float o0 = wave_scan_add(A.cr), o1 = wave_scan_add(A.cg), o2 = wave_scan_add(A.cb), o3 = wave_scan_add(A.cd),
+                o4 = wave_scan_add(A.ca);
+    if (lane == 63u) {
+        if (dst) { dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3; dst[4] = o4; }
+        if (dst2) { dst2[0] = o0; dst2[1] = o1; dst2[2] = o2; dst2[3] = o3; dst2[4] = o4; }
+    }
+}
+// the same five totals as wave-uniform values, for a caller that goes on computing with them
+__device__ __forceinline__ void composite_total5(const CompositeAcc& A, float (&o)[5]) {
+    o[0] = wave_last(wave_scan_add(A.cr));
+    o[1] = wave_last(wave_scan_add(A.cg));
+    o[2] = wave_last(wave_scan_add(A.cb));
+    o[3] = wave_last(wave_scan_add(A.cd));
+    o[4] = wave_last(wave_scan_add(A.ca));
 }
 
 // Which layers have network output (stnerf_composite_params::evaluated): bit i of `masked` = on the rays layer i's hit mask

@@ -404,7 +404,33 @@ extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const flo
                                          const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
                                          int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
                                          const stnerf_layer_cache* layers, int64_t* mismatch, stnerf_stream_t stream) {
+    return stnerf_render_rays_occluded(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
+                                       layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
+                                       tau, terminate, visibility_counts, bkgd_grid, bkgd_counts, layers, mismatch, nullptr, 0, nullptr, nullptr,
+                                       nullptr, stream);
+}
+
+// occluder: one row {r, g, b, a, z} per ray (include/stnerf.h: depth-tested occluder compositing; device) or null.  With one, the
+// final stage's scene pass is followed by stnerf_scene_occluder on the same buffers -- t, raw and the merged weights, which lie over
+// that stage's points and stay live until the call returns.  occluder_stops: an opaque row's depth is folded into t_stop right after
+// stnerf_ray_stop, so the flagged layers' row lists leave out the fine samples behind it; the occluded outputs keep their bits.
+// Without an occluder the call launches what stnerf_render_rays_layers always launched; the workspace is the same either way.
+extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                                           const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
+                                           const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                                           float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                                           const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
+                                           const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
+                                           const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
+                                           int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
+                                           const stnerf_layer_cache* layers, int64_t* mismatch, const float* occluder,
+                                           int32_t occluder_stops, float* occluded_mixed, float* occluded_scene, float* occluder_share,
+                                           stnerf_stream_t stream) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
+    STNERF_REQUIRE(!occluder || (scene_out && occluded_mixed),
+                   "render_rays: an occluder needs scene_out and occluded_mixed (the merged weights exist only with the scene passes)");
+    STNERF_REQUIRE(occluder || (!occluder_stops && !occluded_mixed && !occluded_scene && !occluder_share),
+                   "render_rays: occluder_stops / occluded outputs without an occluder");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
     const int l = p->l, n1 = p->n1, n2 = p->n2, S = n1 + n2, rs = p->ray_stride;
@@ -435,6 +461,8 @@ extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const flo
         STNERF_REQUIRE(((uintptr_t)sample_counts & 7) == 0, "render_rays: sample counts must be 8-byte aligned");
     }
     const bool flagged = any_flag(l, terminate);
+    STNERF_REQUIRE(!occluder_stops || flagged,
+                   "render_rays: occluder_stops needs early ray termination on at least one layer (it lowers the stop depth the row lists test)");
     if (flagged) {
         STNERF_REQUIRE(tau >= 0.f && tau < 1.f, "render_rays: termination with tau = %g outside [0, 1)", (double)tau);
         STNERF_REQUIRE(p->precision != 2, "render_rays: termination is not built for precision 2 (one launch per network)");
@@ -706,10 +734,21 @@ extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const flo
     rc = stnerf_composite_scene(t_c, raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w_c,
                                 nullptr, ray_flags, scene_coarse ? xyz_c : (term ? xyz_f : nullptr), scene_coarse ? scene_out : nullptr, stream);
     if (rc) return rc;
-    if (p->only_coarse) return clear_mask_hints(mask, n * l, as_stream(stream));
+    if (p->only_coarse) {
+        if (occluder) {   // (the coarse stage is the final one: its merged weights lie in xyz_c)
+            rc = stnerf_scene_occluder(t_c, raw_c, mask, xyz_c, n, l, n1, &cp, scene_out, mixed_coarse, occluder, occluded_mixed, occluded_scene,
+                                       occluder_share, nullptr, nullptr, stream);
+            if (rc) return rc;
+        }
+        return clear_mask_hints(mask, n * l, as_stream(stream));
+    }
     if (term) {   // (before the resampler overwrites the weights with the fine points)
         rc = stnerf_ray_stop(t_c, xyz_f, n, l, n1, tau, t_stop, stream);
         if (rc) return rc;
+        if (occluder_stops) {   // an opaque occluder in front of the stop depth is the stop depth
+            rc = stnerf_occluder_stop(occluder, n, t_stop, stream);
+            if (rc) return rc;
+        }
     }
 
     // ---- resample + fine points (:459-475), fine networks, fine composite (:538-606)
@@ -742,5 +781,10 @@ extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const flo
     rc = stnerf_composite_scene(t_f, raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, ray_flags,
                                 scene_out ? xyz_f : nullptr, scene_out, stream);
     if (rc) return rc;
+    if (occluder) {   // (xyz_f holds the fine merged weights)
+        rc = stnerf_scene_occluder(t_f, raw_f, mask, xyz_f, n, l, S, &cp, scene_out, mixed_fine, occluder, occluded_mixed, occluded_scene,
+                                   occluder_share, nullptr, nullptr, stream);
+        if (rc) return rc;
+    }
     return clear_mask_hints(mask, n * l, as_stream(stream));
 }

@@ -229,6 +229,15 @@ _PROTOS = {
                                             C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
                                             C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
                                             C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, C.c_void_p]),
+    "stnerf_scene_occluder": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), c_f32p, c_f32p,
+                                        c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "stnerf_occluder_stop": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_void_p]),
+    "stnerf_render_rays_occluded": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
+                                              C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
+                                              C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
+                                              C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
+                                              C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, c_f32p, C.c_int32,
+                                              c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_copy_layer_raw_listed": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                                C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),

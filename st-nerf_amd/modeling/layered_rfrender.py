@@ -670,7 +670,7 @@ class LayeredRFRender(nn.Module):
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
-                       scene=False, occupancy_ids=None, background_id=None):
+                       scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache or the layer cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
@@ -678,7 +678,9 @@ class LayeredRFRender(nn.Module):
         only by ``render_rays_scene``).  occupancy_ids: the chunk group's frame id per layer, passed only while occupancy grids
         are attached: one grid per shown performer layer is looked up or built and the table travels with the call.
         background_id: the chunk group's background frame id, passed only while the attached grids cull the background: its grid
-        is looked up or built and travels with the call as an argument of its own."""
+        is looked up or built and travels with the call as an argument of its own.  occluder: the piece's rows (n,5) of
+        ``render_rays_occluded`` (with scene): three more tensors come back; occluder_stops: its opaque rows lower the stop depth of
+        the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached)."""
         from stnerf_amd import hip
         n, l = rays.shape[0], self.total_layers
         p = hip.RenderParams()
@@ -773,6 +775,8 @@ class LayeredRFRender(nn.Module):
             out = ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
                                   u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
                                   **(dict(scene=True) if scene else {}), **occ_kw, **lc_kw,
+                                  **(dict(occluder=occluder, occluder_stops=bool(occluder_stops) and "terminate" in occ_kw)
+                                     if occluder is not None else {}),
                                   **(dict(layer_alpha=table) if table is not None else {}))
         except Exception:
             if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
@@ -811,6 +815,42 @@ class LayeredRFRender(nn.Module):
         scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.total_layers)]
         return self.as_reference_tuple(raw[:5]), scene
 
+    def render_rays_occluded(self, rays, occluder, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
+                             ref_chunk: Optional[int] = None, stops=False):
+        """``render_rays_scene`` with a depth-tested occluder in the scene -> (the reference 5-tuple, scene, occluded).
+        ``occluder`` (n,5) fp32 on the device: one row {r, g, b, a, z} per ray -- a CG prop, a title card, a plate with a z-buffer;
+        z is a RAY PARAMETER, in the units of the depth outputs (``ops.ray_parameter`` turns a camera-space z-buffer into it); a row
+        with a <= 0 (or NaN) or a z that is not finite is absent.  It is sliced by launch piece and chunk group exactly as the rays
+        are.  ``occluded`` = dict(mixed=triple, scene=[l triples], share=triple): the mixed image with the occluder in the scene
+        (it hides the samples at or behind z in proportion to a, and is hidden by the samples in front of it), every layer's share
+        of that image, and the occluder's own premultiplied share; mixed = sum of the shares up to fp32 summation order.  Samples
+        are not clipped at z: one that starts in front keeps its whole weight.  include/stnerf.h states the arithmetic.
+        ``stops=True``: an opaque row (a >= 1) also lowers early ray termination's stop depth to z, so the fine samples behind it
+        are not evaluated; it needs an attached termination (``set_termination``; ValueError otherwise).  The occluded outputs keep
+        their bits; the 5-tuple and ``scene`` become those of the terminated scene.  Without it they are the bits of
+        ``render_rays_scene``.  Inference only, one rank, the fused pipeline only."""
+        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("render_rays_occluded in training mode: the occluder composite has no backward; call model.eval() or "
+                               "wrap the render in torch.no_grad()")
+        from stnerf_amd import parallel
+        if parallel.active_group(self) is not None:
+            raise RuntimeError("render_rays_occluded under shard_views with more than one rank: the all-gather's modes "
+                               "(stnerf_amd.parallel) have fixed widths and a \"scene\" gather mode is out of scope; render on one "
+                               "rank (model.shard_views = False)")
+        if stops and getattr(self, "_termination", None) is None:
+            raise ValueError("render_rays_occluded(stops=True) without early ray termination: the occluder lowers the stop depth the "
+                             "terminated layers' row lists test; call set_termination(...) first or pass stops=False")
+        if not torch.is_tensor(occluder) or occluder.dim() != 2 or tuple(occluder.shape) != (rays.shape[0], 5):
+            raise ValueError(f"render_rays_occluded: the occluder must be a ({rays.shape[0]},5) tensor of (r, g, b, a, z) rows, got "
+                             f"{tuple(occluder.shape) if torch.is_tensor(occluder) else type(occluder).__name__}")
+        raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True,
+                                    occluder=occluder, occluder_stops=stops)
+        l = self.total_layers
+        trip = lambda x: (x[..., 0:3], x[..., 3:4], x[..., 4:5])
+        scene = [trip(raw[5][:, i]) for i in range(l)]
+        occluded = dict(mixed=trip(raw[6]), scene=[trip(raw[7][:, i]) for i in range(l)], share=trip(raw[8]))
+        return self.as_reference_tuple(raw[:5]), scene, occluded
+
     def as_reference_tuple(self, raw):
         """(mixed_fine (n,5), mixed_coarse (n,5), layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l)) -> the
         reference's 5-tuple of (color (n,3), depth (n,1), acc (n,1)) triples and bool masks (layered_rfrender.py:725-734)."""
@@ -848,8 +888,10 @@ class LayeredRFRender(nn.Module):
         wrote (what stnerf_amd.parallel packs into its one all-gather)."""
         return self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk)
 
-    def _render_rays_raw(self, rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=False):
-        """``render_rays_raw``; scene: a sixth tensor, the in-scene layer passes (n,l,5) of ``render_rays_scene``."""
+    def _render_rays_raw(self, rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=False, occluder=None,
+                         occluder_stops=False):
+        """``render_rays_raw``; scene: a sixth tensor, the in-scene layer passes (n,l,5) of ``render_rays_scene``; occluder (with
+        scene): the rows (N,5) of ``render_rays_occluded``, three more tensors (occluded mixed, scene, share)."""
         if not rays.is_cuda:
             raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
         rays = rays.contiguous().float()
@@ -874,6 +916,10 @@ class LayeredRFRender(nn.Module):
         if self.bkgd_use_space_time and self.use_space_time:
             from stnerf_amd.modeling import training as _training
             per_sample_bkgd_time = _training.mixed_bkgd_ids(rays)
+        if occluder is not None and per_sample_bkgd_time:
+            raise NotImplementedError("an occluder on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
+                                      "op-by-op path, which has no occluder composite -- a render-time edit, as rotation is; render one "
+                                      "background frame id per call")
         if scene and per_sample_bkgd_time:
             raise RuntimeError("render_rays_scene on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
                                "op-by-op path, which has no in-scene layer passes; render one background frame id per call")
@@ -910,6 +956,8 @@ class LayeredRFRender(nn.Module):
                                  "ignores both opacities, so its stop depth would be wrong for a layer made transparent in the fine "
                                  "composite; leave them at 1 or set_termination(None)")
         self._warn_if_eval_with_grad()
+        if occluder is not None:
+            occluder = occluder.to(rays.device, torch.float32).contiguous()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None
         groups = []  # (start, end, boxes, pivot[, rotations])
@@ -964,9 +1012,11 @@ class LayeredRFRender(nn.Module):
                                                     bkgd_density_threshold, window_at(s), rp, *(((s, e),) if cacheable else ()),
                                                     **(dict(rotations=rot[0]) if rot else {}), **(dict(scene=True) if scene else {}),
                                                     **(dict(occupancy_ids=occ_ids[gi]) if occ_ids is not None else {}),
-                                                    **(dict(background_id=bg_ids[gi]) if bg_ids is not None else {})))
+                                                    **(dict(background_id=bg_ids[gi]) if bg_ids is not None else {}),
+                                                    **(dict(occluder=occluder[s:e], occluder_stops=occluder_stops)
+                                                       if occluder is not None else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
-        raw = tuple(cat(j) for j in range(6 if scene else 5))
+        raw = tuple(cat(j) for j in range((9 if occluder is not None else 6) if scene else 5))
         self.advance_seed()
         return raw
 

@@ -310,7 +310,8 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
-                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows", "copy_layer_raw_listed")
+                   "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows", "copy_layer_raw_listed",
+                   "scene_occluder", "occluder_stop")
 
 
 def profile_begin() -> None:
@@ -892,7 +893,8 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 layer_alpha: Optional[Sequence[float]] = None, occupancy=None, occupancy_counts: Optional[Tensor] = None,
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
                 visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None,
-                layer_caches=None, layer_mismatch: Optional[Tensor] = None):
+                layer_caches=None, layer_mismatch: Optional[Tensor] = None, occluder: Optional[Tensor] = None,
+                occluder_stops: bool = False):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -919,8 +921,19 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     ``layer_caches``: per layer None | (raw_coarse (capacity,n1,4), raw_fine (capacity,n1+n2,4) | None, rays (capacity,) int32, count (1,)
     int32, mode), the layer cache's table (stnerf_render_rays_layers; include/stnerf.h states the rules): hip.LAYER_CACHE_CAPTURE fills
     the entry from the layer's hit rays, hip.LAYER_CACHE_REUSE leaves the layer out of the network stages and copies the slices in.
-    Entry 0 must be None.  ``layer_mismatch``: int64 (1,) | None, += 1 per restore whose frame has another hit count than the entry."""
+    Entry 0 must be None.  ``layer_mismatch``: int64 (1,) | None, += 1 per restore whose frame has another hit count than the entry.
+    ``occluder``: (n,5) rows {r, g, b, a, z} | None, a depth-tested occluder composited into the final stage (stnerf_render_rays_occluded;
+    include/stnerf.h states the rules; z in ray-parameter units, ``ray_parameter``).  It needs ``scene=True`` and appends
+    occluded_mixed (n,5), occluded_scene (n,l,5) and occluder_share (n,5) to the returned tuple.  ``occluder_stops``: an opaque row
+    also lowers the stop depth of early ray termination (needs a ``terminate`` flag); the three occluded outputs keep their bits."""
     n, l = rays.shape[0], params.l
+    if occluder is not None:
+        if not scene:
+            raise ValueError("render_rays: an occluder needs scene=True (the merged weights exist only with the scene passes)")
+        if tuple(occluder.shape) != (n, 5):
+            raise ValueError(f"render_rays: the occluder of {n} rays must be ({n},5) rows of (r, g, b, a, z), got {tuple(occluder.shape)}")
+    elif occluder_stops:
+        raise ValueError("render_rays: occluder_stops without an occluder")
     bp, bstride, lb = _boxes_arg(boxes, n)
     if lb != l:
         raise ValueError(f"boxes carry {lb} layers, params.l = {l}")
@@ -948,8 +961,12 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
     if layer_alpha is not None and len(layer_alpha) != l:
         raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
-    if layer_caches is not None or background_grid is not None:
-        # (the two widest entries share their argument checks and tables; stnerf_render_rays_layers is stnerf_render_rays_background
+    occ_out = None
+    if occluder is not None:
+        occ_out = (torch.empty(n, 5, dtype=torch.float32, device=dev), torch.empty(n, l, 5, dtype=torch.float32, device=dev),
+                   torch.empty(n, 5, dtype=torch.float32, device=dev))
+    if layer_caches is not None or background_grid is not None or occluder is not None:
+        # (the widest entries share their argument checks and tables; stnerf_render_rays_layers is stnerf_render_rays_background
         # plus the layer cache's table)
         sampled = occupancy_samples is not None and any(occupancy_samples)
         if sampled and (occupancy is None or len(occupancy_samples) != l):
@@ -972,7 +989,13 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                   None if terminate is None else _layer_flags(terminate, l, "terminate"),
                   hip.dptr(visibility_counts, torch.int64, "visibility_counts"), bg,
                   hip.dptr(background_counts, torch.int64, "background_counts"))
-        if layer_caches is not None:
+        if occluder is not None:
+            lc = None if layer_caches is None else _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse))
+            hip.check(hip.lib().stnerf_render_rays_occluded(*shared, lc, hip.dptr(layer_mismatch, torch.int64, "layer_mismatch"),
+                                                            hip.dptr(occluder.contiguous(), name="occluder"), int(bool(occluder_stops)),
+                                                            hip.dptr(occ_out[0]), hip.dptr(occ_out[1]), hip.dptr(occ_out[2]), hip.stream_ptr()),
+                      "stnerf_render_rays_occluded")
+        elif layer_caches is not None:
             hip.check(hip.lib().stnerf_render_rays_layers(*shared, _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse)),
                                                           hip.dptr(layer_mismatch, torch.int64, "layer_mismatch"), hip.stream_ptr()),
                       "stnerf_render_rays_layers")
@@ -1028,7 +1051,65 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     else:
         hip.check(hip.lib().stnerf_render_rays_cached(*args, C.byref(bc), hip.stream_ptr()), "stnerf_render_rays_cached")
     out = (mix_c, mix_c, lo_c, lo_c, mask) if params.only_coarse else (mix_f, mix_c, lo_f, lo_c, mask)
-    return out + (scene_out,) if scene else out
+    out = out + (scene_out,) if scene else out
+    return out + occ_out if occ_out is not None else out
+
+
+# ---------------------------------------------------------------------------------------- depth-tested occluders
+def scene_occluder(t: Tensor, raw: Tensor, mask: Optional[Tensor], merged_weights: Tensor, scene: Tensor, mixed: Tensor,
+                   occluder: Tensor, params: Optional["hip.CompositeParams"] = None, rgb_activated: bool = False,
+                   evaluated: Optional[Sequence[int]] = None, want_scene: bool = True, want_share: bool = True,
+                   want_front_behind: bool = False):
+    """A depth-tested occluder on the merged weights of a finished composite (stnerf_scene_occluder; include/stnerf.h states the
+    rules).  t (n,l,S), raw (n,l,S,4), mask (n,l) uint8 | None, merged_weights (n,l,S), scene (n,l,5) and mixed (n,5) are what
+    ``composite_scene`` took and returned (``params``: its stnerf_composite_params, of which rgb_activated and evaluated are
+    read; None: built from the two keywords).  occluder (n,5): rows {r, g, b, a, z}, z in ray-parameter units.  ->
+    (occluded_mixed (n,5), occluded_scene (n,l,5) | None, occluder_share (n,5) | None, front (n,l,5) | None, behind (n,l,5) | None):
+    the mixed image with the occluder in the scene, every layer's share of it, the occluder's own premultiplied share, and the
+    two halves of every layer's scene pass in front of and behind z.  Rows with a <= 0 or a z that is not finite are absent: the
+    plain outputs come back."""
+    if t.dim() != 3 or tuple(raw.shape) != tuple(t.shape) + (4,) or tuple(merged_weights.shape) != tuple(t.shape):
+        raise ValueError(f"scene_occluder: t and merged_weights must be (n,l,S) and raw (n,l,S,4), got {tuple(t.shape)}, "
+                         f"{tuple(merged_weights.shape)}, {tuple(raw.shape)}")
+    n, l, S = t.shape
+    if tuple(scene.shape) != (n, l, 5) or tuple(mixed.shape) != (n, 5) or tuple(occluder.shape) != (n, 5):
+        raise ValueError(f"scene_occluder: scene must be ({n},{l},5), mixed and occluder ({n},5), got {tuple(scene.shape)}, "
+                         f"{tuple(mixed.shape)}, {tuple(occluder.shape)}")
+    p = params if params is not None else composite_params(evaluated=evaluated, rgb_activated=rgb_activated)
+    dev = t.device
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out_mixed = new(n, 5)
+    out_scene = new(n, l, 5) if want_scene else None
+    share = new(n, 5) if want_share else None
+    front = new(n, l, 5) if want_front_behind else None
+    behind = new(n, l, 5) if want_front_behind else None
+    hip.check(hip.lib().stnerf_scene_occluder(hip.dptr(t, name="t"), hip.dptr(raw, name="raw"), hip.dptr(mask, torch.uint8, "mask"),
+                                              hip.dptr(merged_weights, name="merged_weights"), n, l, S, C.byref(p),
+                                              hip.dptr(scene, name="scene"), hip.dptr(mixed, name="mixed"),
+                                              hip.dptr(occluder, name="occluder"), hip.dptr(out_mixed), hip.dptr(out_scene),
+                                              hip.dptr(share), hip.dptr(front), hip.dptr(behind), hip.stream_ptr()),
+              "stnerf_scene_occluder")
+    return out_mixed, out_scene, share, front, behind
+
+
+def occluder_stop(occluder: Tensor, t_stop: Tensor) -> Tensor:
+    """Fold the opaque rows of an occluder (n,5) into early ray termination's stop depths t_stop (n,), IN PLACE
+    (stnerf_occluder_stop): a present row with a >= 1 and z < t_stop[ray] makes z the ray's stop depth.  -> t_stop."""
+    if occluder.dim() != 2 or occluder.shape[1] != 5 or tuple(t_stop.shape) != (occluder.shape[0],):
+        raise ValueError(f"occluder_stop: occluder must be (n,5) and t_stop (n,), got {tuple(occluder.shape)} and {tuple(t_stop.shape)}")
+    hip.check(hip.lib().stnerf_occluder_stop(hip.dptr(occluder, name="occluder"), occluder.shape[0], hip.dptr(t_stop, name="t_stop"),
+                                             hip.stream_ptr()), "stnerf_occluder_stop")
+    return t_stop
+
+
+def ray_parameter(rays: Tensor, pose: Tensor, zcam) -> Tensor:
+    """The ray parameter t at which o + t d has camera-space depth ``zcam``: t = zcam / (d . forward), with forward = pose[:3, 2],
+    the viewing axis ``generate_rays`` rotates the pixel directions by.  This is how a renderer's z-buffer becomes the z of an
+    occluder row.  rays (n, >= 6), pose (4,4) or (3,4) camera-to-world, zcam (n,) or a scalar; plain torch, host or device."""
+    d = rays[:, 3:6]
+    forward = torch.as_tensor(pose, dtype=d.dtype)[:3, 2].to(d.device)
+    z = torch.as_tensor(zcam, dtype=d.dtype).to(d.device)
+    return z / (d * forward).sum(-1)
 
 
 # ---------------------------------------------------------------------------------------- 8(f)4: training GEMMs

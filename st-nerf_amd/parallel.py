@@ -390,13 +390,16 @@ def _view_frame_ids(model, frame_ids):
 
 
 def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, bkgd_density_threshold=0.0,
-                chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda", gather: Optional[str] = None, scene: bool = False):
+                chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda", gather: Optional[str] = None, scene: bool = False,
+                occluder=None, occluder_stops: bool = False):
     """One view from its camera: rays generated on the device (no CPU ray tensor), ``layered_batchify_ray`` semantics, the
     reference's 5-tuple on every rank.  Without a process group: the whole view on this GPU.  With one: interleaved
     stripes of ``stripe_rows`` image rows over the ranks (rank r generates and renders rows r, r + G, ... only), one
     all-gather of ``gather`` (default: ``model.gather``).  The SAME function is bench.py's step at every N and what
     ``render.render_pose`` calls (with gather="fine": the images it returns).  ``scene``: (5-tuple, scene) of
-    ``LayeredRFRender.render_rays_scene`` instead -- on one rank only (the gather modes have fixed widths; it raises otherwise)."""
+    ``LayeredRFRender.render_rays_scene`` instead -- on one rank only (the gather modes have fixed widths; it raises otherwise).
+    ``occluder``: (h w, 5) rows {r, g, b, a, z} of the view's rays, z a ray parameter -> (5-tuple, scene, occluded) of
+    ``LayeredRFRender.render_rays_occluded`` (``occluder_stops``: its ``stops``); one rank only, as ``scene``."""
     from stnerf_amd import ops
     from stnerf_amd.utils.batchify_rays import layered_batchify_ray
     act = active_group(model)
@@ -407,6 +410,11 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
         try:
             model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids), _view_frame_ids(model, frame_ids)
             with torch.no_grad():
+                if occluder is not None:
+                    if n_total < chuncks:
+                        return model.render_rays_occluded(rays, occluder, stops=occluder_stops)
+                    return model.render_rays_occluded(rays, occluder, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks,
+                                                      stops=occluder_stops)
                 if scene:   # (layered_batchify_ray's two cases: a view of less than one chunk renders with the model's defaults)
                     if n_total < chuncks:
                         return model.render_rays_scene(rays)
@@ -415,6 +423,9 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
                                             bkgd_density_threshold=bkgd_density_threshold)
         finally:
             model.view_key, model.view_frame_ids = saved_key, saved_ids
+    if occluder is not None:
+        raise RuntimeError("render_view(occluder=...) on a view sharded over more than one rank: a \"scene\" gather mode is out of scope; "
+                           "render with an occluder on one rank (model.shard_views = False)")
     if scene:
         raise RuntimeError("render_view(scene=True) on a view sharded over more than one rank: a \"scene\" gather mode is out of scope; "
                            "render the in-scene layer passes on one rank (model.shard_views = False)")

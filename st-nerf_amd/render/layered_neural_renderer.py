@@ -33,7 +33,8 @@ class LayeredNeuralRenderer:
 
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
-                 layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False):
+                 layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
+                 occluder=None, occluder_stops=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -78,6 +79,14 @@ class LayeredNeuralRenderer:
         # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
         # hand the frame's dict to on_frame as the keyword `scene`; not in the reference (keyword-only, off by default)
         self.scene_passes = bool(scene_passes)
+        # occluder: callable(frame_index, pose, K) -> (rgba (H,W,4), depth (H,W) in ray-parameter units) | None, an element that is
+        # not a radiance field put into every frame it returns one for (render_pose's `occluder`); the frame's occluded results are
+        # kept in images_occluded and handed to on_frame as the keyword `occluded`.  occluder_stops: its opaque pixels also stop
+        # early ray termination (it needs `terminate`).  Not in the reference (keyword-only, off by default)
+        if occluder is not None and not callable(occluder):
+            raise TypeError(f"occluder is a callable (frame_index, pose, K) -> (rgba, depth) | None, got {type(occluder).__name__}")
+        self.occluder, self.occluder_stops = occluder, bool(occluder_stops)
+        self.images_occluded = []
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -377,20 +386,25 @@ class LayeredNeuralRenderer:
                 self.layer_frame_pairs[i][j] = (layer, round(weight * (new_end - new_start) + new_start))
 
     # ---- rendering -------------------------------------------------------------------------------------------
-    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False):
+    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
-        element, the dict of in-scene layer passes (stnerf_amd.render.render_pose)."""
+        element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
+        also holds the occluded results."""
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
-                            bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}))
+                            bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
+                            **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}))
 
     def _render_frame(self, idx, density_threshold, bkgd_density_threshold, inverse_y_axis):
         """Frame ``idx`` of the path -> (color, depth, color_layer, depth_layer, passes): ``render_pose``, flipped on request;
-        ``passes`` is None unless ``scene_passes`` is on (then ``render_pose``'s dict, flipped alike)."""
+        ``passes`` is None unless ``scene_passes`` is on or the frame has an occluder (then ``render_pose``'s dict, flipped
+        alike)."""
         passes = None
-        if self.scene_passes:
+        occ = self.occluder(idx, self.poses[idx], self.Ks[idx]) if self.occluder is not None else None
+        if self.scene_passes or occ is not None:
             color, depth, color_layer, depth_layer, passes = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                              self.layer_frame_pairs[idx], density_threshold,
-                                                                             bkgd_density_threshold, scene_passes=True)
+                                                                             bkgd_density_threshold, scene_passes=True,
+                                                                             **(dict(occluder=occ) if occ is not None else {}))
         else:
             color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                      self.layer_frame_pairs[idx], density_threshold,
@@ -400,8 +414,22 @@ class LayeredNeuralRenderer:
             color_layer = [torch.flip(i, [0]) for i in color_layer]
             depth_layer = [torch.flip(i, [0]) for i in depth_layer]
             if passes is not None:
-                passes = {k: [torch.flip(i, [0]) for i in v] for k, v in passes.items()}
+                flip = lambda v: torch.flip(v, [0]) if torch.is_tensor(v) else type(v)(flip(i) for i in v)
+                passes = {k: flip(v) for k, v in passes.items()}
         return color, depth, color_layer, depth_layer, passes
+
+    def _frame_keywords(self, passes):
+        """on_frame's keywords beyond the reference's five arguments: ``scene`` with ``scene_passes``, ``occluded`` with an
+        ``occluder`` (the frame's occluded entries of the dict, or None where the callable gave none)."""
+        kw = dict(scene=passes) if self.scene_passes else {}
+        if self.occluder is not None:
+            has = passes is not None and "color_occluded" in passes
+            kw["occluded"] = {k: v for k, v in passes.items() if "occlude" in k} if has else None
+        return kw
+
+    def _keep_occluded(self, passes):
+        if passes is not None and "color_occluded" in passes:
+            self.images_occluded.append(passes["color_occluded"].cpu())
 
     def _keep_scene(self, passes, layer_id):
         self.images_scene[layer_id].append(passes["color_scene"][layer_id].cpu())
@@ -419,6 +447,7 @@ class LayeredNeuralRenderer:
         self.depths_layer = [[] for _ in range(self.total_layers)]
         self.images_scene = [[] for _ in range(self.total_layers)]
         self.alphas_scene = [[] for _ in range(self.total_layers)]
+        self.images_occluded = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -434,15 +463,16 @@ class LayeredNeuralRenderer:
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
                                                                                 inverse_y_axis)
             if on_frame is not None:
-                on_frame(idx, color, depth, color_layer, depth_layer, **(dict(scene=passes) if self.scene_passes else {}))
+                on_frame(idx, color, depth, color_layer, depth_layer, **self._frame_keywords(passes))
             if auto_save:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
+                self._keep_occluded(passes)
                 for layer_id in range(self.total_layers):
                     if self.is_shown_layer(layer_id):
                         self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                         self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
-                        if passes is not None:
+                        if passes is not None and self.scene_passes:
                             self._keep_scene(passes, layer_id)
             self.image_num += 1
         return self.images, self.depths
@@ -460,6 +490,7 @@ class LayeredNeuralRenderer:
         self.depths_layer = [[] for _ in range(self.total_layers)]
         self.images_scene = [[] for _ in range(self.total_layers)]
         self.alphas_scene = [[] for _ in range(self.total_layers)]
+        self.images_occluded = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
@@ -472,16 +503,17 @@ class LayeredNeuralRenderer:
                 index = torch.logical_and(index, color_layer[2] != 0)
                 color_hide[index] = color_layer[2][index]
             if on_frame is not None:
-                on_frame(idx, color, depth, color_layer, depth_layer, **(dict(scene=passes) if self.scene_passes else {}))
+                on_frame(idx, color, depth, color_layer, depth_layer, **self._frame_keywords(passes))
             if auto_save:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
                 if color_hide is not None:
                     self.images_hide.append(color_hide.cpu())
+                self._keep_occluded(passes)
                 for layer_id in range(self.total_layers):
                     self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                     self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())
-                    if passes is not None:
+                    if passes is not None and self.scene_passes:
                         self._keep_scene(passes, layer_id)
             self.image_num += 1
         return self.images, self.depths

@@ -14,7 +14,8 @@ from stnerf_amd.parallel import render_view, total_layers
 
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
-                density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False):
+                density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
+                occluder=None, occluder_stops: bool = False):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -30,23 +31,54 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     ``scene_passes``: a fifth element, the in-scene layer passes (``LayeredRFRender.render_rays_scene``) as a dict of per-layer
     image lists on the device: ``color_scene`` (H,W,3) premultiplied, ``alpha_scene`` (H,W,1), ``depth_scene`` (H,W,1) = the
     weighted depth / far, not clamped.  Their sums over the layers are the mixed colour, alpha and (unclamped) depth.  One rank
-    only."""
+    only.
+
+    ``occluder`` = (rgba (H,W,4), depth (H,W)): a depth-tested occluder in the scene -- a CG prop, a title card, a plate with a
+    z-buffer (``LayeredRFRender.render_rays_occluded``).  rgba: straight (not premultiplied) colour and
+    coverage; ``depth`` is in RAY-PARAMETER units, those of the depth outputs before the division by far
+    (``ops.ray_parameter`` converts a camera-space z-buffer); a pixel with alpha <= 0 or a depth that is not finite has no
+    occluder.  The fifth element is returned as with ``scene_passes`` (the plain passes come with it either way) and gains
+    ``color_occluded`` (H,W,3), ``alpha_occluded``, ``depth_occluded`` (H,W,1; weighted depth / far, not clamped) -- the mixed image
+    with the occluder in it --, the per-layer lists ``color_scene_occluded`` / ``alpha_scene_occluded`` / ``depth_scene_occluded`` --
+    every layer's share of it -- and ``occluder_share`` = (colour (H,W,3), alpha (H,W,1), depth (H,W,1) / far), the occluder's own
+    premultiplied share.  ``occluder_stops``: opaque pixels also stop early ray termination at their depth
+    (``render_rays_occluded(stops=True)``: it needs ``model.set_termination``).  One rank only."""
+    occ_rows = None
+    if occluder is not None:
+        rgba, zbuf = (torch.as_tensor(x, dtype=torch.float32) for x in occluder)
+        if tuple(rgba.shape) != (height, width, 4) or tuple(zbuf.shape) != (height, width):
+            raise ValueError(f"render_pose: the occluder must be (rgba ({height},{width},4), depth ({height},{width})), got "
+                             f"{tuple(rgba.shape)} and {tuple(zbuf.shape)}")
+        occ_rows = torch.cat([rgba.reshape(-1, 4), zbuf.reshape(-1, 1).to(rgba.device)], 1).to(device).contiguous()
     frame_ids = [0.0] * total_layers(model)       # (the layer instances have their own frame ids)
     for layer_id, frame_id in layer_frame_pair:
         frame_ids[layer_id] = float(frame_id)
     out = render_view(model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width,
                       frame_ids, density_threshold, bkgd_density_threshold, device=device, gather="fine",
-                      **(dict(scene=True) if scene_passes else {}))
-    (stage2, _, stage2_layer, _, _), scene = out if scene_passes else (out, None)
+                      **(dict(scene=True) if scene_passes else {}),
+                      **(dict(occluder=occ_rows, occluder_stops=occluder_stops) if occ_rows is not None else {}))
+    occluded = None
+    if occ_rows is not None:
+        (stage2, _, stage2_layer, _, _), scene, occluded = out
+    else:
+        (stage2, _, stage2_layer, _, _), scene = out if scene_passes else (out, None)
     color = stage2[0].reshape(height, width, 3)
     depth = stage2[1].reshape(height, width, 1).clamp_min(0) / far
     color_layer = [t[0].reshape(height, width, 3) for t in stage2_layer]
     depth_layer = [t[1].reshape(height, width, 1) / far for t in stage2_layer]
-    if not scene_passes:
+    if not scene_passes and occluded is None:
         return color, depth, color_layer, depth_layer
     passes = dict(color_scene=[t[0].reshape(height, width, 3) for t in scene],
                   alpha_scene=[t[2].reshape(height, width, 1) for t in scene],
                   depth_scene=[t[1].reshape(height, width, 1) / far for t in scene])
+    if occluded is not None:
+        img = lambda t, c: t.reshape(height, width, c)
+        mixed, share = occluded["mixed"], occluded["share"]
+        passes.update(color_occluded=img(mixed[0], 3), alpha_occluded=img(mixed[2], 1), depth_occluded=img(mixed[1], 1) / far,
+                      color_scene_occluded=[img(t[0], 3) for t in occluded["scene"]],
+                      alpha_scene_occluded=[img(t[2], 1) for t in occluded["scene"]],
+                      depth_scene_occluded=[img(t[1], 1) / far for t in occluded["scene"]],
+                      occluder_share=(img(share[0], 3), img(share[2], 1), img(share[1], 1) / far))
     return color, depth, color_layer, depth_layer, passes
 
 
