@@ -1003,6 +1003,46 @@ int stnerf_render_rays_occluded(const float* rays, int64_t n, const float* boxes
                                 int32_t occluder_stops, float* occluded_mixed, float* occluded_scene, float* occluder_share,
                                 stnerf_stream_t stream);
 
+/* ---- Progressive multi-sample frames (csrc/accumulate.hip): a frame as the per-pixel mean of several
+ * passes -- each with its own sub-pixel offset, shutter time and seed -- in which a pixel stops being sampled once its running
+ * mean is known well enough.  Three helpers around the render entries, every fp32 operation below on its own (no contraction).
+ *
+ * Rays of a pixel list: stnerf_generate_rays with two differences.  The pixel of row i is pixels[i] (device int32), or i with
+ * pixels = NULL (the contiguous pixels 0..n-1), and
+ *     u = (float)(pix % w) + du        v = (float)(pix / w) + dv
+ * Every other operation is that kernel's, in its order: with du = dv = 0 row i is bit-identical to row pixels[i] of
+ * stnerf_generate_rays.  STNERF_EINVAL before any launch: a null pointer, h or w < 1 or h * w > INT32_MAX, n < 0 or n > h * w (a
+ * list names a pixel at most once), a NaN offset, bad frame-id columns.  The kernel leaves the row of a list entry outside
+ * [0, h * w) unwritten. */
+int stnerf_generate_rays_list(const float* Kinv_host, const float* T_host, int h, int w, const int32_t* pixels, int64_t n, float du,
+                              float dv, const float* frame_ids_host, int n_frame_cols, float* rays, int ray_stride,
+                              stnerf_stream_t stream);
+/* The accumulator.  State per pixel q of P = n_pixels: mean[P][C], m2[P][V] (the first V <= C columns carry a second moment),
+ * count[P] int32.  values: n rows of C floats, value_stride floats apart; row i belongs to pixel q = pixels[i], or q = i with
+ * pixels = NULL.  For every column x of the row (Welford's update):
+ *     c = count[q] + 1
+ *     c == 1:  mean = x  (the value itself: one pass reproduces its bits, -0.0 included)          m2 = 0
+ *     else:    d = x - mean      mean = mean + d / (float)c      m2 = m2 + d * (x - mean)          (the NEW mean; columns < V)
+ *     count[q] = c
+ * A list must not name a pixel twice (not checked: the update of a pixel named twice is undefined); an entry outside [0, P) is
+ * skipped.  Two launches: one lane per (row, column) reads count, one lane per row then writes it, so no reader races the
+ * writer.  HBM-bound: 3 C + 2 V floats per row; no LDS.  STNERF_EINVAL before any launch: a null pointer, V or C out of range
+ * (1 <= V <= C <= 4096), value_stride < C, P outside 1..INT32_MAX, n < 0 or n > P. */
+int stnerf_accumulate(const float* values, int64_t n, int C, int64_t value_stride, const int32_t* pixels, int64_t n_pixels, int V,
+                      float* mean, float* m2, int32_t* count, stnerf_stream_t stream);
+/* The pixels still active, in ascending order.  Pixel q is active if and only if
+ *     count[q] < min_spp,  or
+ *     count[q] < max_spp and, for any of the V columns,  m2[q][v] > tol2 * (float)(count[q] * (count[q] - 1))
+ * -- the variance of the mean, m2 / (c (c - 1)), exceeds tol2 = tol^2; the product is the int32 one, converted, times tol2 in
+ * fp32 (a NaN m2 is not active).  pixels_out[0 .. *n_out) = the active q ascending (room for P entries); n_out: one device
+ * int32.  Deterministic: launch 1 takes the popcount of every 256 pixels with a ballot, launch 2 scans the popcounts in ONE
+ * workgroup (1024 per pass), launch 3 writes; no workgroup waits on another.  workspace: device memory of at least
+ * stnerf_accumulate_select_workspace_bytes of P (STNERF_EINVAL for P outside 1..INT32_MAX), overwritten.  STNERF_EINVAL before
+ * any launch: a null pointer, P or V out of range, not 1 <= min_spp <= max_spp <= 32768, tol2 < 0 or NaN, a workspace too small. */
+int64_t stnerf_accumulate_select_workspace_bytes(int64_t n_pixels);
+int stnerf_accumulate_select(const float* m2, const int32_t* count, int64_t n_pixels, int V, int min_spp, int max_spp, float tol2,
+                             int32_t* pixels_out, int32_t* n_out, void* workspace, int64_t workspace_bytes, stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ SOURCES = [
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),
     ("background_rows.hip", ["-ffp-contract=off"]),
+    ("accumulate.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

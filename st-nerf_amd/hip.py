@@ -238,6 +238,12 @@ _PROTOS = {
                                               C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
                                               C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, c_f32p, C.c_int32,
                                               c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "stnerf_generate_rays_list": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
+                                            C.c_float, C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
+    "stnerf_accumulate": (C.c_int, [c_f32p, c_i64, C.c_int, c_i64, C.c_void_p, c_i64, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
+    "stnerf_accumulate_select_workspace_bytes": (c_i64, [c_i64]),
+    "stnerf_accumulate_select": (C.c_int, [c_f32p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, c_i64, C.c_void_p]),
     "stnerf_copy_layer_raw_listed": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                                C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),

@@ -100,10 +100,23 @@ def window_size(total: int, first: int, stripe: int, period: int) -> int:
 
 
 def generate_rays(K: Tensor, T: Tensor, h: int, w: int, frame_ids: Optional[Sequence[float]] = None,
-                  first_ray: int = 0, n: Optional[int] = None, device="cuda", stripe: int = 0, period: int = 0) -> Tensor:
+                  first_ray: int = 0, n: Optional[int] = None, device="cuda", stripe: int = 0, period: int = 0,
+                  pixels: Optional[Tensor] = None, offset: Sequence[float] = (0.0, 0.0)) -> Tensor:
     """Rays of a view, generated on the device: (n, 6 + len(frame_ids)).  (first_ray, stripe, period) = the ray
     window of include/stnerf.h: a contiguous piece of the view (stripe = 0) or interleaved stripes.
-    utils/render_helpers.py:42-128 + data/datasets/ray_dataset.py:276-281."""
+    utils/render_helpers.py:42-128 + data/datasets/ray_dataset.py:276-281.
+
+    ``pixels`` / ``offset`` (stnerf_generate_rays_list; progressive multi-sample frames): row i is pixel ``pixels[i]`` of the
+    view -- a device int32 list naming a pixel at most once; None with ``n``: the contiguous pixels 0..n-1 -- moved by
+    ``offset`` = (du, dv) pixels.  With a zero offset row i is bit-identical to row ``pixels[i]`` of the plain call.  They do
+    not combine with a ray window."""
+    listed = pixels is not None or tuple(float(x) for x in offset) != (0.0, 0.0)
+    if listed and (first_ray or stripe or period):
+        raise ValueError("generate_rays: pixels= / offset= do not combine with a ray window (first_ray, stripe, period)")
+    if pixels is not None:
+        if pixels.dim() != 1 or (n is not None and n != pixels.shape[0]):
+            raise ValueError(f"generate_rays: pixels must be a 1-D int32 list (of n entries), got {tuple(pixels.shape)} and n = {n}")
+        n = pixels.shape[0]
     n = window_size(h * w, first_ray, stripe, period) if n is None else n
     kinv = torch.inverse(K.detach().to("cpu", torch.float32)).contiguous()  # :103 (torch.inverse on the host)
     Tm = torch.as_tensor(T, dtype=torch.float32).detach().cpu().contiguous()
@@ -112,6 +125,11 @@ def generate_rays(K: Tensor, T: Tensor, h: int, w: int, frame_ids: Optional[Sequ
     kin = (C.c_float * 9)(*kinv.reshape(-1).tolist())
     tin = (C.c_float * 16)(*Tm.reshape(-1).tolist())
     fin = (C.c_float * max(len(fids), 1))(*(fids or [0.0]))
+    if listed:
+        hip.check(hip.lib().stnerf_generate_rays_list(kin, tin, h, w, hip.dptr(pixels, torch.int32, "pixels"), n, float(offset[0]),
+                                                      float(offset[1]), fin if fids else None, len(fids), hip.dptr(rays),
+                                                      rays.shape[1], hip.stream_ptr()), "stnerf_generate_rays_list")
+        return rays
     hip.check(hip.lib().stnerf_generate_rays(kin, tin, h, w, first_ray, stripe, period, n, fin if fids else None, len(fids),
                                              hip.dptr(rays), rays.shape[1], hip.stream_ptr()), "stnerf_generate_rays")
     return rays
@@ -1110,6 +1128,70 @@ def ray_parameter(rays: Tensor, pose: Tensor, zcam) -> Tensor:
     forward = torch.as_tensor(pose, dtype=d.dtype)[:3, 2].to(d.device)
     z = torch.as_tensor(zcam, dtype=d.dtype).to(d.device)
     return z / (d * forward).sum(-1)
+
+
+# ---------------------------------------------------------------------------------------- progressive multi-sample frames
+class AccumulateState:
+    """Per-pixel running statistics of a progressive frame (include/stnerf.h: stnerf_accumulate): ``mean`` (P,C), ``m2`` (P,V)
+    -- the second moment of the first V columns -- and ``count`` (P,) int32, all zero at first; plus the buffers
+    ``accumulate_select`` writes (made on first use)."""
+
+    def __init__(self, n_pixels: int, C_: int, V: int = 3, device="cuda"):
+        if n_pixels < 1 or not (1 <= V <= C_):
+            raise ValueError(f"accumulate_state: need n_pixels >= 1 and 1 <= V <= C, got n_pixels={n_pixels}, C={C_}, V={V}")
+        self.mean = torch.zeros(n_pixels, C_, dtype=torch.float32, device=device)
+        self.m2 = torch.zeros(n_pixels, V, dtype=torch.float32, device=device)
+        self.count = torch.zeros(n_pixels, dtype=torch.int32, device=device)
+        self._select = None
+
+    @property
+    def n_pixels(self) -> int:
+        return self.count.shape[0]
+
+
+def accumulate_state(n_pixels: int, C_: int, V: int = 3, device="cuda") -> AccumulateState:
+    """A zeroed ``AccumulateState`` for n_pixels pixels of C floats, the first V with a second moment."""
+    return AccumulateState(n_pixels, C_, V, device)
+
+
+def accumulate(values: Tensor, state: AccumulateState, pixels: Optional[Tensor] = None) -> AccumulateState:
+    """One more sample of some pixels, IN PLACE (stnerf_accumulate: Welford's update, every fp32 operation on its own).
+    values (n,C): a 2-D float32 device view with dense columns (any row stride); row i belongs to pixel ``pixels[i]`` -- a device
+    int32 list that names a pixel at most once -- or to pixel i without a list.  A pixel's first sample becomes its mean as it
+    is.  -> state."""
+    vp, stride = _mat(values, "values")
+    n, C_ = values.shape
+    if C_ != state.mean.shape[1]:
+        raise ValueError(f"accumulate: values are {C_} floats wide, the state {state.mean.shape[1]}")
+    if pixels is not None and tuple(pixels.shape) != (n,):
+        raise ValueError(f"accumulate: pixels must be ({n},), got {tuple(pixels.shape)}")
+    hip.check(hip.lib().stnerf_accumulate(vp, n, C_, stride if n > 1 else C_, hip.dptr(pixels, torch.int32, "pixels"), state.n_pixels,
+                                          state.m2.shape[1], hip.dptr(state.mean, name="mean"), hip.dptr(state.m2, name="m2"),
+                                          hip.dptr(state.count, torch.int32, "count"), hip.stream_ptr()), "stnerf_accumulate")
+    return state
+
+
+def accumulate_select(state: AccumulateState, min_spp: int, max_spp: int, tol: float) -> Tuple[Tensor, int]:
+    """The pixels still to be sampled, ascending (stnerf_accumulate_select): count < min_spp, or count < max_spp and the variance
+    of the mean of any of the V columns above tol^2 -- written m2 > tol2 * (float)(count * (count - 1)) with tol2 = tol * tol in
+    fp32.  -> (pixels (n,) int32 on the device, n): n is a Python int, read back with one small D2H."""
+    P = state.n_pixels
+    if state._select is None:
+        nbytes = hip.lib().stnerf_accumulate_select_workspace_bytes(P)
+        if nbytes < 0:
+            hip.check(int(nbytes), "stnerf_accumulate_select_workspace_bytes")
+        dev = state.count.device
+        state._select = (torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                         torch.zeros(1, dtype=torch.int32, device=dev))
+    work, out, n_out = state._select
+    t = torch.tensor(float(tol), dtype=torch.float32)
+    tol2 = float(t * t)
+    hip.check(hip.lib().stnerf_accumulate_select(hip.dptr(state.m2, name="m2"), hip.dptr(state.count, torch.int32, "count"), P,
+                                                 state.m2.shape[1], int(min_spp), int(max_spp), tol2, hip.dptr(out, torch.int32),
+                                                 hip.dptr(n_out, torch.int32), hip.dptr(work, torch.uint8), work.numel(),
+                                                 hip.stream_ptr()), "stnerf_accumulate_select")
+    n = int(n_out.item())
+    return out[:n].clone(), n      # (the buffer is the next call's too)
 
 
 # ---------------------------------------------------------------------------------------- 8(f)4: training GEMMs

@@ -441,6 +441,78 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     return model.as_reference_tuple(unpack_outputs(whole, total_layers(model), mode))
 
 
+def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, density_threshold=0.0, bkgd_density_threshold=0.0,
+                            chuncks: int = 512 * 7, device="cuda", scene: bool = False, occluder=None):
+    """One view as a progressive multi-sample frame (``stnerf_amd.accumulate.AccumulateSpec``): the
+    per-pixel mean of up to ``spec.max_spp`` passes -> (the reference's 5-tuple built from the means, coarse entries None as in
+    gather mode "fine", stats).  Inference only, one rank.
+
+    Pass p renders with seed (s0 + p) mod 2^64 (s0 = ``model.seed`` on entry), the sub-pixel offset ``spec.offset(p)`` and the
+    frame ids ``spec.frame_ids(p, frame_ids)``; a pixel's own p-th sample is what pass p rendered for it (pixels leave the
+    active set and never return).  Passes p < ``spec.min_spp`` render the whole view; later ones the ascending list of
+    ``ops.accumulate_select``, the loop ending when that list is empty or p == ``spec.max_spp``.  The ray window stays at its
+    default, so the RNG key of a ray of a sparse pass is its position in that list.  Thresholds follow
+    ``layered_batchify_ray``'s rule by the VIEW's size (h w < chuncks: the model's defaults), so every pass of a frame uses
+    the same ones.  Averaged: the mixed 5 floats and the 5 l layer floats of ``pack_outputs(raw, "fine")``; the hit masks
+    returned are pass 0's (the plain frame's).  On return the seed is s0 + passes if ``model.fresh_draws_per_call``, else s0.
+
+    stats: ``spp`` (h w,) int32 and ``variance`` (h w, 3) = m2 / (c (c - 1)) of the mixed colour's mean, 0 where c < 2, on
+    the device; ``passes`` and ``rays_rendered``, Python ints."""
+    from stnerf_amd import ops
+    from stnerf_amd.accumulate import as_spec
+    spec = as_spec(spec)
+    if active_group(model) is not None:
+        raise RuntimeError("render_view_accumulated under shard_views with more than one rank: the per-pixel state lives on one "
+                           "device and multi-rank accumulation is out of scope; render on one rank (model.shard_views = False)")
+    if scene or occluder is not None:
+        raise ValueError("render_view_accumulated with scene passes or an occluder: averaging those passes is out of scope; render "
+                         "them without accumulate=")
+    if getattr(model, "_bkgd_cache", None) is not None or getattr(model, "_layer_cache", None) is not None:
+        raise ValueError("render_view_accumulated with a background cache or a layer cache attached: a cached run pins one jitter "
+                         "pattern for all its frames, which contradicts a seed per pass; detach the cache "
+                         "(set_background_cache(None) / set_layer_cache(None))")
+    if getattr(model, "replay", None) is not None:
+        raise ValueError("render_view_accumulated with replayed draws (model.replay): they pin one jitter pattern, which contradicts "
+                         "a seed per pass; set model.replay = None")
+    l = total_layers(model)
+    frame_ids = [float(f) for f in frame_ids]
+    if spec.has_shutter(len(frame_ids)) and getattr(model, "_occupancy", None) is not None:
+        raise ValueError("render_view_accumulated with a non-zero shutter and occupancy grids attached: the grids are keyed by frame "
+                         "id and every pass plays another one; use shutter = 0 or set_occupancy(None)")
+    n_total = h * w
+    mask64 = 0xFFFFFFFFFFFFFFFF
+    s0 = int(model.seed) & mask64
+    state = ops.accumulate_state(n_total, 5 + 5 * l, 3, device)
+    pixels, n_active, bits = None, n_total, None
+    p = rays_rendered = 0
+    try:
+        with torch.no_grad():
+            while p < spec.max_spp:
+                if p >= spec.min_spp:
+                    pixels, n_active = ops.accumulate_select(state, spec.min_spp, spec.max_spp, spec.tol)
+                    if n_active == 0:
+                        break
+                model.seed = (s0 + p) & mask64
+                rays = ops.generate_rays(K, T, h, w, frame_ids=spec.frame_ids(p, frame_ids), device=device, pixels=pixels,
+                                         offset=spec.offset(p))
+                if n_total < chuncks:     # (layered_batchify_ray's small-call rule, decided by the view)
+                    raw = model.render_rays_raw(rays)
+                else:
+                    raw = model.render_rays_raw(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks)
+                packed = pack_outputs(raw, "fine")
+                if p == 0:
+                    bits = packed[:, -1:].clone()
+                ops.accumulate(packed[:, :-1], state, pixels)
+                rays_rendered += n_active
+                p += 1
+    finally:
+        model.seed = (s0 + p) & mask64 if model.fresh_draws_per_call else s0
+    c = state.count.to(torch.float32).unsqueeze(1)
+    variance = torch.where(c >= 2, state.m2 / (c * (c - 1)).clamp_min(1.0), torch.zeros_like(state.m2))
+    stats = dict(spp=state.count, variance=variance, passes=p, rays_rendered=rays_rendered)
+    return model.as_reference_tuple(unpack_outputs(torch.cat([state.mean, bits], 1), l, "fine")), stats
+
+
 def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: int, density_threshold=0.0,
                       bkgd_density_threshold=0.0, chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda",
                       mode: str = "all") -> torch.Tensor:

@@ -34,7 +34,7 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False):
+                 occluder=None, occluder_stops=False, accumulate=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -87,6 +87,17 @@ class LayeredNeuralRenderer:
             raise TypeError(f"occluder is a callable (frame_index, pose, K) -> (rgba, depth) | None, got {type(occluder).__name__}")
         self.occluder, self.occluder_stops = occluder, bool(occluder_stops)
         self.images_occluded = []
+        # accumulate: an stnerf_amd.accumulate.AccumulateSpec or the dict of its arguments -- every frame of render_path /
+        # render_path_walking is the per-pixel mean of several passes (anti-aliasing, motion blur, adaptive samples per pixel:
+        # render_pose's `accumulate`); the frame's stats go to on_frame as the keyword `accumulated` and its samples-per-pixel map
+        # is kept in spp_maps.  It does not combine with scene_passes or an occluder.  Not in the reference (keyword-only, off by
+        # default)
+        self.accumulate = None
+        if accumulate is not None:
+            from stnerf_amd.accumulate import as_spec
+            self.accumulate = as_spec(accumulate)
+        self.spp_maps = []
+        self._frame_stats = None
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -386,21 +397,33 @@ class LayeredNeuralRenderer:
                 self.layer_frame_pairs[i][j] = (layer, round(weight * (new_end - new_start) + new_start))
 
     # ---- rendering -------------------------------------------------------------------------------------------
-    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None):
+    def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None,
+                    accumulate=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
         element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
-        also holds the occluded results."""
+        also holds the occluded results; with ``accumulate`` = a spec the frame is a progressive multi-sample one and the fifth
+        element is its ``stats``."""
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
                             bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
-                            **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}))
+                            **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}),
+                            **(dict(accumulate=accumulate) if accumulate is not None else {}))
 
     def _render_frame(self, idx, density_threshold, bkgd_density_threshold, inverse_y_axis):
         """Frame ``idx`` of the path -> (color, depth, color_layer, depth_layer, passes): ``render_pose``, flipped on request;
         ``passes`` is None unless ``scene_passes`` is on or the frame has an occluder (then ``render_pose``'s dict, flipped
         alike)."""
         passes = None
+        self._frame_stats = None
         occ = self.occluder(idx, self.poses[idx], self.Ks[idx]) if self.occluder is not None else None
-        if self.scene_passes or occ is not None:
+        if self.accumulate is not None:
+            color, depth, color_layer, depth_layer, stats = self.render_pose(self.poses[idx], self.Ks[idx], self.layer_frame_pairs[idx],
+                                                                            density_threshold, bkgd_density_threshold,
+                                                                            scene_passes=self.scene_passes, occluder=occ,
+                                                                            accumulate=self.accumulate)
+            if inverse_y_axis:
+                stats = dict(stats, spp=torch.flip(stats["spp"], [0]), variance=torch.flip(stats["variance"], [0]))
+            self._frame_stats = stats
+        elif self.scene_passes or occ is not None:
             color, depth, color_layer, depth_layer, passes = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                              self.layer_frame_pairs[idx], density_threshold,
                                                                              bkgd_density_threshold, scene_passes=True,
@@ -422,6 +445,8 @@ class LayeredNeuralRenderer:
         """on_frame's keywords beyond the reference's five arguments: ``scene`` with ``scene_passes``, ``occluded`` with an
         ``occluder`` (the frame's occluded entries of the dict, or None where the callable gave none)."""
         kw = dict(scene=passes) if self.scene_passes else {}
+        if self.accumulate is not None:
+            kw["accumulated"] = self._frame_stats
         if self.occluder is not None:
             has = passes is not None and "color_occluded" in passes
             kw["occluded"] = {k: v for k, v in passes.items() if "occlude" in k} if has else None
@@ -430,6 +455,10 @@ class LayeredNeuralRenderer:
     def _keep_occluded(self, passes):
         if passes is not None and "color_occluded" in passes:
             self.images_occluded.append(passes["color_occluded"].cpu())
+
+    def _keep_spp(self):
+        if self._frame_stats is not None:
+            self.spp_maps.append(self._frame_stats["spp"].cpu())
 
     def _keep_scene(self, passes, layer_id):
         self.images_scene[layer_id].append(passes["color_scene"][layer_id].cpu())
@@ -441,13 +470,16 @@ class LayeredNeuralRenderer:
         ``auto_save`` the frames are kept in ``self.images`` / ``self.depths`` (CPU tensors, as the reference
         keeps them for ``save_video``); ``on_frame(idx, color, depth, color_layer, depth_layer)`` is called with
         the device tensors (write files there); with ``scene_passes`` it also gets ``scene=`` the frame's dict of in-scene layer
-        passes, which are kept in ``self.images_scene`` / ``self.alphas_scene`` next to ``images_layer``."""
+        passes, which are kept in ``self.images_scene`` / ``self.alphas_scene`` next to ``images_layer``; with ``accumulate`` every
+        frame is a progressive multi-sample one, ``on_frame`` gets ``accumulated=`` its stats (spp and variance maps flipped with
+        the images) and the samples-per-pixel maps are kept in ``self.spp_maps``."""
         self.images, self.depths = [], []
         self.images_layer = [[] for _ in range(self.total_layers)]
         self.depths_layer = [[] for _ in range(self.total_layers)]
         self.images_scene = [[] for _ in range(self.total_layers)]
         self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.images_occluded = []
+        self.spp_maps = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -468,6 +500,7 @@ class LayeredNeuralRenderer:
                 self.images.append(color.cpu())
                 self.depths.append(depth.cpu())
                 self._keep_occluded(passes)
+                self._keep_spp()
                 for layer_id in range(self.total_layers):
                     if self.is_shown_layer(layer_id):
                         self.images_layer[layer_id].append(color_layer[layer_id].cpu())
@@ -491,6 +524,7 @@ class LayeredNeuralRenderer:
         self.images_scene = [[] for _ in range(self.total_layers)]
         self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.images_occluded = []
+        self.spp_maps = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,
@@ -510,6 +544,7 @@ class LayeredNeuralRenderer:
                 if color_hide is not None:
                     self.images_hide.append(color_hide.cpu())
                 self._keep_occluded(passes)
+                self._keep_spp()
                 for layer_id in range(self.total_layers):
                     self.images_layer[layer_id].append(color_layer[layer_id].cpu())
                     self.depths_layer[layer_id].append(depth_layer[layer_id].cpu())

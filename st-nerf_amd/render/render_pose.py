@@ -15,7 +15,7 @@ from stnerf_amd.parallel import render_view, total_layers
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
                 density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
-                occluder=None, occluder_stops: bool = False):
+                occluder=None, occluder_stops: bool = False, accumulate=None):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -42,7 +42,25 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     with the occluder in it --, the per-layer lists ``color_scene_occluded`` / ``alpha_scene_occluded`` / ``depth_scene_occluded`` --
     every layer's share of it -- and ``occluder_share`` = (colour (H,W,3), alpha (H,W,1), depth (H,W,1) / far), the occluder's own
     premultiplied share.  ``occluder_stops``: opaque pixels also stop early ray termination at their depth
-    (``render_rays_occluded(stops=True)``: it needs ``model.set_termination``).  One rank only."""
+    (``render_rays_occluded(stops=True)``: it needs ``model.set_termination``).  One rank only.
+
+    ``accumulate`` = an ``stnerf_amd.accumulate.AccumulateSpec`` (or the dict of its arguments): the frame is the per-pixel mean
+    of several passes -- anti-aliasing, motion blur, adaptive samples per pixel (``parallel.render_view_accumulated``; DESIGN.md
+    section 7).  The depth post-processing above is applied to the means, and a fifth element ``stats`` is returned: ``spp``
+    (H,W) int32, ``variance`` (H,W,3) of the mixed colour's mean, ``passes``, ``rays_rendered``.  It does not combine with
+    ``scene_passes`` or an occluder (ValueError).  One rank only."""
+    if accumulate is not None:
+        from stnerf_amd.parallel import render_view_accumulated
+        frame_ids = [0.0] * total_layers(model)
+        for layer_id, frame_id in layer_frame_pair:
+            frame_ids[layer_id] = float(frame_id)
+        (stage2, _, stage2_layer, _, _), stats = render_view_accumulated(
+            model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width, frame_ids,
+            accumulate, density_threshold, bkgd_density_threshold, device=device, scene=bool(scene_passes), occluder=occluder)
+        stats = dict(stats, spp=stats["spp"].reshape(height, width), variance=stats["variance"].reshape(height, width, 3))
+        return (stage2[0].reshape(height, width, 3), stage2[1].reshape(height, width, 1).clamp_min(0) / far,
+                [t[0].reshape(height, width, 3) for t in stage2_layer], [t[1].reshape(height, width, 1) / far for t in stage2_layer],
+                stats)
     occ_rows = None
     if occluder is not None:
         rgba, zbuf = (torch.as_tensor(x, dtype=torch.float32) for x in occluder)

@@ -32,4 +32,7 @@ def __getattr__(name):
     if name == "Termination":
         from stnerf_amd.termination import Termination
         return Termination
+    if name == "AccumulateSpec":
+        from stnerf_amd.accumulate import AccumulateSpec
+        return AccumulateSpec
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
