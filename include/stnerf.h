@@ -1003,6 +1003,47 @@ int stnerf_render_rays_occluded(const float* rays, int64_t n, const float* boxes
                                 int32_t occluder_stops, float* occluded_mixed, float* occluded_scene, float* occluder_share,
                                 stnerf_stream_t stream);
 
+/* ---- the render call's optional arguments, stated once ----------------------------------------------------------------------------
+ * Every optional argument of stnerf_render_rays_occluded, in that entry's order and with that entry's meaning; the paragraph that
+ * introduces an argument above is the field's contract.  A caller sets struct_size = sizeof(stnerf_render_options) and zeroes the
+ * rest: an all-zero record with the size set is "no feature" and makes exactly the launches of stnerf_render_rays, in a workspace of
+ * stnerf_render_workspace_bytes.  struct_size is what lets a later feature add a FIELD instead of an entry: a size the library does
+ * not know is refused with STNERF_EINVAL and a message that names the field, before anything else is looked at.
+ * The named entries above are the fixed-argument forms of this call: each fills a record from its arguments and forwards it. */
+typedef struct stnerf_render_options {
+    int32_t struct_size;                    /* sizeof(stnerf_render_options), set by the caller                                   */
+    const stnerf_bkgd_cache* cache;         /* host, or NULL: the background cache (stnerf_render_rays_cached)                      */
+    const stnerf_layer_rotation* rot;       /* host, params->l entries, or NULL: per-layer rotations (stnerf_render_rays_rot)       */
+    float* scene_out;                       /* device [n][l][5] or NULL: the final stage's scene passes (stnerf_render_rays_scene)  */
+    const float* layer_alpha;               /* host, params->l factors finite and >= 0, or NULL (stnerf_render_rays_opacity)        */
+    const stnerf_occupancy* occ;            /* host, params->l entries, or NULL: the ray cull's grids (stnerf_render_rays_occupancy)*/
+    int32_t* counts;                        /* device int32 [l][2] += (pairs tested, culled), 8-byte aligned, or NULL               */
+    const int32_t* samples;                 /* host, params->l flags, or NULL: the sample cull (stnerf_render_rays_samples)         */
+    int64_t* sample_counts;                 /* device int64 [l][2] += (samples tested, skipped), or NULL                            */
+    float tau;                              /* in [0, 1); read only with a terminate flag set (stnerf_render_rays_terminated)       */
+    const int32_t* terminate;               /* host, params->l flags, or NULL: early ray termination of the fine stage              */
+    int64_t* visibility_counts;             /* device int64 [l][2] += (fine samples tested, not listed), or NULL                    */
+    const stnerf_occupancy* bkgd_grid;      /* host, one entry, or NULL (or bits == NULL): stnerf_render_rays_background            */
+    int64_t* bkgd_counts;                   /* device int64 [2] += (samples tested, not listed), or NULL                            */
+    const stnerf_layer_cache* layers;       /* host, params->l entries, entry 0 OFF, or NULL (stnerf_render_rays_layers)            */
+    int64_t* mismatch;                      /* device int64, the restore copies' counter, or NULL                                   */
+    const float* occluder;                  /* device [n][5] or NULL; needs scene_out and occluded_mixed (above)                    */
+    int32_t occluder_stops;                 /* != 0: an opaque row lowers the stop depth; needs a terminate flag                    */
+    float* occluded_mixed;                  /* device [n][5]; required with an occluder, refused without                            */
+    float* occluded_scene;                  /* device [n][l][5] or NULL                                                             */
+    float* occluder_share;                  /* device [n][5] or NULL                                                                */
+} stnerf_render_options;
+/* The workspace of stnerf_render_rays_opts for n rays.  Reads struct_size, samples, terminate and bkgd_grid (a grid with bits grows
+ * the workspace as `background` != 0 does above); opts_host NULL = an all-zero record = stnerf_render_workspace_bytes. */
+int64_t stnerf_render_workspace_bytes_opts(int64_t n, int l, int n1, int n2, int only_coarse, const stnerf_render_options* opts_host);
+/* stnerf_render_rays with a record of options; opts_host NULL = no feature.  The one render call with a body: new callers should
+ * use this pair. */
+int stnerf_render_rays_opts(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
+                            const stnerf_nets* nets_host, const stnerf_render_params* params_host, const float* jitter,
+                            const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
+                            float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
+                            const stnerf_render_options* opts_host, stnerf_stream_t stream);
+
 /* ---- Progressive multi-sample frames (csrc/accumulate.hip): a frame as the per-pixel mean of several
  * passes -- each with its own sub-pixel offset, shutter time and seed -- in which a pixel stops being sampled once its running
  * mean is known well enough.  Three helpers around the render entries, every fp32 operation below on its own (no contraction).

@@ -1,8 +1,13 @@
-// stnerf_render_rays[_cached | _rot | _scene | _opacity | _occupancy | _samples | _terminated | _background | _layers]: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
+// stnerf_render_rays_opts: the whole chunk pipeline of LayeredRFRender.forward (modeling/layered_rfrender.py:141-734)
 // behind ONE C-ABI call -- coarse sampler -> mask compaction -> [MotionNet] -> SpaceNets -> density edits +
 // per-layer composite + depth merge + merged composite -> inverse-CDF resample -> [MotionNet] -> fine SpaceNets ->
 // composite.  Host-side sequencing only: every stage is one of the kernels behind the op-level entry points,
 // enqueued on the caller's stream into a caller-provided workspace (no allocation, no synchronisation).
+// Every optional argument travels in one stnerf_render_options record (include/stnerf.h).  The call is three things, in this
+// order in the file: check_call (the argument checks and the bit sets they derive), Workspace (the carve, beside the Plan and
+// RowPlan the size query shares with it) and launch_sequence.  The named entries stnerf_render_rays[_cached | _rot | _scene |
+// _opacity | _occupancy | _samples | _terminated | _background | _layers | _occluded] and the four named size queries are the
+// fixed-argument forms: each fills a record and forwards it (the end of the file).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +43,7 @@ struct Plan {
     int64_t tail() const { return pad(raw_c) + pad(w_c) > pad(slots) ? pad(raw_c) + pad(w_c) : pad(slots); }
     int64_t coarse_block() const { return pad(t_c) + pad(xyz_c) + tail(); }
     int64_t shared() const { return coarse_block() > pad(raw_f) ? coarse_block() : pad(raw_f); }
+    int64_t bytes() const { return (shared() + t_f + xyz_f + raybias) * 4 + (list + count) * 4 + flags + 16 * 256; }
 };
 Plan make_plan(int64_t n, int l, int n1, int n2, int only_coarse) {
     Plan p;
@@ -58,63 +64,97 @@ Plan make_plan(int64_t n, int l, int n1, int n2, int only_coarse) {
     return p;
 }
 
-}  // namespace
-
-extern "C" int64_t stnerf_render_workspace_bytes(int64_t n, int l, int n1, int n2, int only_coarse) {
-    if (n < 0 || l < 1 || l > STNERF_MAX_LAYERS || n1 < 3 || n2 < 0) {
-        set_error("render_workspace_bytes: bad shape");
-        return STNERF_EINVAL;
-    }
-    const Plan p = make_plan(n, l, n1, n2, only_coarse);
-    const int64_t floats = p.shared() + p.t_f + p.xyz_f + p.raybias;
-    return floats * 4 + (p.list + p.count) * 4 + p.flags + 16 * 256;
-}
-
-// The sample cull's share of the workspace: one row list of n x (samples of the larger stage) words per
-// sample-culled layer and the lists' counts.  Nothing without such a layer.
-static int sampled_layers(int l, const int32_t* samples) {
+int sampled_layers(int l, const int32_t* samples) {
     int c = 0;
     for (int i = 0; samples && i < l; ++i) c += samples[i] ? 1 : 0;
     return c;
 }
-static int64_t row_capacity(int64_t n, int n1, int n2, int only_coarse) { return n * (only_coarse ? n1 : n1 + n2); }
-
-extern "C" int64_t stnerf_render_workspace_bytes_samples(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples) {
-    const int64_t base = stnerf_render_workspace_bytes(n, l, n1, n2, only_coarse);
-    if (base < 0) return base;
-    const int c = sampled_layers(l, samples);
-    if (c == 0) return base;
-    return base + c * ((row_capacity(n, n1, n2, only_coarse) * 4 + 255) & ~int64_t(255)) + STNERF_MAX_LAYERS * 4 + 2 * 256;
-}
-
-// Early ray termination's share (nothing under only_coarse or without a flag): the stop depths, n floats that
-// live from the coarse composite to the fine stage, and a fine row list per flagged layer that the sample cull has not given one.
-static bool any_flag(int l, const int32_t* flags) {
+bool any_flag(int l, const int32_t* flags) {
     for (int i = 0; flags && i < l; ++i)
         if (flags[i]) return true;
     return false;
 }
 
-extern "C" int64_t stnerf_render_workspace_bytes_terminated(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
-                                                            const int32_t* terminate) {
-    const int64_t base = stnerf_render_workspace_bytes_samples(n, l, n1, n2, only_coarse, samples);
-    if (base < 0 || only_coarse || !any_flag(l, terminate)) return base;
-    int extra = 0;
-    for (int i = 0; i < l; ++i) extra += terminate[i] && !(samples && samples[i]) ? 1 : 0;
-    const int64_t counts = sampled_layers(l, samples) ? 0 : STNERF_MAX_LAYERS * 4 + 2 * 256;   // (the sample cull's size has them)
-    return base + extra * ((row_capacity(n, n1, n2, 0) * 4 + 255) & ~int64_t(255)) + counts + ((n * 4 + 255) & ~int64_t(255)) + 256;
+// The three culls' share of the workspace, shared by the size query and the carve as Plan is.  A layer walks
+// ONE row list of n x (samples of the larger stage) words when it is sample-culled, when its fine stage is terminated (a flag and a
+// fine stage: nothing under only_coarse) or when it is the background under its grid -- which shares the list termination gives
+// layer 0.  The lists bring their counts; termination brings the stop depths, n floats that live from the coarse composite to the
+// fine stage.  Nothing without a cull.
+struct RowPlan {
+    uint32_t listed = 0;    // bit i: layer i has a row list
+    int n_lists = 0;        // (a sample flag on layer 0 beside a grid is counted twice, as the named queries always did: the call refuses it)
+    bool stops = false;     // termination: t_stop
+    int64_t row_cap = 0;    // words per list
+    int64_t bytes(int64_t n) const {
+        if (n_lists == 0) return 0;
+        return n_lists * ((row_cap * 4 + 255) & ~int64_t(255)) + STNERF_MAX_LAYERS * 4 + 2 * 256 + (stops ? ((n * 4 + 255) & ~int64_t(255)) + 256 : 0);
+    }
+};
+RowPlan make_row_plan(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples, const int32_t* terminate, bool bg) {
+    RowPlan r;
+    r.row_cap = n * (only_coarse ? n1 : n1 + n2);
+    r.stops = !only_coarse && any_flag(l, terminate);
+    for (int i = 0; i < l; ++i) {
+        const bool own = (samples && samples[i]) || (r.stops && terminate[i]);
+        if (own || (bg && i == 0)) r.listed |= 1u << i;
+        r.n_lists += own ? 1 : 0;
+    }
+    if (bg && !(r.stops && terminate[0])) r.n_lists += 1;
+    return r;
 }
 
-// The background grid's share: layer 0 takes ONE row list of row_capacity words, the one termination gives it
-// when both are on, and the lists' counts when no other cull has brought them.  Nothing without a grid.
-extern "C" int64_t stnerf_render_workspace_bytes_background(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
-                                                            const int32_t* terminate, int background) {
-    const int64_t base = stnerf_render_workspace_bytes_terminated(n, l, n1, n2, only_coarse, samples, terminate);
-    if (base < 0 || !background) return base;
-    const bool lists = !only_coarse && any_flag(l, terminate);
-    const int64_t list0 = lists && terminate[0] ? 0 : (row_capacity(n, n1, n2, only_coarse) * 4 + 255) & ~int64_t(255);
-    const int64_t counts = sampled_layers(l, samples) || lists ? 0 : STNERF_MAX_LAYERS * 4 + 2 * 256;
-    return base + list0 + counts;
+// the workspace of one call, carved as Plan and RowPlan size it
+struct Workspace {
+    float *t_c, *xyz_c, *raw_c, *w_c, *raw_f, *t_f, *xyz_f, *ray_bias, *t_stop = nullptr;
+    int32_t *slots, *ray_list, *ray_count, *row_count = nullptr;
+    int32_t* row_list[STNERF_MAX_LAYERS] = {nullptr};
+    uint8_t* ray_flags;
+    Workspace(void* base, int64_t bytes, const Plan& pl, const RowPlan& rows, int64_t n, int l) {
+        Carve ws{static_cast<char*>(base), 0, bytes};
+        float* shared = ws.take<float>(pl.shared());
+        Carve cb{reinterpret_cast<char*>(shared), 0, pl.shared() * 4};   // the coarse block inside the shared region
+        t_c = cb.take<float>(pl.t_c);
+        xyz_c = cb.take<float>(pl.xyz_c);
+        raw_c = cb.take<float>(pl.raw_c);
+        w_c = cb.take<float>(pl.w_c);
+        slots = reinterpret_cast<int32_t*>(raw_c);   // over raw_c / w_c: written after the resampler, read before the fine stage
+        raw_f = shared;            // over the coarse block: first written by the fine stage, after the resampler read t_c / w_c
+        t_f = ws.take<float>(pl.t_f);
+        xyz_f = ws.take<float>(pl.xyz_f);
+        ray_list = ws.take<int32_t>(pl.list);
+        ray_count = ws.take<int32_t>(pl.count);
+        ray_flags = ws.take<uint8_t>(pl.flags);
+        ray_bias = ws.take<float>(pl.raybias);
+        if (rows.listed) {
+            for (int i = 0; i < l; ++i)
+                if (rows.listed >> i & 1) row_list[i] = ws.take<int32_t>(rows.row_cap);
+            row_count = ws.take<int32_t>(STNERF_MAX_LAYERS);
+            if (rows.stops) t_stop = ws.take<float>(n);
+        }
+    }
+};
+
+const stnerf_render_options kNoOptions = {(int32_t)sizeof(stnerf_render_options)};
+
+int check_options_size(const stnerf_render_options* opts, const char* what) {
+    STNERF_REQUIRE(!opts || opts->struct_size == (int32_t)sizeof(stnerf_render_options),
+                   "%s: stnerf_render_options.struct_size = %d is not a size this library knows (%d): set it to sizeof", what,
+                   opts ? (int)opts->struct_size : 0, (int)sizeof(stnerf_render_options));
+    return STNERF_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t stnerf_render_workspace_bytes_opts(int64_t n, int l, int n1, int n2, int only_coarse, const stnerf_render_options* opts) {
+    const int src = check_options_size(opts, "render_workspace_bytes");
+    if (src) return src;
+    if (n < 0 || l < 1 || l > STNERF_MAX_LAYERS || n1 < 3 || n2 < 0) {
+        set_error("render_workspace_bytes: bad shape");
+        return STNERF_EINVAL;
+    }
+    const stnerf_render_options& o = opts ? *opts : kNoOptions;
+    return make_plan(n, l, n1, n2, only_coarse).bytes() +
+           make_row_plan(n, l, n1, n2, only_coarse, o.samples, o.terminate, o.bkgd_grid && o.bkgd_grid->bits).bytes(n);
 }
 
 // The mask the caller gets back is the reference's ray_mask (0 / 1): the sampler's "missed" hint (bit 1) served the compositor and
@@ -256,180 +296,32 @@ extern "C" int stnerf_copy_layer_raw(float* raw, int64_t n, int l, int layer, in
     return STNERF_OK;
 }
 
-extern "C" int stnerf_render_rays(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                  const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                  const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                  float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                  stnerf_stream_t stream) {
-    return stnerf_render_rays_rot(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                  mixed_coarse, layer_fine, layer_coarse, mask, nullptr, nullptr, stream);
-}
+// ---- the render call.  The 15 arguments every render entry starts with, and the same handed on:
+#define RENDER_PARAMS                                                                                                                   \
+    const float *rays, int64_t n, const float *boxes, int64_t box_ray_stride, const stnerf_nets *nets, const stnerf_render_params *p,    \
+        const float *jitter, const float *u, void *workspace, int64_t workspace_bytes, float *mixed_fine, float *mixed_coarse,          \
+        float *layer_fine, float *layer_coarse, uint8_t *mask
+#define RENDER_ARGS rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse, layer_fine, layer_coarse, mask
 
-extern "C" int stnerf_render_rays_cached(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                         const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                         const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                         float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                         const stnerf_bkgd_cache* cache, stnerf_stream_t stream) {
-    return stnerf_render_rays_rot(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                  mixed_coarse, layer_fine, layer_coarse, mask, cache, nullptr, stream);
-}
+namespace {
 
-extern "C" int stnerf_render_rays_rot(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                      const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                      const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                      float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                      const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, stnerf_stream_t stream) {
-    return stnerf_render_rays_scene(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                    mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, nullptr, stream);
-}
+// what the checks derive from a call's arguments
+struct Call {
+    int n_sampled;            // sample-culled layers
+    bool flagged;             // a terminate flag is set
+    bool bg;                  // the background's grid has bits
+    int cache_mode;           // the background cache's
+    uint32_t lcap, lreuse;    // bit i: performer i's slices go to / come from its layer cache entry (a hidden layer's entry is ignored)
+    uint32_t term;            // bit i: layer i's fine stage is terminated
+    RowPlan rows;
+};
 
-// rot: per-layer rotations (include/stnerf.h) or null.  The table reaches the sampler, the resampler and the ray-bias launches
-// of both passes; everything else -- the stage kernels, the compositor, the workspace -- is what it was.
-// scene_out: the in-scene layer passes of the final stage, or null.  Their merged weights (n l ns floats) are written over that
-// stage's points (xyz_c with only_coarse, else xyz_f: three times as large), which nobody reads once the stage's networks
-// have run: the background cache's copies move `raw` only, the MotionNet reuse reads xyz_c BEFORE the fine stage and the fine
-// compositor reads t_f / raw_f, neither of which overlaps xyz_f.
-extern "C" int stnerf_render_rays_scene(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                        const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                        const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                        float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                        const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                        stnerf_stream_t stream) {
-    return stnerf_render_rays_opacity(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                      mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, scene_out, nullptr, stream);
-}
-
-// layer_alpha: one density factor per layer for the FINE composite (host array of p->l floats), or null = the reference's
-// `if i == 2: density *= alpha` (p->alpha on layer 2).  A table replaces p->alpha; only_coarse ignores both.  Entries of
-// `nets` may alias (include/stnerf.h): nothing below compares or groups network pointers.
-extern "C" int stnerf_render_rays_opacity(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                          const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                          const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                          float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                          const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                          const float* layer_alpha, stnerf_stream_t stream) {
-    return stnerf_render_rays_occupancy(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine,
-                                        mixed_coarse, layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, nullptr, nullptr,
-                                        stream);
-}
-
-// occ: per-layer occupancy grids (include/stnerf.h: stnerf_occupancy; host array of p->l entries) or null.  The cull runs between the
-// coarse sampler and the ray compaction and writes nothing but bit 0 of the mask: a culled (ray, performer) pair never reaches a
-// network stage, and the compositor and the resampler treat it as they treat a ray that grazes the box.  counts: [l][2] int32 on the
-// device (pairs tested, pairs culled; accumulated) or null.  Without a table the call launches what it always launched.
-extern "C" int stnerf_render_rays_occupancy(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                            const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                            const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                            float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                            const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                            const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                            stnerf_stream_t stream) {
-    return stnerf_render_rays_samples(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
-                                      layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, nullptr, nullptr, stream);
-}
-
-// samples: per-layer flags (host array of p->l entries) or null.  A flagged layer's stages walk a row list (stnerf_occupancy_rows ->
-// stnerf_mlp_stage_rows): the rows kernel runs right before each stage, on the points that stage is given, and stores the zeros of
-// the samples it does not list.  In the fine pass that is after the resampler and after every MotionNet-reuse launch of the other
-// layers: the zeros go into raw_f, which lies over t_c / xyz_c, and those launches read them.  A flagged layer is never in `reuse`:
-// its MotionNet runs fused, on listed rows only.  Without a flag the call launches what stnerf_render_rays_occupancy always launched.
-extern "C" int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                          const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                          const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                          float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                          const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                          const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                          const int32_t* samples, int64_t* sample_counts, stnerf_stream_t stream) {
-    return stnerf_render_rays_terminated(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
-                                         layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
-                                         0.f, nullptr, nullptr, stream);
-}
-
-// terminate: per-layer flags (host array of p->l entries) or null; tau: the transmittance under which a ray counts as opaque
-// (include/stnerf.h: early ray termination).  With a flag set -- and a fine stage to apply it to -- the coarse composite also writes
-// its merged weights, into xyz_f's region, which nobody writes before the resampler; stnerf_ray_stop turns them into t_stop (a region
-// of its own: it must survive to the fine stage), and a flagged layer's fine row list comes from stnerf_visibility_rows, at the place
-// and time stnerf_occupancy_rows makes a sample-culled layer's: after the resampler and the MotionNet-reuse launches of the other
-// layers.  The coarse stage is untouched.  Layer 0 is listed with ray_list == NULL (every ray): the row-list stage kernels address
-// points, outputs and the ray-bias row by the word's ray, and the ray-bias launch of a layer without a list fills every ray's row.
-// Without a flag, or with only_coarse, the call launches what stnerf_render_rays_samples always launched.
-extern "C" int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                             const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                             const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                             const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                             const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                             const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
-                                             int64_t* visibility_counts, stnerf_stream_t stream) {
-    return stnerf_render_rays_background(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
-                                         layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
-                                         tau, terminate, visibility_counts, nullptr, nullptr, stream);
-}
-
-// bkgd_grid: the background's own occupancy grid (include/stnerf.h: "Background sample cull"; host, one entry) or null.  With bits,
-// layer 0 is sample-culled in every stage it is evaluated in: stnerf_background_rows runs over EVERY ray (no mask bit is consulted:
-// evaluated[0] == 2) on the points the stage is given -- xyz_c after the compaction, xyz_f after the resampler and every
-// MotionNet-reuse launch, since the zeros land in raw_f over t_c / xyz_c -- and the stage walks layer 0's row list.  Where layer 0's
-// fine stage is terminated too the same launch takes t_f / t_stop, in place of stnerf_visibility_rows, and the two share the list.
-// A background cache REUSE frame makes no rows launch (layer 0 is in no stage); a CAPTURE frame is culled by the grid and still not
-// terminated, so the cached raw is a function of view and grid only.  The grid is an argument of its own: occ[0] / samples[0] stay
-// refused.  Without bits the call launches what stnerf_render_rays_terminated always launched, in its workspace.
-extern "C" int stnerf_render_rays_background(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                             const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                             const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                             const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                             const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                             const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
-                                             int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
-                                             stnerf_stream_t stream) {
-    return stnerf_render_rays_layers(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
-                                     layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
-                                     tau, terminate, visibility_counts, bkgd_grid, bkgd_counts, nullptr, nullptr, stream);
-}
-
-// layers: the layer cache's table (include/stnerf.h: stnerf_layer_cache; host, p->l entries) or null.  A performer's raw outputs are a
-// function of the view and of its own inputs, as the background's are, so a layer in REUSE is in no network stage: no stage item, no
-// stand-alone MotionNet or MotionNet-reuse fill (its `reuse` bit is cleared), no ray-bias and no rows launch -- its slices are copied
-// in by stnerf_copy_layer_raw_listed where the background's are, for the rays the slice was captured on.  A layer in CAPTURE renders
-// as usual and is copied out after each stage; the coarse copy keeps the frame's ray list, the fine one walks the kept list.  Neither
-// is terminated (its `term` bit is cleared: the raw outputs would depend on the other layers).  Everything else runs for every layer
-// in every mode.  Without a table, or with every mode OFF, the call launches what stnerf_render_rays_background always launched.
-extern "C" int stnerf_render_rays_layers(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                         const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                         const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                         float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                         const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                         const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                         const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
-                                         int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
-                                         const stnerf_layer_cache* layers, int64_t* mismatch, stnerf_stream_t stream) {
-    return stnerf_render_rays_occluded(rays, n, boxes, box_ray_stride, nets, p, jitter, u, workspace, workspace_bytes, mixed_fine, mixed_coarse,
-                                       layer_fine, layer_coarse, mask, cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts,
-                                       tau, terminate, visibility_counts, bkgd_grid, bkgd_counts, layers, mismatch, nullptr, 0, nullptr, nullptr,
-                                       nullptr, stream);
-}
-
-// occluder: one row {r, g, b, a, z} per ray (include/stnerf.h: depth-tested occluder compositing; device) or null.  With one, the
-// final stage's scene pass is followed by stnerf_scene_occluder on the same buffers -- t, raw and the merged weights, which lie over
-// that stage's points and stay live until the call returns.  occluder_stops: an opaque row's depth is folded into t_stop right after
-// stnerf_ray_stop, so the flagged layers' row lists leave out the fine samples behind it; the occluded outputs keep their bits.
-// Without an occluder the call launches what stnerf_render_rays_layers always launched; the workspace is the same either way.
-extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const float* boxes, int64_t box_ray_stride,
-                                           const stnerf_nets* nets, const stnerf_render_params* p, const float* jitter,
-                                           const float* u, void* workspace, int64_t workspace_bytes, float* mixed_fine,
-                                           float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
-                                           const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out,
-                                           const float* layer_alpha, const stnerf_occupancy* occ, int32_t* counts,
-                                           const int32_t* samples, int64_t* sample_counts, float tau, const int32_t* terminate,
-                                           int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
-                                           const stnerf_layer_cache* layers, int64_t* mismatch, const float* occluder,
-                                           int32_t occluder_stops, float* occluded_mixed, float* occluded_scene, float* occluder_share,
-                                           stnerf_stream_t stream) {
+// Every argument check of the render call, on the host and before anything is launched.
+int check_call(RENDER_PARAMS, const stnerf_render_options& o, Call* call) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
-    STNERF_REQUIRE(!occluder || (scene_out && occluded_mixed),
+    STNERF_REQUIRE(!o.occluder || (o.scene_out && o.occluded_mixed),
                    "render_rays: an occluder needs scene_out and occluded_mixed (the merged weights exist only with the scene passes)");
-    STNERF_REQUIRE(occluder || (!occluder_stops && !occluded_mixed && !occluded_scene && !occluder_share),
+    STNERF_REQUIRE(o.occluder || (!o.occluder_stops && !o.occluded_mixed && !o.occluded_scene && !o.occluder_share),
                    "render_rays: occluder_stops / occluded outputs without an occluder");
     STNERF_REQUIRE(mixed_coarse && layer_coarse, "render_rays: coarse outputs are required");
     STNERF_REQUIRE(p->only_coarse || (mixed_fine && layer_fine), "render_rays: fine outputs are required");
@@ -447,63 +339,62 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
         STNERF_REQUIRE(nets->space[i] && (p->only_coarse || nets->space_fine[i]), "render_rays: SpaceNet of layer %d missing", i);
         STNERF_REQUIRE(!p->use_deform_time || nets->motion[i], "render_rays: MotionNet of layer %d missing", i);
     }
-    if (layer_alpha)
+    if (o.layer_alpha)
         for (int i = 0; i < l; ++i)
-            STNERF_REQUIRE(isfinite(layer_alpha[i]) && layer_alpha[i] >= 0.f,
-                           "render_rays: layer_alpha[%d] = %g is not a finite, non-negative factor", i, (double)layer_alpha[i]);
-    const int n_sampled = sampled_layers(l, samples);
-    if (n_sampled) {
+            STNERF_REQUIRE(isfinite(o.layer_alpha[i]) && o.layer_alpha[i] >= 0.f,
+                           "render_rays: layer_alpha[%d] = %g is not a finite, non-negative factor", i, (double)o.layer_alpha[i]);
+    call->n_sampled = sampled_layers(l, o.samples);
+    if (call->n_sampled) {
         STNERF_REQUIRE(p->precision != 2, "render_rays: the sample cull is not built for precision 2 (one launch per network)");
-        STNERF_REQUIRE(!samples[0], "render_rays: layer 0 cannot be sample-culled (the background is never listed)");
+        STNERF_REQUIRE(!o.samples[0], "render_rays: layer 0 cannot be sample-culled (the background is never listed)");
         for (int i = 1; i < l; ++i)
-            STNERF_REQUIRE(!samples[i] || (occ && occ[i].bits), "render_rays: layer %d is to be sample-culled but has no occupancy grid", i);
+            STNERF_REQUIRE(!o.samples[i] || (o.occ && o.occ[i].bits), "render_rays: layer %d is to be sample-culled but has no occupancy grid", i);
         STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the sample cull packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
-        STNERF_REQUIRE(((uintptr_t)sample_counts & 7) == 0, "render_rays: sample counts must be 8-byte aligned");
+        STNERF_REQUIRE(((uintptr_t)o.sample_counts & 7) == 0, "render_rays: sample counts must be 8-byte aligned");
     }
-    const bool flagged = any_flag(l, terminate);
-    STNERF_REQUIRE(!occluder_stops || flagged,
+    const bool flagged = call->flagged = any_flag(l, o.terminate);
+    STNERF_REQUIRE(!o.occluder_stops || flagged,
                    "render_rays: occluder_stops needs early ray termination on at least one layer (it lowers the stop depth the row lists test)");
     if (flagged) {
-        STNERF_REQUIRE(tau >= 0.f && tau < 1.f, "render_rays: termination with tau = %g outside [0, 1)", (double)tau);
+        STNERF_REQUIRE(o.tau >= 0.f && o.tau < 1.f, "render_rays: termination with tau = %g outside [0, 1)", (double)o.tau);
         STNERF_REQUIRE(p->precision != 2, "render_rays: termination is not built for precision 2 (one launch per network)");
         STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: termination packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
-        STNERF_REQUIRE(((uintptr_t)visibility_counts & 7) == 0, "render_rays: visibility counts must be 8-byte aligned");
+        STNERF_REQUIRE(((uintptr_t)o.visibility_counts & 7) == 0, "render_rays: visibility counts must be 8-byte aligned");
         if (!p->only_coarse) {   // (only_coarse ignores both opacities and terminates nothing)
-            STNERF_REQUIRE(layer_alpha || l <= 2 || p->alpha == 1.f,
+            STNERF_REQUIRE(o.layer_alpha || l <= 2 || p->alpha == 1.f,
                            "render_rays: termination with alpha = %g: the coarse composite ignores it, so its stop depth would be wrong", (double)p->alpha);
-            for (int i = 0; layer_alpha && i < l; ++i)
-                STNERF_REQUIRE(layer_alpha[i] == 1.f, "render_rays: termination with layer_alpha[%d] = %g: the coarse composite ignores it, so its stop depth would be wrong",
-                               i, (double)layer_alpha[i]);
+            for (int i = 0; o.layer_alpha && i < l; ++i)
+                STNERF_REQUIRE(o.layer_alpha[i] == 1.f, "render_rays: termination with layer_alpha[%d] = %g: the coarse composite ignores it, so its stop depth would be wrong",
+                               i, (double)o.layer_alpha[i]);
         }
     }
-    const bool bg = bkgd_grid && bkgd_grid->bits;
+    const bool bg = call->bg = o.bkgd_grid && o.bkgd_grid->bits;
     if (bg) {
-        const int brc = check_background_grid(bkgd_grid, "render_rays");
+        const int brc = check_background_grid(o.bkgd_grid, "render_rays");
         if (brc) return brc;
         STNERF_REQUIRE(p->precision != 2, "render_rays: the background grid is not built for precision 2 (one launch per network)");
         STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the background grid packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
-        STNERF_REQUIRE(((uintptr_t)bkgd_counts & 7) == 0, "render_rays: background counts must be 8-byte aligned");
+        STNERF_REQUIRE(((uintptr_t)o.bkgd_counts & 7) == 0, "render_rays: background counts must be 8-byte aligned");
     }
-    const int64_t need = stnerf_render_workspace_bytes_background(n, l, n1, n2, p->only_coarse, samples, terminate, bg ? 1 : 0);
+    call->rows = make_row_plan(n, l, n1, n2, p->only_coarse, o.samples, o.terminate, bg);
+    const int64_t need = make_plan(n, l, n1, n2, p->only_coarse).bytes() + call->rows.bytes(n);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
-    const int cache_mode = cache ? cache->mode : STNERF_BKGD_CACHE_OFF;
+    const int cache_mode = call->cache_mode = o.cache ? o.cache->mode : STNERF_BKGD_CACHE_OFF;
     STNERF_REQUIRE(cache_mode == STNERF_BKGD_CACHE_OFF || cache_mode == STNERF_BKGD_CACHE_CAPTURE || cache_mode == STNERF_BKGD_CACHE_REUSE,
                    "render_rays: unknown background cache mode %d", cache_mode);
     if (cache_mode != STNERF_BKGD_CACHE_OFF) {
-        STNERF_REQUIRE(cache->raw_coarse, "render_rays: background cache without raw_coarse");
-        STNERF_REQUIRE(p->only_coarse || cache->raw_fine, "render_rays: background cache without raw_fine (required unless only_coarse)");
-        STNERF_REQUIRE(((uintptr_t)cache->raw_coarse & 15) == 0 && (p->only_coarse || ((uintptr_t)cache->raw_fine & 15) == 0),
+        STNERF_REQUIRE(o.cache->raw_coarse, "render_rays: background cache without raw_coarse");
+        STNERF_REQUIRE(p->only_coarse || o.cache->raw_fine, "render_rays: background cache without raw_fine (required unless only_coarse)");
+        STNERF_REQUIRE(((uintptr_t)o.cache->raw_coarse & 15) == 0 && (p->only_coarse || ((uintptr_t)o.cache->raw_fine & 15) == 0),
                        "render_rays: background cache buffers must be 16-byte aligned");
     }
-    const bool cached = cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
-    // the layer cache: bit i of lcap / lreuse = performer i's slices go to / come from its entry (a hidden layer's entry is ignored)
     uint32_t lcap = 0, lreuse = 0;
-    if (layers) {
-        STNERF_REQUIRE(layers[0].mode == STNERF_LAYER_CACHE_OFF, "render_rays: layer cache entry 0 must be OFF (the background has its own cache)");
-        STNERF_REQUIRE(((uintptr_t)mismatch & 7) == 0, "render_rays: the layer cache's mismatch counter must be 8-byte aligned");
+    if (o.layers) {
+        STNERF_REQUIRE(o.layers[0].mode == STNERF_LAYER_CACHE_OFF, "render_rays: layer cache entry 0 must be OFF (the background has its own cache)");
+        STNERF_REQUIRE(((uintptr_t)o.mismatch & 7) == 0, "render_rays: the layer cache's mismatch counter must be 8-byte aligned");
         for (int i = 1; i < l; ++i) {
-            const stnerf_layer_cache& e = layers[i];
+            const stnerf_layer_cache& e = o.layers[i];
             STNERF_REQUIRE(e.mode == STNERF_LAYER_CACHE_OFF || e.mode == STNERF_LAYER_CACHE_CAPTURE || e.mode == STNERF_LAYER_CACHE_REUSE,
                            "render_rays: unknown layer cache mode %d of layer %d", e.mode, i);
             if (e.mode == STNERF_LAYER_CACHE_OFF || !p->shown[i]) continue;
@@ -515,64 +406,83 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
             (e.mode == STNERF_LAYER_CACHE_REUSE ? lreuse : lcap) |= 1u << i;
         }
     }
-    // bit i: layer i's fine stage is terminated.  Not the background's while its raw outputs go to or come from the cache (they would
-    // depend on the performers), not a performer's while they go to or come from the layer cache, not a hidden performer's (it is
-    // in no stage).
-    uint32_t term = 0;
+    call->lcap = lcap;
+    call->lreuse = lreuse;
+    // Not the background's while its raw outputs go to or come from the cache (they would depend on the performers), not a
+    // performer's while they go to or come from the layer cache, not a hidden performer's (it is in no stage).
+    call->term = 0;
     if (flagged && !p->only_coarse)
         for (int i = 0; i < l; ++i)
-            if (terminate[i] && (i == 0 ? cache_mode == STNERF_BKGD_CACHE_OFF : p->shown[i] != 0 && !((lcap | lreuse) >> i & 1))) term |= 1u << i;
-    if (occ) {
-        const int orc = check_occupancy_table(occ, l, "render_rays");
+            if (o.terminate[i] && (i == 0 ? cache_mode == STNERF_BKGD_CACHE_OFF : p->shown[i] != 0 && !((lcap | lreuse) >> i & 1))) call->term |= 1u << i;
+    if (o.occ) {
+        const int orc = check_occupancy_table(o.occ, l, "render_rays");
         if (orc) return orc;
-        STNERF_REQUIRE(((uintptr_t)counts & 7) == 0, "render_rays: occupancy counts must be 8-byte aligned");
+        STNERF_REQUIRE(((uintptr_t)o.counts & 7) == 0, "render_rays: occupancy counts must be 8-byte aligned");
     }
-    if (n == 0) return STNERF_OK;
+    return STNERF_OK;
+}
 
-    const Plan pl = make_plan(n, l, n1, n2, p->only_coarse);
-    Carve ws{static_cast<char*>(workspace), 0, workspace_bytes};
-    float* shared = ws.take<float>(pl.shared());
-    Carve cb{reinterpret_cast<char*>(shared), 0, pl.shared() * 4};   // the coarse block inside the shared region
-    float* t_c = cb.take<float>(pl.t_c);
-    float* xyz_c = cb.take<float>(pl.xyz_c);
-    float* raw_c = cb.take<float>(pl.raw_c);
-    float* w_c = cb.take<float>(pl.w_c);
-    int32_t* slots = reinterpret_cast<int32_t*>(raw_c);   // over raw_c / w_c: written after the resampler, read before the fine stage
-    float* raw_f = shared;            // over the coarse block: first written by the fine stage, after the resampler read t_c / w_c
-    float* t_f = ws.take<float>(pl.t_f);
-    float* xyz_f = ws.take<float>(pl.xyz_f);
-    int32_t* ray_list = ws.take<int32_t>(pl.list);
-    int32_t* ray_count = ws.take<int32_t>(pl.count);
-    uint8_t* ray_flags = ws.take<uint8_t>(pl.flags);
-    float* ray_bias = ws.take<float>(pl.raybias);
-    const int64_t row_cap = row_capacity(n, n1, n2, p->only_coarse);
-    int32_t* row_list[STNERF_MAX_LAYERS] = {nullptr};
-    int32_t* row_count = nullptr;
-    float* t_stop = nullptr;
-    const bool lists = flagged && !p->only_coarse;   // (the carve follows the flags, as the size query does)
-    if (n_sampled || lists || bg) {
-        for (int i = 0; i < l; ++i)
-            if ((samples && samples[i]) || (lists && terminate[i]) || (bg && i == 0)) row_list[i] = ws.take<int32_t>(row_cap);
-        row_count = ws.take<int32_t>(STNERF_MAX_LAYERS);
-        if (lists) t_stop = ws.take<float>(n);
-    }
+// The launches of one checked call with n > 0 rays, in stream order.  How each option acts:
+// rot: the table reaches the sampler, the resampler and the ray-bias launches of both passes; everything else -- the stage
+// kernels, the compositor, the workspace -- is what it is without one.
+// scene_out: the in-scene layer passes of the final stage.  Their merged weights (n l ns floats) are written over that stage's
+// points (xyz_c with only_coarse, else xyz_f: three times as large), which nobody reads once the stage's networks have run: the
+// background cache's copies move `raw` only, the MotionNet reuse reads xyz_c BEFORE the fine stage and the fine compositor reads
+// t_f / raw_f, neither of which overlaps xyz_f.
+// layer_alpha: one density factor per layer for the FINE composite, or null = the reference's `if i == 2: density *= alpha`
+// (p->alpha on layer 2).  A table replaces p->alpha; only_coarse ignores both.  Entries of `nets` may alias (include/stnerf.h):
+// nothing below compares or groups network pointers.
+// occ: the cull runs between the coarse sampler and the ray compaction and writes nothing but bit 0 of the mask: a culled (ray,
+// performer) pair never reaches a network stage, and the compositor and the resampler treat it as they treat a ray that grazes
+// the box.
+// samples: a flagged layer's stages walk a row list (stnerf_occupancy_rows -> stnerf_mlp_stage_rows): the rows kernel runs right
+// before each stage, on the points that stage is given, and stores the zeros of the samples it does not list.  In the fine pass
+// that is after the resampler and after every MotionNet-reuse launch of the other layers: the zeros go into raw_f, which lies
+// over t_c / xyz_c, and those launches read them.  A flagged layer is never in `reuse`: its MotionNet runs fused, on listed rows.
+// terminate: with a flag set -- and a fine stage to apply it to -- the coarse composite also writes its merged weights, into
+// xyz_f's region, which nobody writes before the resampler; stnerf_ray_stop turns them into t_stop (a region of its own: it must
+// survive to the fine stage), and a flagged layer's fine row list comes from stnerf_visibility_rows, at the place and time
+// stnerf_occupancy_rows makes a sample-culled layer's.  The coarse stage is untouched.  Layer 0 is listed with ray_list == NULL
+// (every ray): the row-list stage kernels address points, outputs and the ray-bias row by the word's ray, and the ray-bias launch
+// of a layer without a list fills every ray's row.
+// bkgd_grid: with bits, layer 0 is sample-culled in every stage it is evaluated in: stnerf_background_rows runs over EVERY ray (no
+// mask bit is consulted: evaluated[0] == 2) on the points the stage is given -- xyz_c after the compaction, xyz_f after the
+// resampler and every MotionNet-reuse launch, since the zeros land in raw_f over t_c / xyz_c -- and the stage walks layer 0's row
+// list.  Where layer 0's fine stage is terminated too the same launch takes t_f / t_stop, in place of stnerf_visibility_rows, and
+// the two share the list.  A background cache REUSE frame makes no rows launch (layer 0 is in no stage); a CAPTURE frame is culled
+// by the grid and still not terminated, so the cached raw is a function of view and grid only.
+// layers: a performer's raw outputs are a function of the view and of its own inputs, as the background's are, so a layer in REUSE
+// is in no network stage: no stage item, no stand-alone MotionNet or MotionNet-reuse fill (its `reuse` bit is cleared), no ray-bias
+// and no rows launch -- its slices are copied in by stnerf_copy_layer_raw_listed where the background's are, for the rays the slice
+// was captured on.  A layer in CAPTURE renders as usual and is copied out after each stage; the coarse copy keeps the frame's ray
+// list, the fine one walks the kept list.  Neither is terminated (its `term` bit is cleared: the raw outputs would depend on the
+// other layers).  Everything else runs for every layer in every mode.
+// occluder: the final stage's scene pass is followed by stnerf_scene_occluder on the same buffers -- t, raw and the merged weights,
+// which lie over that stage's points and stay live until the call returns.  occluder_stops: an opaque row's depth is folded into
+// t_stop right after stnerf_ray_stop, so the flagged layers' row lists leave out the fine samples behind it.
+// An option that is absent (a null table, no flag set, no bits, every mode OFF) adds no launch and changes none.
+int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const Call& c, const Plan& pl, const Workspace& w, stnerf_stream_t stream) {
+    const int l = p->l, n1 = p->n1, n2 = p->n2, S = n1 + n2, rs = p->ray_stride;
+    const bool cached = c.cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
+    const uint32_t lcap = c.lcap, lreuse = c.lreuse, term = c.term;
+    const int64_t row_cap = c.rows.row_cap;
     hipStream_t st = as_stream(stream);
     int rc;
 
     // ---- coarse samples + hit masks (+ un-edit), then the per-layer lists of hit rays
     rc = stnerf_sample_coarse_rot(rays, n, rs, boxes, box_ray_stride, l, n1, jitter, p->seed, p->ray_index_base,
                                   p->ray_index_stripe, p->ray_index_period,
-                                  p->has_edits ? p->edits_coarse : nullptr, p->pivot, rot, t_c, xyz_c, mask, stream);
+                                  p->has_edits ? p->edits_coarse : nullptr, p->pivot, o.rot, w.t_c, w.xyz_c, mask, stream);
     if (rc) return rc;
-    if (occ) {   // (before the compaction: a culled pair is on no list)
-        rc = stnerf_occupancy_cull(xyz_c, n, l, n1, occ, mask, counts, stream);
+    if (o.occ) {   // (before the compaction: a culled pair is on no list)
+        rc = stnerf_occupancy_cull(w.xyz_c, n, l, n1, o.occ, mask, o.counts, stream);
         if (rc) return rc;
     }
-    if (hipMemsetAsync(ray_count, 0, sizeof(int32_t) * pl.count, st) != hipSuccess) {
+    if (hipMemsetAsync(w.ray_count, 0, sizeof(int32_t) * pl.count, st) != hipSuccess) {
         set_error("render_rays: hipMemsetAsync failed");
         return STNERF_ELAUNCH;
     }
-    rc = stnerf_compact_rays(mask, n, l, ray_list, ray_count, stream);
+    rc = stnerf_compact_rays(mask, n, l, w.ray_list, w.ray_count, stream);
     if (rc) return rc;
 
     // ---- the performer layers whose MotionNet runs on its own (MotionNet reuse, above): split-bf16 stages, both passes, the same
@@ -582,10 +492,10 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
         const char* sw = getenv("STNERF_MOTION_REUSE");
         if (!(sw && sw[0] == '0'))
             for (int i = 1; i < l; ++i)
-                if (p->shown[i] && !row_list[i] && !(lreuse >> i & 1) && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
+                if (p->shown[i] && !w.row_list[i] && !(lreuse >> i & 1) && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
                     reuse |= 1u << i;
     }
-    uint32_t* motion_queue = reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
+    uint32_t* motion_queue = reinterpret_cast<uint32_t*>(w.ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
 
     // ---- one network stage: deform + evaluate every shown layer on its hit rays (:340-418 / :495-576)
     auto stage = [&](float* xyz, float* raw, int ns, bool fine, uint32_t moved) -> int {
@@ -607,34 +517,34 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
                     stnerf_stage_layer& e = sl[ns_l++];
                     e.space = i == 0 ? (fine ? nets->bkgd_fine : nets->bkgd) : (fine ? nets->space_fine[i] : nets->space[i]);
                     e.motion = deform && !(moved >> i & 1) ? nets->motion[i] : nullptr;   // (moved: points deformed already)
-                    e.ray_list = i == 0 ? nullptr : ray_list + (int64_t)i * n;
-                    e.ray_count = i == 0 ? nullptr : ray_count + i;
+                    e.ray_list = i == 0 ? nullptr : w.ray_list + (int64_t)i * n;
+                    e.ray_count = i == 0 ? nullptr : w.ray_count + i;
                     e.xyz = xyz + (int64_t)i * ns * 3;
                     e.raw = raw + (int64_t)i * ns * 4;
                     e.times = (timed || deform) ? rays + (p->retiming ? 6 + i : 6) : nullptr;
                     e.use_time = timed ? 1 : 0;
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
-                    e.rotation = rot ? rot + i : nullptr;
-                    const bool culled = samples && samples[i];
-                    if (i == 0 && bg) {   // the background's grid: every ray; with termination the same launch drops the hidden samples
+                    e.rotation = o.rot ? o.rot + i : nullptr;
+                    const bool culled = o.samples && o.samples[i];
+                    if (i == 0 && c.bg) {   // the background's grid: every ray; with termination the same launch drops the hidden samples
                         const bool stop = fine && (term & 1);
-                        const int r1 = stnerf_background_rows(n, e.xyz, xs, ns, bkgd_grid, stop ? t_f : nullptr, (int64_t)l * ns, stop ? t_stop : nullptr,
-                                                              e.raw, ws_, row_list[0], row_cap, row_count, bkgd_counts, stream);
+                        const int r1 = stnerf_background_rows(n, e.xyz, xs, ns, o.bkgd_grid, stop ? w.t_f : nullptr, (int64_t)l * ns, stop ? w.t_stop : nullptr,
+                                                              e.raw, ws_, w.row_list[0], row_cap, w.row_count, o.bkgd_counts, stream);
                         if (r1) return r1;
                     } else if (fine && (term >> i & 1)) {   // termination: the rows that are not hidden (and, sample-culled too, in an occupied cell)
-                        const int r1 = stnerf_visibility_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, t_f + (int64_t)i * ns, (int64_t)l * ns, t_stop, ns,
-                                                              culled ? occ + i : nullptr, e.raw, ws_, row_list[i], row_cap, row_count + i,
-                                                              visibility_counts, stream);
+                        const int r1 = stnerf_visibility_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, w.t_f + (int64_t)i * ns, (int64_t)l * ns, w.t_stop, ns,
+                                                              culled ? o.occ + i : nullptr, e.raw, ws_, w.row_list[i], row_cap, w.row_count + i,
+                                                              o.visibility_counts, stream);
                         if (r1) return r1;
                     } else if (culled) {   // the sample cull: this layer's rows of this stage, and the zeros of the others
-                        const int r1 = stnerf_occupancy_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, ns, occ + i, e.raw, ws_, row_list[i], row_cap,
-                                                             row_count + i, sample_counts, stream);
+                        const int r1 = stnerf_occupancy_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, ns, o.occ + i, e.raw, ws_, w.row_list[i], row_cap,
+                                                             w.row_count + i, o.sample_counts, stream);
                         if (r1) return r1;
                     } else {
                         continue;
                     }
-                    sr[ns_l - 1].row_list = row_list[i];
-                    sr[ns_l - 1].row_count = row_count + i;
+                    sr[ns_l - 1].row_list = w.row_list[i];
+                    sr[ns_l - 1].row_count = w.row_count + i;
                     any_list = true;
                 }
             }
@@ -642,7 +552,7 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
             set_launch_tag(fine ? 1 : 0);
             const int r2 = stnerf_mlp_stage_rows(sl, any_list ? sr : nullptr, ns_l, n, ns, rays + 3, rs, rs, xs, ws_,
                                                  (p->deep_rgb ? STNERF_STAGE_DEEP_RGB : 0) | STNERF_STAGE_SIGMOID_RGB | (p->precision == 3 ? STNERF_STAGE_BF16X3 : 0),
-                                                 reinterpret_cast<uint32_t*>(ray_count + STNERF_MAX_LAYERS + (fine ? 1 : 0)), ray_bias, stream);
+                                                 reinterpret_cast<uint32_t*>(w.ray_count + STNERF_MAX_LAYERS + (fine ? 1 : 0)), w.ray_bias, stream);
             set_launch_tag(-1);
             return r2;
         }
@@ -655,8 +565,8 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
             // performers: time_deform_nets[i-1] on the hit rays, fractional frame ids lerp the encodings (:340-356);
             // background: bkgd_time_deform_net on every ray, MotionNet(input_time=False) (:358-367)
             const float* times = rays + (p->retiming ? 6 + i : 6);
-            const int32_t* lst = i == 0 ? nullptr : ray_list + (int64_t)i * n;
-            const int32_t* cnt = i == 0 ? nullptr : ray_count + i;
+            const int32_t* lst = i == 0 ? nullptr : w.ray_list + (int64_t)i * n;
+            const int32_t* cnt = i == 0 ? nullptr : w.ray_count + i;
             const int flags = STNERF_MOTION_ADD_TO_XYZ | (i == 0 ? STNERF_MOTION_PLAIN_TIME : 0);
             const int r2 = stnerf_motionnet_fwd(nets->motion[i], n, ns, lst, cnt, xyz + (int64_t)i * ns * 3, xs, times,
                                                       rs, nullptr, 0, flags, stream);
@@ -670,10 +580,10 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
             const int kind = timed ? (p->deep_rgb ? STNERF_NET_SPACE_TIME_DEEP : STNERF_NET_SPACE_TIME)
                                    : (p->deep_rgb ? STNERF_NET_SPACE_DEEP : STNERF_NET_SPACE);
             const float* times = timed ? rays + (p->retiming ? 6 + i : 6) : nullptr;
-            const int32_t* lst = i == 0 ? nullptr : ray_list + (int64_t)i * n;
-            const int32_t* cnt = i == 0 ? nullptr : ray_count + i;
+            const int32_t* lst = i == 0 ? nullptr : w.ray_list + (int64_t)i * n;
+            const int32_t* cnt = i == 0 ? nullptr : w.ray_count + i;
             const int r2 = stnerf_spacenet_fwd_rot(kind, net, n, ns, lst, cnt, xyz + (int64_t)i * ns * 3, xs, rays + 3, rs, times, rs,
-                                                   raw + (int64_t)i * ns * 4, ws_, ray_bias + (int64_t)i * n * 128, rot ? rot + i : nullptr,
+                                                   raw + (int64_t)i * ns * 4, ws_, w.ray_bias + (int64_t)i * n * 128, o.rot ? o.rot + i : nullptr,
                                                    stream);
             if (r2) return r2;
         }
@@ -682,7 +592,7 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
     };
     for (int i = 1; i < l; ++i) {
         if (!(reuse >> i & 1)) continue;
-        rc = motion_rows(nets, p, rays, n, i, n1, n1, xyz_c, ray_list, ray_count, nullptr, 0, motion_queue + 2 * i, st);
+        rc = motion_rows(nets, p, rays, n, i, n1, n1, w.xyz_c, w.ray_list, w.ray_count, nullptr, 0, motion_queue + 2 * i, st);
         if (rc) return rc;
     }
     // The stage followed by the caches' copies: layer 0's slice (the background cache) and the cached performers' (the layer cache,
@@ -690,29 +600,29 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
     auto stage_and_cache = [&](float* xyz, float* raw, int ns, bool fine, float* kept) -> int {
         const int r2 = stage(xyz, raw, ns, fine, reuse);
         if (r2) return r2;
-        if (cache_mode != STNERF_BKGD_CACHE_OFF) {
+        if (c.cache_mode != STNERF_BKGD_CACHE_OFF) {
             set_launch_tag(0);
-            const int r3 = stnerf_copy_layer_raw(raw, n, l, 0, ns, kept, cache_mode == STNERF_BKGD_CACHE_CAPTURE, stream);
+            const int r3 = stnerf_copy_layer_raw(raw, n, l, 0, ns, kept, c.cache_mode == STNERF_BKGD_CACHE_CAPTURE, stream);
             set_launch_tag(-1);
             if (r3) return r3;
         }
         for (int i = 1; i < l; ++i) {
             if (!((lcap | lreuse) >> i & 1)) continue;
-            const stnerf_layer_cache& e = layers[i];
+            const stnerf_layer_cache& e = o.layers[i];
             const bool capture = lcap >> i & 1;
             // (the fine capture walks the list the coarse one kept: list and count alias the entry's and stay as they are)
-            const int32_t* lst = capture && fine ? e.rays : ray_list + (int64_t)i * n;
-            const int32_t* cnt = capture && fine ? e.count : ray_count + i;
+            const int32_t* lst = capture && fine ? e.rays : w.ray_list + (int64_t)i * n;
+            const int32_t* cnt = capture && fine ? e.count : w.ray_count + i;
             set_launch_tag(i);
             const int r3 = stnerf_copy_layer_raw_listed(raw, n, l, i, ns, lst, cnt, fine ? e.raw_fine : e.raw_coarse, e.rays, e.count, e.capacity,
-                                                        capture ? 1 : 0, capture ? nullptr : mismatch, stream);
+                                                        capture ? 1 : 0, capture ? nullptr : o.mismatch, stream);
             set_launch_tag(-1);
             if (r3) return r3;
         }
         return STNERF_OK;
     };
     // (raw_f lies over the whole coarse block: the coarse slice is copied here, before the compositor reads raw_c)
-    rc = stage_and_cache(xyz_c, raw_c, n1, false, cache ? cache->raw_coarse : nullptr);
+    rc = stage_and_cache(w.xyz_c, w.raw_c, n1, false, o.cache ? o.cache->raw_coarse : nullptr);
     if (rc) return rc;
 
     // ---- coarse: density edits, per-layer + merged composite (:414-448)
@@ -729,44 +639,44 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
         cp.use_threshold[i] = (p->retiming && i >= 1) ? 1 : 0;  // :416-418 (performers, retiming only)
         cp.threshold[i] = p->density_threshold;
     }
-    const bool scene_coarse = scene_out && p->only_coarse;   // (xyz_c is dead: the coarse networks have run)
+    const bool scene_coarse = o.scene_out && p->only_coarse;   // (xyz_c is dead: the coarse networks have run)
     // (termination: the merged weights go where the fine points will be -- scene_coarse is only_coarse, which terminates nothing)
-    rc = stnerf_composite_scene(t_c, raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w_c,
-                                nullptr, ray_flags, scene_coarse ? xyz_c : (term ? xyz_f : nullptr), scene_coarse ? scene_out : nullptr, stream);
+    rc = stnerf_composite_scene(w.t_c, w.raw_c, mask, n, l, n1, &cp, layer_coarse, mixed_coarse, p->only_coarse ? nullptr : w.w_c,
+                                nullptr, w.ray_flags, scene_coarse ? w.xyz_c : (term ? w.xyz_f : nullptr), scene_coarse ? o.scene_out : nullptr, stream);
     if (rc) return rc;
     if (p->only_coarse) {
-        if (occluder) {   // (the coarse stage is the final one: its merged weights lie in xyz_c)
-            rc = stnerf_scene_occluder(t_c, raw_c, mask, xyz_c, n, l, n1, &cp, scene_out, mixed_coarse, occluder, occluded_mixed, occluded_scene,
-                                       occluder_share, nullptr, nullptr, stream);
+        if (o.occluder) {   // (the coarse stage is the final one: its merged weights lie in xyz_c)
+            rc = stnerf_scene_occluder(w.t_c, w.raw_c, mask, w.xyz_c, n, l, n1, &cp, o.scene_out, mixed_coarse, o.occluder, o.occluded_mixed, o.occluded_scene,
+                                       o.occluder_share, nullptr, nullptr, stream);
             if (rc) return rc;
         }
         return clear_mask_hints(mask, n * l, as_stream(stream));
     }
     if (term) {   // (before the resampler overwrites the weights with the fine points)
-        rc = stnerf_ray_stop(t_c, xyz_f, n, l, n1, tau, t_stop, stream);
+        rc = stnerf_ray_stop(w.t_c, w.xyz_f, n, l, n1, o.tau, w.t_stop, stream);
         if (rc) return rc;
-        if (occluder_stops) {   // an opaque occluder in front of the stop depth is the stop depth
-            rc = stnerf_occluder_stop(occluder, n, t_stop, stream);
+        if (o.occluder_stops) {   // an opaque occluder in front of the stop depth is the stop depth
+            rc = stnerf_occluder_stop(o.occluder, n, w.t_stop, stream);
             if (rc) return rc;
         }
     }
 
     // ---- resample + fine points (:459-475), fine networks, fine composite (:538-606)
-    rc = stnerf_resample_rot(t_c, w_c, n, l, n1, n2, u, p->seed, p->ray_index_base, p->ray_index_stripe, p->ray_index_period,
+    rc = stnerf_resample_rot(w.t_c, w.w_c, n, l, n1, n2, u, p->seed, p->ray_index_base, p->ray_index_stripe, p->ray_index_period,
                              rays, rs,
-                             p->has_edits ? p->edits_fine : nullptr, p->pivot, rot, mask, t_f, xyz_f, nullptr, nullptr, nullptr, stream);
+                             p->has_edits ? p->edits_fine : nullptr, p->pivot, o.rot, mask, w.t_f, w.xyz_f, nullptr, nullptr, nullptr, stream);
     if (rc) return rc;
     for (int i = 1; i < l; ++i) {   // (xyz_c and t_c lie under raw_f: read here, before the fine stage)
         if (!(reuse >> i & 1)) continue;
-        hipLaunchKernelGGL(motion_reuse_fill_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, t_c, xyz_c, t_f, xyz_f,
-                           ray_list + (int64_t)i * n, ray_count + i, n, l, i, n1, n2, slots);
+        hipLaunchKernelGGL(motion_reuse_fill_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, w.t_c, w.xyz_c, w.t_f, w.xyz_f,
+                           w.ray_list + (int64_t)i * n, w.ray_count + i, n, l, i, n1, n2, w.slots);
         STNERF_CHECK_LAUNCH("render_rays (MotionNet reuse)");
         if (n2 == 0) continue;
-        rc = motion_rows(nets, p, rays, n, i, n2, S, xyz_f, ray_list, ray_count, slots, n2, motion_queue + 2 * i + 1, st);
+        rc = motion_rows(nets, p, rays, n, i, n2, S, w.xyz_f, w.ray_list, w.ray_count, w.slots, n2, motion_queue + 2 * i + 1, st);
         if (rc) return rc;
     }
     // (the cached fine slice lands on t_c / xyz_c: after the MotionNet reuse launches above have read them)
-    rc = stage_and_cache(xyz_f, raw_f, S, true, cache ? cache->raw_fine : nullptr);
+    rc = stage_and_cache(w.xyz_f, w.raw_f, S, true, o.cache ? o.cache->raw_fine : nullptr);
     if (rc) return rc;
     cp.fine = 1;
     cp.cut_negative_t = 0;
@@ -774,17 +684,107 @@ extern "C" int stnerf_render_rays_occluded(const float* rays, int64_t n, const f
         cp.use_threshold[i] = p->retiming ? 1 : 0;                       // :538-547 (bkgd), :564-566 (performers)
         cp.threshold[i] = i == 0 ? p->bkgd_density_threshold : p->density_threshold;
     }
-    if (layer_alpha)
-        for (int i = 0; i < l; ++i) cp.sigma_scale[i] = layer_alpha[i];
+    if (o.layer_alpha)
+        for (int i = 0; i < l; ++i) cp.sigma_scale[i] = o.layer_alpha[i];
     else if (l > 2)
         cp.sigma_scale[2] = p->alpha;                                    // :575-576
-    rc = stnerf_composite_scene(t_f, raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, ray_flags,
-                                scene_out ? xyz_f : nullptr, scene_out, stream);
+    rc = stnerf_composite_scene(w.t_f, w.raw_f, mask, n, l, S, &cp, layer_fine, mixed_fine, nullptr, nullptr, w.ray_flags,
+                                o.scene_out ? w.xyz_f : nullptr, o.scene_out, stream);
     if (rc) return rc;
-    if (occluder) {   // (xyz_f holds the fine merged weights)
-        rc = stnerf_scene_occluder(t_f, raw_f, mask, xyz_f, n, l, S, &cp, scene_out, mixed_fine, occluder, occluded_mixed, occluded_scene,
-                                   occluder_share, nullptr, nullptr, stream);
+    if (o.occluder) {   // (xyz_f holds the fine merged weights)
+        rc = stnerf_scene_occluder(w.t_f, w.raw_f, mask, w.xyz_f, n, l, S, &cp, o.scene_out, mixed_fine, o.occluder, o.occluded_mixed, o.occluded_scene,
+                                   o.occluder_share, nullptr, nullptr, stream);
         if (rc) return rc;
     }
     return clear_mask_hints(mask, n * l, as_stream(stream));
+}
+
+}  // namespace
+
+extern "C" int stnerf_render_rays_opts(RENDER_PARAMS, const stnerf_render_options* opts, stnerf_stream_t stream) {
+    const int src = check_options_size(opts, "render_rays");
+    if (src) return src;
+    const stnerf_render_options& o = opts ? *opts : kNoOptions;
+    Call call;
+    const int rc = check_call(RENDER_ARGS, o, &call);
+    if (rc) return rc;
+    if (n == 0) return STNERF_OK;
+    const Plan pl = make_plan(n, p->l, p->n1, p->n2, p->only_coarse);
+    const Workspace w(workspace, workspace_bytes, pl, call.rows, n, p->l);
+    return launch_sequence(RENDER_ARGS, o, call, pl, w, stream);
+}
+
+// ---- the fixed-argument forms (include/stnerf.h): each names the options up to the one it introduced, in the record's order, and
+// leaves the rest zero
+#define RENDER_ENTRY(name, params, ...)                                                \
+    extern "C" int name(RENDER_PARAMS, params stnerf_stream_t stream) {                \
+        const stnerf_render_options o = {(int32_t)sizeof(stnerf_render_options), __VA_ARGS__}; \
+        return stnerf_render_rays_opts(RENDER_ARGS, &o, stream);                       \
+    }
+#define P(...) __VA_ARGS__,
+extern "C" int stnerf_render_rays(RENDER_PARAMS, stnerf_stream_t stream) { return stnerf_render_rays_opts(RENDER_ARGS, nullptr, stream); }
+RENDER_ENTRY(stnerf_render_rays_cached, P(const stnerf_bkgd_cache* cache), cache)
+RENDER_ENTRY(stnerf_render_rays_rot, P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot), cache, rot)
+RENDER_ENTRY(stnerf_render_rays_scene, P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out), cache, rot, scene_out)
+RENDER_ENTRY(stnerf_render_rays_opacity, P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha),
+             cache, rot, scene_out, layer_alpha)
+RENDER_ENTRY(stnerf_render_rays_occupancy,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts),
+             cache, rot, scene_out, layer_alpha, occ, counts)
+RENDER_ENTRY(stnerf_render_rays_samples,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts, const int32_t* samples, int64_t* sample_counts),
+             cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts)
+RENDER_ENTRY(stnerf_render_rays_terminated,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts, const int32_t* samples, int64_t* sample_counts, float tau,
+               const int32_t* terminate, int64_t* visibility_counts),
+             cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts, tau, terminate, visibility_counts)
+RENDER_ENTRY(stnerf_render_rays_background,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts, const int32_t* samples, int64_t* sample_counts, float tau,
+               const int32_t* terminate, int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts),
+             cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts, tau, terminate, visibility_counts, bkgd_grid, bkgd_counts)
+RENDER_ENTRY(stnerf_render_rays_layers,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts, const int32_t* samples, int64_t* sample_counts, float tau,
+               const int32_t* terminate, int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
+               const stnerf_layer_cache* layers, int64_t* mismatch),
+             cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts, tau, terminate, visibility_counts, bkgd_grid, bkgd_counts,
+             layers, mismatch)
+RENDER_ENTRY(stnerf_render_rays_occluded,
+             P(const stnerf_bkgd_cache* cache, const stnerf_layer_rotation* rot, float* scene_out, const float* layer_alpha,
+               const stnerf_occupancy* occ, int32_t* counts, const int32_t* samples, int64_t* sample_counts, float tau,
+               const int32_t* terminate, int64_t* visibility_counts, const stnerf_occupancy* bkgd_grid, int64_t* bkgd_counts,
+               const stnerf_layer_cache* layers, int64_t* mismatch, const float* occluder, int32_t occluder_stops, float* occluded_mixed,
+               float* occluded_scene, float* occluder_share),
+             cache, rot, scene_out, layer_alpha, occ, counts, samples, sample_counts, tau, terminate, visibility_counts, bkgd_grid, bkgd_counts,
+             layers, mismatch, occluder, occluder_stops, occluded_mixed, occluded_scene, occluder_share)
+#undef P
+#undef RENDER_ENTRY
+
+// the named size queries: `background` != 0 stands for a grid with bits
+static int64_t workspace_bytes_of(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples, const int32_t* terminate, int background) {
+    static const uint32_t some_bits = 0;
+    const stnerf_occupancy grid = {&some_bits};
+    stnerf_render_options o = kNoOptions;
+    o.samples = samples;
+    o.terminate = terminate;
+    o.bkgd_grid = background ? &grid : nullptr;
+    return stnerf_render_workspace_bytes_opts(n, l, n1, n2, only_coarse, &o);
+}
+extern "C" int64_t stnerf_render_workspace_bytes(int64_t n, int l, int n1, int n2, int only_coarse) {
+    return workspace_bytes_of(n, l, n1, n2, only_coarse, nullptr, nullptr, 0);
+}
+extern "C" int64_t stnerf_render_workspace_bytes_samples(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples) {
+    return workspace_bytes_of(n, l, n1, n2, only_coarse, samples, nullptr, 0);
+}
+extern "C" int64_t stnerf_render_workspace_bytes_terminated(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
+                                                            const int32_t* terminate) {
+    return workspace_bytes_of(n, l, n1, n2, only_coarse, samples, terminate, 0);
+}
+extern "C" int64_t stnerf_render_workspace_bytes_background(int64_t n, int l, int n1, int n2, int only_coarse, const int32_t* samples,
+                                                            const int32_t* terminate, int background) {
+    return workspace_bytes_of(n, l, n1, n2, only_coarse, samples, terminate, background);
 }

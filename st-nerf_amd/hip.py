@@ -85,6 +85,20 @@ class Occupancy(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("res", C.c_int32 * 3), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
 
 
+class RenderOptions(C.Structure):
+    """stnerf_render_options (include/stnerf.h): every optional argument of the render call, in the order the named entries take them.
+    ``RenderOptions()`` is "no feature": all zero, struct_size set."""
+    _fields_ = [("struct_size", C.c_int32), ("cache", C.POINTER(BkgdCache)), ("rot", C.POINTER(LayerRotation)), ("scene_out", c_f32p),
+                ("layer_alpha", C.POINTER(C.c_float)), ("occ", C.POINTER(Occupancy)), ("counts", C.c_void_p),
+                ("samples", C.POINTER(C.c_int32)), ("sample_counts", C.c_void_p), ("tau", C.c_float),
+                ("terminate", C.POINTER(C.c_int32)), ("visibility_counts", C.c_void_p), ("bkgd_grid", C.POINTER(Occupancy)),
+                ("bkgd_counts", C.c_void_p), ("layers", C.POINTER(LayerCache)), ("mismatch", C.c_void_p), ("occluder", c_f32p),
+                ("occluder_stops", C.c_int32), ("occluded_mixed", c_f32p), ("occluded_scene", c_f32p), ("occluder_share", c_f32p)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=C.sizeof(RenderOptions), **fields)
+
+
 BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
 LAYER_CACHE_OFF, LAYER_CACHE_CAPTURE, LAYER_CACHE_REUSE = 0, 1, 2   # STNERF_LAYER_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
@@ -180,64 +194,22 @@ _PROTOS = {
                                        c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_composite_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "stnerf_render_workspace_bytes": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "stnerf_render_rays": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                     C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
-    "stnerf_render_rays_cached": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                            C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                            C.c_void_p]),
-    "stnerf_render_rays_rot": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                         C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                         C.POINTER(LayerRotation), C.c_void_p]),
-    "stnerf_render_rays_scene": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                           C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                           C.POINTER(LayerRotation), c_f32p, C.c_void_p]),
-    "stnerf_render_rays_opacity": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                             C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                             C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.c_void_p]),
-    "stnerf_render_rays_occupancy": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                               C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                               C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                               C.c_void_p]),
     "stnerf_occupancy_build": (C.c_int, [c_f32p, c_f32p, C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_occupancy_cull": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(Occupancy), C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_occupancy_rows": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64,
                                         C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_render_workspace_bytes_samples": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
-    "stnerf_render_rays_samples": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                             C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                             C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                             C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "stnerf_ray_stop": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "stnerf_visibility_rows": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, c_f32p, c_i64, c_f32p, c_i64, c_f32p, C.c_int,
                                          C.POINTER(Occupancy), c_f32p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_render_workspace_bytes_terminated": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "stnerf_render_rays_terminated": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                                C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                                C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                                C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "stnerf_background_rows": (C.c_int, [c_i64, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64, c_f32p, c_f32p, c_i64,
                                          C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_render_workspace_bytes_background": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                          C.c_int]),
-    "stnerf_render_rays_background": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                                C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                                C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                                C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
-                                                C.POINTER(Occupancy), C.c_void_p, C.c_void_p]),
-    "stnerf_render_rays_layers": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                            C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                            C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                            C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
-                                            C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, C.c_void_p]),
     "stnerf_scene_occluder": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), c_f32p, c_f32p,
                                         c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_occluder_stop": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_void_p]),
-    "stnerf_render_rays_occluded": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p,
-                                              C.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.POINTER(BkgdCache),
-                                              C.POINTER(LayerRotation), c_f32p, C.POINTER(C.c_float), C.POINTER(Occupancy), C.c_void_p,
-                                              C.POINTER(C.c_int32), C.c_void_p, C.c_float, C.POINTER(C.c_int32), C.c_void_p,
-                                              C.POINTER(Occupancy), C.c_void_p, C.POINTER(LayerCache), C.c_void_p, c_f32p, C.c_int32,
-                                              c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_generate_rays_list": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
                                             C.c_float, C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_accumulate": (C.c_int, [c_f32p, c_i64, C.c_int, c_i64, C.c_void_p, c_i64, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
@@ -254,6 +226,19 @@ _PROTOS = {
                                       C.c_int, C.POINTER(LayerEdit), C.POINTER(C.c_float), C.POINTER(LayerRotation), C.c_void_p, c_f32p,
                                       c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p]),
 }
+
+# The render entries: the 15 arguments each of them starts with, then the options -- as one record (stnerf_render_rays_opts) or, in
+# the named fixed-argument forms, the record's fields up to the one the entry introduced -- then the stream.
+_RENDER_PREFIX = [c_f32p, c_i64, c_f32p, c_i64, C.POINTER(Nets), C.POINTER(RenderParams), c_f32p, c_f32p, C.c_void_p, c_i64,
+                  c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]
+_OPTION_NAMES, _OPTION_TYPES = zip(*RenderOptions._fields_)
+_LAST_OPTION = {"": "struct_size", "_cached": "cache", "_rot": "rot", "_scene": "scene_out", "_opacity": "layer_alpha",
+                "_occupancy": "counts", "_samples": "sample_counts", "_terminated": "visibility_counts", "_background": "bkgd_counts",
+                "_layers": "mismatch", "_occluded": "occluder_share"}
+for _suffix, _last in _LAST_OPTION.items():   # (struct_size itself is no argument of a named entry)
+    _PROTOS["stnerf_render_rays" + _suffix] = (C.c_int, _RENDER_PREFIX + list(_OPTION_TYPES[1:_OPTION_NAMES.index(_last) + 1]) + [C.c_void_p])
+_PROTOS["stnerf_render_rays_opts"] = (C.c_int, _RENDER_PREFIX + [C.POINTER(RenderOptions), C.c_void_p])
+_PROTOS["stnerf_render_workspace_bytes_opts"] = (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RenderOptions)])
 
 _lib: Optional[C.CDLL] = None
 

@@ -251,6 +251,31 @@ class LayeredRFRender(nn.Module):
         self._layer_cache = cache
         return self
 
+    def _edited_layer_key(self, i, box, pivot):
+        """What the two cache keys hold of layer ``i``'s edits, as hashable host values: its EDITED box (``box``: the unedited one, a
+        host copy this may change), its coarse and its fine point un-edit, the pivot they use and its (m, c) ray transform with the
+        default centre it would get (the edited box's) -> (box bytes, coarse edit, fine edit, pivot tuple | None, rot | None)."""
+        if self.scale is not None and pivot is None:
+            pivot = self._pivot()
+        if self.scale is not None and i < len(self.scale):
+            box = (box - pivot) * self.scale[i] + pivot
+        if self.shift is not None and i < len(self.shift) and self.shift[i] is not None:
+            box = box + torch.tensor(self.shift[i], dtype=torch.float32)
+        rot = None
+        if self.rotation is not None:
+            sp = self._rotation_specs()
+            if sp is not None and sp[i] is not None:
+                m = sp[i][0].T.contiguous()
+                c = sp[i][1] if sp[i][1] is not None else torch.mean(box, 0)
+                rot = (m.numpy().tobytes(), c.numpy().tobytes())
+        def edit(fine):
+            e = self._point_edits(self.total_layers, fine)
+            if e is None:
+                return None
+            sh, sc = e[i]
+            return (None if sh is None else tuple(float(x) for x in sh), None if sc is None else float(sc))
+        return box.numpy().tobytes(), edit(False), edit(True), None if pivot is None else tuple(float(x) for x in pivot.tolist()), rot
+
     def layer_cache_key(self, i, view_key, piece, window, retiming, only_coarse, pivot=None, frame_ids=None, density_threshold=None):
         """(group, piece): the key of performer / instance ``i``'s raw outputs of a launch piece -- host arithmetic only (the box
         table's host copy is made once per tensor version, ``_box_table_host``).  The group reads every item of
@@ -281,26 +306,7 @@ class LayeredRFRender(nn.Module):
                 raise ValueError("layer_cache_key: with retiming and a fine stage the layer's fine samples depend on density_threshold; pass it")
             thr = float(density_threshold)
         view = view_key[0]
-        box = self.layer_box_at(i, fid, retiming).clone()
-        if self.scale is not None and pivot is None:
-            pivot = self._pivot()
-        if self.scale is not None and i < len(self.scale):
-            box = (box - pivot) * self.scale[i] + pivot
-        if self.shift is not None and i < len(self.shift) and self.shift[i] is not None:
-            box = box + torch.tensor(self.shift[i], dtype=torch.float32)
-        rot = None
-        if self.rotation is not None:                     # the layer's ray transform (its default centre: the edited box's)
-            sp = self._rotation_specs()
-            if sp is not None and sp[i] is not None:
-                m = sp[i][0].T.contiguous()
-                c = sp[i][1] if sp[i][1] is not None else torch.mean(box, 0)
-                rot = (m.numpy().tobytes(), c.numpy().tobytes())
-        def edit(fine):
-            e = self._point_edits(l, fine)
-            if e is None:
-                return None
-            sh, sc = e[i]
-            return (None if sh is None else tuple(float(x) for x in sh), None if sc is None else float(sc))
+        box, edit_c, edit_f, pivot, rot = self._edited_layer_key(i, self.layer_box_at(i, fid, retiming).clone(), pivot)
         j = self._module_index(i)
         nets = [self.spacenets[j], self.spacenets_fine[j]] + ([self.time_deform_nets[j]] if self.use_deform_time else [])
         prec = self.bkgd_spacenet.precision
@@ -317,7 +323,7 @@ class LayeredRFRender(nn.Module):
             grid = None if grid is None else grid + (bool(grids.samples),)
         group = ("layer", int(i), view, int(self.seed) & 0xFFFFFFFFFFFFFFFF, int(self.coarse_ray_sample), int(self.fine_ray_sample),
                  bool(only_coarse), prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), 6 + want,
-                 box.numpy().tobytes(), edit(False), edit(True), None if pivot is None else tuple(float(x) for x in pivot.tolist()),
+                 box, edit_c, edit_f, pivot,
                  float(self.near), float(self.boarder_weight), (bool(self.use_deform_time), bool(self.use_space_time), bool(self.deep_rgb)),
                  j, tuple(_params_fingerprint(m) for m in nets), fid, rot, grid, thr)
         return group, (int(piece[0]), int(piece[1]), tuple(int(x) for x in window))
@@ -406,6 +412,13 @@ class LayeredRFRender(nn.Module):
             ops.spacenet_fwd(nets[j]._packed("fp32"), xyz, dirs, times if self.use_space_time else None, raw)
         return raw[..., 3].reshape(rz + 1, ry + 1, rx + 1).contiguous(), lo, hi
 
+    @staticmethod
+    def _frame_id_ranges(groups, cols):
+        """(min, max) of the frame-id columns ``cols(start, end)`` within every chunk group, on the host (a min / max on the device
+        and one device-to-host copy), and the test both callers apply to a pair: the ids differ, or are NaN."""
+        mm = torch.stack([torch.stack([cols(g[0], g[1]).amin(0), cols(g[0], g[1]).amax(0)]) for g in groups]).cpu()
+        return mm, lambda lo, hi: float(lo) != float(hi) or lo != lo
+
     def _occupancy_frame_ids(self, rays, groups, retiming):
         """Per chunk group the frame id of every layer (l floats), after checking that each CULLED layer's frame-id column is
         constant within the group: a min / max on the device and one device-to-host copy.  A grid at row 0's id applied to rays
@@ -413,11 +426,11 @@ class LayeredRFRender(nn.Module):
         l = self.total_layers
         culled = self._occupancy.culled_layers(self)
         cols = (lambda a, b: rays[a:b, 6:6 + l]) if retiming else (lambda a, b: rays[a:b, 6:7].expand(b - a, l))
-        mm = torch.stack([torch.stack([cols(g[0], g[1]).amin(0), cols(g[0], g[1]).amax(0)]) for g in groups]).cpu()
+        mm, mixed = self._frame_id_ranges(groups, cols)
         out = []
         for k, g in enumerate(groups):
             for i in culled:
-                if float(mm[k, 0, i]) != float(mm[k, 1, i]) or mm[k, 0, i] != mm[k, 0, i]:
+                if mixed(mm[k, 0, i], mm[k, 1, i]):
                     raise ValueError(f"occupancy: layer {i} has frame ids {float(mm[k, 0, i])} .. {float(mm[k, 1, i])} among rays {g[0]}..{g[1]} of "
                                      "one chunk group; a culled layer needs one frame id per group (its grid is made at that id) -- "
                                      "render one frame id per chunk group, or detach the grids (set_occupancy(None))")
@@ -428,10 +441,10 @@ class LayeredRFRender(nn.Module):
         """Per chunk group the background's frame id (column 6), for its occupancy grid; where the background flags make the id an
         input of the density it must be constant within the group (the min / max check of ``_occupancy_frame_ids``): a grid made
         at row 0's id applied to rays of another id would cull wrongly and silently."""
-        mm = torch.stack([torch.stack([rays[g[0]:g[1], 6].amin(0), rays[g[0]:g[1], 6].amax(0)]) for g in groups]).cpu()
+        mm, mixed = self._frame_id_ranges(groups, lambda a, b: rays[a:b, 6])
         if self._occupancy.background_timed(self):
             for k, g in enumerate(groups):
-                if float(mm[k, 0]) != float(mm[k, 1]) or mm[k, 0] != mm[k, 0]:
+                if mixed(mm[k, 0], mm[k, 1]):
                     raise ValueError(f"occupancy: the background has frame ids {float(mm[k, 0])} .. {float(mm[k, 1])} among rays {g[0]}..{g[1]} of "
                                      "one chunk group; under BKGD_USE_DEFORM_TIME / BKGD_USE_SPACE_TIME its grid is made at one id -- "
                                      "render one background frame id per chunk group, or drop the background's grid")
@@ -450,37 +463,17 @@ class LayeredRFRender(nn.Module):
         digest of a manual one -- the cached outputs are the culled ones."""
         from stnerf_amd.modeling._packed import _params_fingerprint
         view, bkgd_frame = view_key
-        l = self.total_layers
         timed = self.bkgd_use_deform_time or (self.bkgd_use_space_time and self.use_space_time)
         bk = self.bkgd_bbox
         host = getattr(self, "_bkgd_bbox_host", None)          # (one D2H per box version, not per frame)
         if host is None or host[0] is not bk or host[1] != bk._version:
             host = self._bkgd_bbox_host = (bk, bk._version, bk.detach().cpu().float().clone())
-        box0 = host[2].clone()
-        if self.scale is not None and pivot is None:
-            pivot = self._pivot()
-        if self.scale is not None and len(self.scale) > 0:
-            box0 = (box0 - pivot) * self.scale[0] + pivot
-        if self.shift is not None and len(self.shift) > 0 and self.shift[0] is not None:
-            box0 = box0 + torch.tensor(self.shift[0], dtype=torch.float32)
-        rot0 = None
-        if self.rotation is not None:                     # layer 0's ray transform (its default centre: the edited box's)
-            sp0 = self._rotation_specs()
-            if sp0 is not None and sp0[0] is not None:
-                m0 = sp0[0][0].T.contiguous()
-                c0 = sp0[0][1] if sp0[0][1] is not None else torch.mean(box0, 0)
-                rot0 = (m0.numpy().tobytes(), c0.numpy().tobytes())
-        def edit0(fine):
-            e = self._point_edits(l, fine)
-            if e is None:
-                return None
-            sh, sc = e[0]
-            return (None if sh is None else tuple(float(x) for x in sh), None if sc is None else float(sc))
+        box0, edit_c, edit_f, pivot, rot0 = self._edited_layer_key(0, host[2].clone(), pivot)
         nets = [self.bkgd_spacenet, self.bkgd_spacenet_fine] + ([self.bkgd_time_deform_net] if self.bkgd_use_deform_time else [])
         prec = self.bkgd_spacenet.precision
         group = (view, int(self.seed) & 0xFFFFFFFFFFFFFFFF, int(self.coarse_ray_sample), int(self.fine_ray_sample), bool(only_coarse),
-                 prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), box0.numpy().tobytes(), edit0(False), edit0(True),
-                 None if pivot is None else tuple(float(x) for x in pivot.tolist()), float(self.near), float(self.boarder_weight),
+                 prec, self.mlp_schedule if prec != "bf16x3" else "stage", bool(retiming), box0, edit_c, edit_f,
+                 pivot, float(self.near), float(self.boarder_weight),
                  (bool(self.bkgd_use_deform_time), bool(self.bkgd_use_space_time), bool(self.use_space_time), bool(self.deep_rgb)),
                  tuple(_params_fingerprint(m) for m in nets), bkgd_frame if timed else None, rot0)
         grids = getattr(self, "_occupancy", None)
@@ -682,16 +675,58 @@ class LayeredRFRender(nn.Module):
         ``render_rays_occluded`` (with scene): three more tensors come back; occluder_stops: its opaque rows lower the stop depth of
         the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached)."""
         from stnerf_amd import hip
-        n, l = rays.shape[0], self.total_layers
+        n, l, dev = rays.shape[0], self.total_layers, rays.device
+        p = self._render_params(rays.shape[1], pivot, retiming, only_coarse, thr, bthr, window)
+        keep = []                                                    # packed blobs and grids must outlive the enqueue
+        nets = self._net_pointers(keep)
+        # the culls come before the workspace: their row lists and stop depths are part of it
+        kw = self._occupancy_keywords(rays, retiming, occupancy_ids, background_id, keep)
+        lcache = self._layer_cache if piece is not None else None
+        lkeys = self._layer_cache_keys(lcache, piece, window, retiming, only_coarse, pivot, thr)
+        kw.update(self._termination_keywords(dev, only_coarse, lkeys))
+        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=kw.get("occupancy_samples"),
+                                          **(dict(terminate=kw["terminate"]) if "terminate" in kw else {}),
+                                          **(dict(background=True) if "background_grid" in kw else {}))
+        ws = getattr(self, "_workspace", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        cache = self._bkgd_cache if piece is not None else None
+        key, cache_arg = self._plan_background_cache(cache, piece, window, retiming, only_coarse, pivot, n, dev)
+        lc_kw, wanted, capturing = self._plan_layer_caches(lcache, lkeys, only_coarse, dev)
+        kw.update(lc_kw)
+        # (a keyword travels only while its feature is on: an uncached, unedited call is the plain one it always was)
+        if scene:
+            kw.update(scene=True)
+        if occluder is not None:
+            kw.update(occluder=occluder, occluder_stops=bool(occluder_stops) and "terminate" in kw)
+        table = self._layer_alpha_table()
+        if table is not None:
+            kw.update(layer_alpha=table)
+        try:
+            out = ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
+                                  u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations, **kw)
+        except Exception:
+            if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
+                cache.discard(key)             # (never filled)
+            for k in capturing:
+                lcache.discard(k)
+            raise
+        for i in wanted:                       # first sighting: the layer's hit count stays on the device (no sync)
+            lcache.sighted(lkeys[i], out[4][:, i].sum(dtype=torch.int32))
+        return out
+
+    def _render_params(self, ray_width, pivot, retiming, only_coarse, thr, bthr, window):
+        """The stnerf_render_params of one launch piece."""
+        from stnerf_amd import hip
+        l = self.total_layers
         p = hip.RenderParams()
-        p.l, p.n1, p.n2, p.ray_stride = l, self.coarse_ray_sample, self.fine_ray_sample, rays.shape[1]
+        p.l, p.n1, p.n2, p.ray_stride = l, self.coarse_ray_sample, self.fine_ray_sample, ray_width
         p.retiming, p.only_coarse = int(retiming), int(only_coarse)
         p.use_deform_time, p.use_space_time = int(self.use_deform_time), int(self.use_space_time)
         p.bkgd_use_deform_time, p.bkgd_use_space_time = int(self.bkgd_use_deform_time), int(self.bkgd_use_space_time)
         p.deep_rgb = int(self.deep_rgb)
         # 3: bf16x3 (the default); 0: exact f32, one persistent launch per network stage; 2: exact f32, one launch per network
-        prec = self.bkgd_spacenet.precision
-        p.precision = 3 if prec == "bf16x3" else (0 if self.mlp_schedule == "stage" else 2)
+        p.precision = 3 if self.bkgd_spacenet.precision == "bf16x3" else (0 if self.mlp_schedule == "stage" else 2)
         for i in range(l):
             p.shown[i] = int(self.is_shown_layer(i))
         p.border, p.near, p.alpha = float(self.boarder_weight), float(self.near), float(self.alpha)
@@ -704,8 +739,13 @@ class LayeredRFRender(nn.Module):
         ops.fill_edits(p.edits_fine, ef, l)
         if pivot is not None:
             p.pivot[0], p.pivot[1], p.pivot[2] = pivot.tolist()
+        return p
+
+    def _net_pointers(self, keep):
+        """The stnerf_nets of the shown layers in the model's arithmetic; the packed blobs go to ``keep``."""
+        from stnerf_amd import hip
+        prec = self.bkgd_spacenet.precision
         nets = hip.Nets()
-        keep = []                                                    # packed blobs must outlive the enqueue
         def ptr(module):
             pk = module._packed(prec)
             keep.append(pk)
@@ -713,80 +753,80 @@ class LayeredRFRender(nn.Module):
         nets.bkgd, nets.bkgd_fine = ptr(self.bkgd_spacenet), ptr(self.bkgd_spacenet_fine)
         if self.bkgd_use_deform_time:
             nets.motion[0] = ptr(self.bkgd_time_deform_net)
-        for i in range(1, l):
+        for i in range(1, self.total_layers):
             if not self.is_shown_layer(i):
                 continue
             j = self._module_index(i)                                # (an instance: its source's blobs, the same pointers)
             nets.space[i], nets.space_fine[i] = ptr(self.spacenets[j]), ptr(self.spacenets_fine[j])
             if self.use_deform_time:
                 nets.motion[i] = ptr(self.time_deform_nets[j])
-        table = self._layer_alpha_table()
-        # the occupancy table comes before the workspace: with the sample cull the workspace grows by the row lists of the gridded
-        # layers, so `need` below depends on it.  (Without grids nothing here runs; the ray cull alone sizes the workspace as ever.)
-        occ_kw = {}
+        return nets
+
+    def _occupancy_keywords(self, rays, retiming, occupancy_ids, background_id, keep):
+        """``ops.render_rays``'s keywords of the attached grids: the performers' table (looked up or built at ``occupancy_ids``) with
+        its counters, the sample flags where the grids cull samples, and the background's grid at ``background_id``.  Nothing
+        without grids; the grids in use go to ``keep``."""
+        l, kw = self.total_layers, {}
         if occupancy_ids is not None:
             grids = self._occupancy
             occ_table, held = grids.table(self, occupancy_ids, rays.device, retiming)
             keep.append(held)
             if any(e is not None for e in occ_table):
-                occ_kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
+                kw = dict(occupancy=occ_table, occupancy_counts=grids.counts(rays.device)[:l])
                 if grids.samples:      # every ray-culled layer is sample-culled too (DESIGN.md section 7)
-                    occ_kw.update(occupancy_samples=[e is not None for e in occ_table], sample_counts=grids.sample_counts(rays.device)[:l])
+                    kw.update(occupancy_samples=[e is not None for e in occ_table], sample_counts=grids.sample_counts(rays.device)[:l])
         if background_id is not None:
             bg = self._occupancy.background_grid(self, background_id, rays.device)
             keep.append(bg)
-            occ_kw.update(background_grid=bg.entry(), background_counts=self._occupancy.background_counts(rays.device))
-        # the layer cache: every shown performer / instance of a piece whose view is known on the host
-        lcache, lkeys = (self._layer_cache if piece is not None else None), {}
-        if lcache is not None and self.view_frame_ids is not None and len(self.view_frame_ids) == (l if retiming else 1):
-            lkeys = {i: self.layer_cache_key(i, self.view_key, piece, window, retiming, only_coarse, pivot, density_threshold=thr)
-                     for i in range(1, l) if self.is_shown_layer(i)}
+            kw.update(background_grid=bg.entry(), background_counts=self._occupancy.background_counts(rays.device))
+        return kw
+
+    def _layer_cache_keys(self, lcache, piece, window, retiming, only_coarse, pivot, thr):
+        """{layer: its ``layer_cache_key``} of every shown performer / instance of a piece whose view is known on the host."""
+        l = self.total_layers
+        if lcache is None or self.view_frame_ids is None or len(self.view_frame_ids) != (l if retiming else 1):
+            return {}
+        return {i: self.layer_cache_key(i, self.view_key, piece, window, retiming, only_coarse, pivot, density_threshold=thr)
+                for i in range(1, l) if self.is_shown_layer(i)}
+
+    def _termination_keywords(self, device, only_coarse, lkeys):
+        """``ops.render_rays``'s keywords of the attached termination, or nothing: no fine stage, no flag left (a cached performer,
+        one of ``lkeys``, is not terminated)."""
         term = getattr(self, "_termination", None)
-        if term is not None and not only_coarse:
-            flags = [0 if i in lkeys else f for i, f in enumerate(term.flags(self))]   # (a cached performer is not terminated)
-            if any(flags):
-                occ_kw.update(terminate=flags, tau=term.tau, visibility_counts=term.counts(rays.device)[:l])
-        need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=occ_kw.get("occupancy_samples"),
-                                          **(dict(terminate=occ_kw["terminate"]) if "terminate" in occ_kw else {}),
-                                          **(dict(background=True) if "background_grid" in occ_kw else {}))
-        ws = getattr(self, "_workspace", None)
-        if ws is None or ws.numel() < need or ws.device != rays.device:
-            self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=rays.device)
-        cache, key, cache_arg = self._bkgd_cache, None, None
-        if piece is not None and cache is not None:
-            # the background's raw outputs of this piece: from the cache (hit), into it (miss with room), or neither (over budget)
-            key = self.background_cache_key(self.view_key, piece, window, retiming, only_coarse, pivot)
-            entry = cache.lookup(key)
-            mode = hip.BKGD_CACHE_REUSE
-            if entry is None:
-                entry, mode = cache.reserve(key, n, p.n1, p.n2, only_coarse, rays.device), hip.BKGD_CACHE_CAPTURE
-            if entry is not None:
-                cache_arg = (entry[0], entry[1], mode)
-        # per cached layer: from its entry (third sighting on), into a fresh one (second sighting, room in the budget), or neither
-        lc_kw, wanted, capturing = {}, [], []
-        if lkeys:
-            plans = {i: lcache.plan(k, p.n1, p.n2, only_coarse, rays.device) for i, k in lkeys.items()}
-            wanted = [i for i, k in lkeys.items() if plans[i][1] is None and lcache.wants_count(k)]
-            capturing = [lkeys[i] for i, (mode, _) in plans.items() if mode == hip.LAYER_CACHE_CAPTURE]
-            if any(e is not None for _, e in plans.values()):
-                lc_kw = dict(layer_caches=[plans[i][1].arg(plans[i][0]) if i in plans and plans[i][1] is not None else None for i in range(l)],
-                             layer_mismatch=lcache.mismatch_counter(rays.device))
-        try:
-            out = ops.render_rays(rays, boxes, nets, p, ws, jitter=replay["jitter"] if replay else None,
-                                  u=(replay.get("u") if replay else None), cache=cache_arg, rotations=rotations,
-                                  **(dict(scene=True) if scene else {}), **occ_kw, **lc_kw,
-                                  **(dict(occluder=occluder, occluder_stops=bool(occluder_stops) and "terminate" in occ_kw)
-                                     if occluder is not None else {}),
-                                  **(dict(layer_alpha=table) if table is not None else {}))
-        except Exception:
-            if cache_arg is not None and cache_arg[2] == hip.BKGD_CACHE_CAPTURE:
-                cache.discard(key)             # (never filled)
-            for k in capturing:
-                lcache.discard(k)
-            raise
-        for i in wanted:                       # first sighting: the layer's hit count stays on the device (no sync)
-            lcache.sighted(lkeys[i], out[4][:, i].sum(dtype=torch.int32))
-        return out
+        if term is None or only_coarse:
+            return {}
+        flags = [0 if i in lkeys else f for i, f in enumerate(term.flags(self))]
+        if not any(flags):
+            return {}
+        return dict(terminate=flags, tau=term.tau, visibility_counts=term.counts(device)[:self.total_layers])
+
+    def _plan_background_cache(self, cache, piece, window, retiming, only_coarse, pivot, n, device):
+        """-> (key, ``ops.render_rays``'s cache argument): the background's raw outputs of this piece come from the cache (hit), go
+        into it (miss with room), or neither (no cache, over budget)."""
+        from stnerf_amd import hip
+        if cache is None:
+            return None, None
+        key = self.background_cache_key(self.view_key, piece, window, retiming, only_coarse, pivot)
+        entry, mode = cache.lookup(key), hip.BKGD_CACHE_REUSE
+        if entry is None:
+            entry, mode = cache.reserve(key, n, self.coarse_ray_sample, self.fine_ray_sample, only_coarse, device), hip.BKGD_CACHE_CAPTURE
+        return key, (None if entry is None else (entry[0], entry[1], mode))
+
+    def _plan_layer_caches(self, lcache, lkeys, only_coarse, device):
+        """-> (``ops.render_rays``'s layer-cache keywords, the layers whose hit count is wanted, the keys being captured).  Per cached
+        layer: from its entry (third sighting on), into a fresh one (second sighting, room in the budget), or neither."""
+        from stnerf_amd import hip
+        if not lkeys:
+            return {}, [], []
+        l = self.total_layers
+        plans = {i: lcache.plan(k, self.coarse_ray_sample, self.fine_ray_sample, only_coarse, device) for i, k in lkeys.items()}
+        wanted = [i for i, k in lkeys.items() if plans[i][1] is None and lcache.wants_count(k)]
+        capturing = [lkeys[i] for i, (mode, _) in plans.items() if mode == hip.LAYER_CACHE_CAPTURE]
+        kw = {}
+        if any(e is not None for _, e in plans.values()):
+            kw = dict(layer_caches=[plans[i][1].arg(plans[i][0]) if i in plans and plans[i][1] is not None else None for i in range(l)],
+                      layer_mismatch=lcache.mismatch_counter(device))
+        return kw, wanted, capturing
 
     def render_rays(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
                     ref_chunk: Optional[int] = None):
@@ -795,6 +835,15 @@ class LayeredRFRender(nn.Module):
         return self.as_reference_tuple(self.render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold,
                                                             ref_chunk))
 
+    def _refuse_scene_call(self, name, what_has, how):
+        """The two refusals of the calls that return scene passes: in training mode (no backward) and on more than one rank."""
+        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError(f"{name} in training mode: {what_has} no backward; call model.eval() or wrap the render in torch.no_grad()")
+        from stnerf_amd import parallel
+        if parallel.active_group(self) is not None:
+            raise RuntimeError(f"{name} under shard_views with more than one rank: the all-gather's modes (stnerf_amd.parallel) "
+                               f"have fixed widths and a \"scene\" gather mode is out of scope; {how} (model.shard_views = False)")
+
     def render_rays_scene(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
                           ref_chunk: Optional[int] = None):
         """``render_rays`` plus the in-scene layer passes of the final stage -> (the reference 5-tuple, scene).  ``scene`` is a
@@ -802,14 +851,7 @@ class LayeredRFRender(nn.Module):
         weighted depth and alpha with the other layers occluding it and being occluded by it (fine_layer[i] is layer i alone).
         Their sum over the layers is the mixed triple up to fp32 summation order; a hidden layer's is exact zeros.  The five
         standard outputs are the bits of ``render_rays``.  Inference only: no backward is defined for the pass."""
-        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("render_rays_scene in training mode: the in-scene layer passes have no backward; call model.eval() or "
-                               "wrap the render in torch.no_grad()")
-        from stnerf_amd import parallel
-        if parallel.active_group(self) is not None:
-            raise RuntimeError("render_rays_scene under shard_views with more than one rank: the all-gather's modes (stnerf_amd.parallel) "
-                               "have fixed widths and a \"scene\" gather mode is out of scope; render the passes on one rank "
-                               "(model.shard_views = False)")
+        self._refuse_scene_call("render_rays_scene", "the in-scene layer passes have", "render the passes on one rank")
         raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True)
         sc = raw[5]
         scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.total_layers)]
@@ -829,14 +871,7 @@ class LayeredRFRender(nn.Module):
         are not evaluated; it needs an attached termination (``set_termination``; ValueError otherwise).  The occluded outputs keep
         their bits; the 5-tuple and ``scene`` become those of the terminated scene.  Without it they are the bits of
         ``render_rays_scene``.  Inference only, one rank, the fused pipeline only."""
-        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("render_rays_occluded in training mode: the occluder composite has no backward; call model.eval() or "
-                               "wrap the render in torch.no_grad()")
-        from stnerf_amd import parallel
-        if parallel.active_group(self) is not None:
-            raise RuntimeError("render_rays_occluded under shard_views with more than one rank: the all-gather's modes "
-                               "(stnerf_amd.parallel) have fixed widths and a \"scene\" gather mode is out of scope; render on one "
-                               "rank (model.shard_views = False)")
+        self._refuse_scene_call("render_rays_occluded", "the occluder composite has", "render on one rank")
         if stops and getattr(self, "_termination", None) is None:
             raise ValueError("render_rays_occluded(stops=True) without early ray termination: the occluder lowers the stop depth the "
                              "terminated layers' row lists test; call set_termination(...) first or pass stops=False")

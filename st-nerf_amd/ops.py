@@ -651,6 +651,11 @@ def _layer_flags(flags, l, name):
     return (C.c_int32 * l)(*(int(bool(f)) for f in flags))
 
 
+# (the size query reads only whether a background grid has bits: any non-null pointer stands for "a grid will be given")
+_SOME_GRID = (hip.Occupancy * 1)()
+_SOME_GRID[0].bits = C.addressof(_SOME_GRID)
+
+
 def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None, terminate=None,
                            background: bool = False) -> int:
     """Bytes of ``render_rays``'s workspace.  ``occupancy_samples``: the per-layer flags of the sample cull or None -- only
@@ -659,20 +664,14 @@ def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, 
     by the stop depths and the flagged layers' fine row lists (stnerf_render_workspace_bytes_terminated).
     ``background``: a background grid will be given -- the workspace grows by layer 0's row list unless termination has given it one
     (stnerf_render_workspace_bytes_background)."""
+    opts = hip.RenderOptions()
+    if occupancy_samples is not None and any(occupancy_samples):
+        opts.samples = _layer_flags(occupancy_samples, l, "occupancy_samples")
+    if terminate is not None:
+        opts.terminate = _layer_flags(terminate, l, "terminate")
     if background:
-        sam = None if occupancy_samples is None or not any(occupancy_samples) else _layer_flags(occupancy_samples, l, "occupancy_samples")
-        ter = None if terminate is None else _layer_flags(terminate, l, "terminate")
-        nb = hip.lib().stnerf_render_workspace_bytes_background(n, l, n1, n2, int(only_coarse), sam, ter, 1)
-    elif terminate is not None:       # (no flag set: the entry returns stnerf_render_workspace_bytes_samples' value)
-        sam = None if occupancy_samples is None or not any(occupancy_samples) else _layer_flags(occupancy_samples, l, "occupancy_samples")
-        nb = hip.lib().stnerf_render_workspace_bytes_terminated(n, l, n1, n2, int(only_coarse), sam, _layer_flags(terminate, l, "terminate"))
-    elif occupancy_samples is not None and any(occupancy_samples):
-        if len(occupancy_samples) != l:
-            raise ValueError(f"occupancy_samples must have one entry per layer ({l}), got {len(occupancy_samples)}")
-        flags = (C.c_int32 * l)(*(int(bool(f)) for f in occupancy_samples))
-        nb = hip.lib().stnerf_render_workspace_bytes_samples(n, l, n1, n2, int(only_coarse), flags)
-    else:
-        nb = hip.lib().stnerf_render_workspace_bytes(n, l, n1, n2, int(only_coarse))
+        opts.bkgd_grid = _SOME_GRID
+    nb = hip.lib().stnerf_render_workspace_bytes_opts(n, l, n1, n2, int(only_coarse), C.byref(opts))
     if nb < 0:
         hip.check(int(nb), "stnerf_render_workspace_bytes")
     return int(nb)
@@ -964,110 +963,57 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     else:
         mix_f = torch.empty(n, 5, dtype=torch.float32, device=dev)
         lo_f = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
-    args = (hip.dptr(rays, name="rays"), n, bp, bstride, C.byref(nets), C.byref(params),
-            hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
-            hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
-            hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8))
-    rot = _rotations(rotations, l)
-    bc = None
+    # every optional argument, checked once and named once (stnerf_render_options); what is given but inert -- tau without a flag, count
+    # tensors without their feature -- travels as it is: the library ignores it
+    opts = hip.RenderOptions(tau=float(tau), occluder_stops=int(bool(occluder_stops)))
+    opts.rot = _rotations(rotations, l)
     if cache is not None:
         raw_c, raw_f, mode = cache
         S = params.n1 + params.n2
         if tuple(raw_c.shape) != (n, params.n1, 4) or (raw_f is not None and tuple(raw_f.shape) != (n, S, 4)):
             raise ValueError(f"render_rays: the background cache of {n} rays must be ({n},{params.n1},4) and ({n},{S},4)")
-        bc = hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode))
+        opts.cache = C.pointer(hip.BkgdCache(hip.dptr(raw_c, name="cache raw_coarse").value, hip.dptr(raw_f, name="cache raw_fine").value, int(mode)))
     scene_out = torch.empty(n, l, 5, dtype=torch.float32, device=dev) if scene else None
-    if layer_alpha is not None and len(layer_alpha) != l:
-        raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
+    opts.scene_out = hip.dptr(scene_out)
+    if layer_alpha is not None:
+        if len(layer_alpha) != l:
+            raise ValueError(f"layer_alpha must have one entry per layer ({l}), got {len(layer_alpha)}")
+        opts.layer_alpha = (C.c_float * l)(*(float(a) for a in layer_alpha))
+    opts.occ = _occupancy_table(occupancy, l)
+    if occupancy_samples is not None and any(occupancy_samples):
+        if occupancy is None or len(occupancy_samples) != l:
+            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
+        opts.samples = _layer_flags(occupancy_samples, l, "occupancy_samples")
+    if terminate is not None:
+        opts.terminate = _layer_flags(terminate, l, "terminate")
+    for name, c in (("occupancy_counts", occupancy_counts), ("sample_counts", sample_counts), ("visibility_counts", visibility_counts)):
+        if c is not None and tuple(c.shape) != (l, 2):
+            raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
+    if background_counts is not None and tuple(background_counts.shape) != (2,):
+        raise ValueError(f"background_counts must be int64 (2,), got {tuple(background_counts.shape)}")
+    if layer_mismatch is not None and layer_mismatch.numel() < 1:
+        raise ValueError("layer_mismatch must hold one int64")
+    opts.counts = hip.dptr(occupancy_counts, torch.int32, "occupancy_counts")
+    opts.sample_counts = hip.dptr(sample_counts, torch.int64, "sample_counts")
+    opts.visibility_counts = hip.dptr(visibility_counts, torch.int64, "visibility_counts")
+    opts.bkgd_counts = hip.dptr(background_counts, torch.int64, "background_counts")
+    opts.mismatch = hip.dptr(layer_mismatch, torch.int64, "layer_mismatch")
+    if background_grid is not None:   # (an entry whose bits are None is no grid)
+        opts.bkgd_grid = (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1)
+    if layer_caches is not None:
+        opts.layers = _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse))
     occ_out = None
     if occluder is not None:
         occ_out = (torch.empty(n, 5, dtype=torch.float32, device=dev), torch.empty(n, l, 5, dtype=torch.float32, device=dev),
                    torch.empty(n, 5, dtype=torch.float32, device=dev))
-    if layer_caches is not None or background_grid is not None or occluder is not None:
-        # (the widest entries share their argument checks and tables; stnerf_render_rays_layers is stnerf_render_rays_background
-        # plus the layer cache's table)
-        sampled = occupancy_samples is not None and any(occupancy_samples)
-        if sampled and (occupancy is None or len(occupancy_samples) != l):
-            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
-        for name, c in (("occupancy_counts", occupancy_counts), ("sample_counts", sample_counts), ("visibility_counts", visibility_counts)):
-            if c is not None and tuple(c.shape) != (l, 2):
-                raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
-        if background_counts is not None and tuple(background_counts.shape) != (2,):
-            raise ValueError(f"background_counts must be int64 (2,), got {tuple(background_counts.shape)}")
-        if layer_mismatch is not None and layer_mismatch.numel() < 1:
-            raise ValueError("layer_mismatch must hold one int64")
-        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
-        bg = None
-        if background_grid is not None:
-            bg = (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1)
-        shared = (*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
-                  _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
-                  _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
-                  hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
-                  None if terminate is None else _layer_flags(terminate, l, "terminate"),
-                  hip.dptr(visibility_counts, torch.int64, "visibility_counts"), bg,
-                  hip.dptr(background_counts, torch.int64, "background_counts"))
-        if occluder is not None:
-            lc = None if layer_caches is None else _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse))
-            hip.check(hip.lib().stnerf_render_rays_occluded(*shared, lc, hip.dptr(layer_mismatch, torch.int64, "layer_mismatch"),
-                                                            hip.dptr(occluder.contiguous(), name="occluder"), int(bool(occluder_stops)),
-                                                            hip.dptr(occ_out[0]), hip.dptr(occ_out[1]), hip.dptr(occ_out[2]), hip.stream_ptr()),
-                      "stnerf_render_rays_occluded")
-        elif layer_caches is not None:
-            hip.check(hip.lib().stnerf_render_rays_layers(*shared, _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse)),
-                                                          hip.dptr(layer_mismatch, torch.int64, "layer_mismatch"), hip.stream_ptr()),
-                      "stnerf_render_rays_layers")
-        else:
-            hip.check(hip.lib().stnerf_render_rays_background(*shared, hip.stream_ptr()), "stnerf_render_rays_background")
-    elif terminate is not None:       # (no flag set: the entry makes stnerf_render_rays_samples' launches)
-        sampled = occupancy_samples is not None and any(occupancy_samples)
-        if sampled and (occupancy is None or len(occupancy_samples) != l):
-            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
-        for name, c in (("occupancy_counts", occupancy_counts), ("sample_counts", sample_counts), ("visibility_counts", visibility_counts)):
-            if c is not None and tuple(c.shape) != (l, 2):
-                raise ValueError(f"{name} must be ({l},2), got {tuple(c.shape)}")
-        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
-        hip.check(hip.lib().stnerf_render_rays_terminated(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
-                                                          _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
-                                                          _layer_flags(occupancy_samples, l, "occupancy_samples") if sampled else None,
-                                                          hip.dptr(sample_counts, torch.int64, "sample_counts"), float(tau),
-                                                          _layer_flags(terminate, l, "terminate"),
-                                                          hip.dptr(visibility_counts, torch.int64, "visibility_counts"), hip.stream_ptr()),
-                  "stnerf_render_rays_terminated")
-    elif occupancy_samples is not None and any(occupancy_samples):
-        if occupancy is None or len(occupancy_samples) != l:
-            raise ValueError(f"occupancy_samples needs an occupancy table and one flag per layer ({l})")
-        if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):
-            raise ValueError(f"occupancy_counts must be ({l},2) int32, got {tuple(occupancy_counts.shape)}")
-        if sample_counts is not None and tuple(sample_counts.shape) != (l, 2):
-            raise ValueError(f"sample_counts must be ({l},2) int64, got {tuple(sample_counts.shape)}")
-        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
-        flags = (C.c_int32 * l)(*(int(bool(f)) for f in occupancy_samples))
-        hip.check(hip.lib().stnerf_render_rays_samples(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
-                                                       _occupancy_table(occupancy, l), hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"),
-                                                       flags, hip.dptr(sample_counts, torch.int64, "sample_counts"), hip.stream_ptr()),
-                  "stnerf_render_rays_samples")
-    elif occupancy is not None:
-        occ = _occupancy_table(occupancy, l)
-        if occupancy_counts is not None and tuple(occupancy_counts.shape) != (l, 2):
-            raise ValueError(f"occupancy_counts must be ({l},2) int32, got {tuple(occupancy_counts.shape)}")
-        table = None if layer_alpha is None else (C.c_float * l)(*(float(a) for a in layer_alpha))
-        hip.check(hip.lib().stnerf_render_rays_occupancy(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table, occ,
-                                                         hip.dptr(occupancy_counts, torch.int32, "occupancy_counts"), hip.stream_ptr()),
-                  "stnerf_render_rays_occupancy")
-    elif layer_alpha is not None:
-        table = (C.c_float * l)(*(float(a) for a in layer_alpha))
-        hip.check(hip.lib().stnerf_render_rays_opacity(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), table,
-                                                       hip.stream_ptr()), "stnerf_render_rays_opacity")
-    elif scene:
-        hip.check(hip.lib().stnerf_render_rays_scene(*args, None if bc is None else C.byref(bc), rot, hip.dptr(scene_out), hip.stream_ptr()),
-                  "stnerf_render_rays_scene")
-    elif rot is not None:
-        hip.check(hip.lib().stnerf_render_rays_rot(*args, None if bc is None else C.byref(bc), rot, hip.stream_ptr()), "stnerf_render_rays_rot")
-    elif bc is None:
-        hip.check(hip.lib().stnerf_render_rays(*args, hip.stream_ptr()), "stnerf_render_rays")
-    else:
-        hip.check(hip.lib().stnerf_render_rays_cached(*args, C.byref(bc), hip.stream_ptr()), "stnerf_render_rays_cached")
+        occluder = occluder.contiguous()
+        opts.occluder = hip.dptr(occluder, name="occluder")
+        opts.occluded_mixed, opts.occluded_scene, opts.occluder_share = (hip.dptr(t) for t in occ_out)
+    hip.check(hip.lib().stnerf_render_rays_opts(hip.dptr(rays, name="rays"), n, bp, bstride, C.byref(nets), C.byref(params),
+                                                hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
+                                                hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
+                                                hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8),
+                                                C.byref(opts), hip.stream_ptr()), "stnerf_render_rays")
     out = (mix_c, mix_c, lo_c, lo_c, mask) if params.only_coarse else (mix_f, mix_c, lo_f, lo_c, mask)
     out = out + (scene_out,) if scene else out
     return out + occ_out if occ_out is not None else out

@@ -118,7 +118,9 @@ def test_ctypes_structs_agree_with_the_c_compiler(tmp_path):
         pytest.skip("no gcc")
     pairs = {"stnerf_layer_edit": hip.LayerEdit, "stnerf_composite_params": hip.CompositeParams, "stnerf_nets": hip.Nets,
              "stnerf_render_params": hip.RenderParams, "stnerf_profile_record": hip.ProfileRecord, "stnerf_dw_problem": hip.DwProblem,
-             "stnerf_transpose_section": hip.TransposeSection}
+             "stnerf_transpose_section": hip.TransposeSection, "stnerf_render_options": hip.RenderOptions,
+             "stnerf_bkgd_cache": hip.BkgdCache, "stnerf_layer_cache": hip.LayerCache, "stnerf_occupancy": hip.Occupancy,
+             "stnerf_layer_rotation": hip.LayerRotation, "stnerf_stage_layer": hip.StageLayer, "stnerf_stage_rows": hip.StageRows}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "stnerf.h"', 'int main(void){']
     for cname, cls in pairs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
