@@ -29,7 +29,7 @@ __global__ void generate_rays_list_kernel(RayListArgs a, int w, int64_t n_pixels
     float cx = a.kinv[0] * u + a.kinv[1] * v + a.kinv[2];
     float cy = a.kinv[3] * u + a.kinv[4] * v + a.kinv[5];
     float cz = a.kinv[6] * u + a.kinv[7] * v + a.kinv[8];
-    const float nrm = sqrtf(cx * cx + cy * cy + cz * cz);
+    const float nrm = sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));  // torch.norm's order (utils/render_helpers.py:108)
     cx = cx / nrm;
     cy = cy / nrm;
     cz = cz / nrm;

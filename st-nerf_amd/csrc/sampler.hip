@@ -28,7 +28,9 @@ __global__ void generate_rays_kernel(RayGenArgs a, int w, RayWindow win, int64_t
     float cx = a.kinv[0] * u + a.kinv[1] * v + a.kinv[2];
     float cy = a.kinv[3] * u + a.kinv[4] * v + a.kinv[5];
     float cz = a.kinv[6] * u + a.kinv[7] * v + a.kinv[8];
-    const float nrm = sqrtf(cx * cx + cy * cy + cz * cz);
+    // torch.norm over the three components (utils/render_helpers.py:108) accumulates with fused multiply-adds, x first:
+    // sqrt(fma(z, z, fma(y, y, x x))).  The unfused sum differs from it in the last bit on about 1 ray in 300.
+    const float nrm = sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
     cx = cx / nrm;
     cy = cy / nrm;
     cz = cz / nrm;

@@ -2,6 +2,8 @@
 stnerf_accumulate, stnerf_accumulate_select): the pass schedule in fp64, rounded to fp32; the ray generator's operation order,
 Welford's update and the select rule in fp32 throughout, ONE operation per line, so that numpy rounds after every operation as
 the kernels (built without contraction) do.  Restated from the definitions, not from the package: nothing here imports it."""
+from fractions import Fraction
+
 import numpy as np
 
 F = np.float32
@@ -48,8 +50,35 @@ def layer_frame_ids(p, frame_ids, shutters, frame_range=None):
 
 
 # ---------------------------------------------------------------------------------------- rays of a pixel list (fp32)
+def _nearest_f32(x, candidates):
+    """The fp32 number nearest to the exact rational x among neighbouring fp32 candidates, ties to the even mantissa."""
+    best = min(candidates, key=lambda c: (abs(Fraction(float(c)) - x), int(np.asarray(c, F).view(np.uint32)) & 1))
+    return F(best)
+
+
+def fma32(a, b, c):
+    """fmaf(a, b, c) on fp32 arrays: a b + c rounded ONCE to fp32.  The float64 product of two fp32 numbers is exact; the float64 sum
+    rounds once to 53 bits, and rounding that again to 24 bits gives the wrong neighbour only where the float64 sum sits exactly
+    halfway between two fp32 numbers -- those elements are decided in exact rational arithmetic."""
+    a, b, c = (np.asarray(x, F) for x in np.broadcast_arrays(a, b, c))
+    s = a.astype(np.float64) * b.astype(np.float64)
+    s = s + c.astype(np.float64)
+    r = s.astype(F)
+    lo, hi = np.nextafter(r, F(-np.inf)), np.nextafter(r, F(np.inf))
+    half_lo = (r.astype(np.float64) + lo.astype(np.float64)) / 2.0        # midpoints of neighbouring fp32 numbers: exact in float64
+    half_hi = (r.astype(np.float64) + hi.astype(np.float64)) / 2.0
+    tie = np.isfinite(s) & ((s == half_lo) | (s == half_hi))
+    if tie.any():
+        r = r.copy()
+        for idx in zip(*np.nonzero(tie)):
+            exact = Fraction(float(a[idx])) * Fraction(float(b[idx])) + Fraction(float(c[idx]))
+            r[idx] = _nearest_f32(exact, (lo[idx], r[idx], hi[idx]))
+    return r
+
+
 def rays_of_pixels(kinv, T, w, pixels, du, dv, frame_ids=()):
-    """generate_rays_kernel's operation order with u = (float)(pix % w) + du, v = (float)(pix / w) + dv.  kinv (3,3), T (4,4) fp32."""
+    """generate_rays_kernel's operation order with u = (float)(pix % w) + du, v = (float)(pix / w) + dv; the squared norm is
+    fmaf(z, z, fmaf(y, y, x x)) as there (torch.norm's order).  kinv (3,3), T (4,4) fp32."""
     kinv, T = np.asarray(kinv, F).reshape(9), np.asarray(T, F).reshape(16)
     pix = np.asarray(pixels, np.int64)
     with np.errstate(all="ignore"):
@@ -64,10 +93,8 @@ def rays_of_pixels(kinv, T, w, pixels, du, dv, frame_ids=()):
             ab = a + b
             cam.append(ab + kinv[3 * r + 2])
         xx = cam[0] * cam[0]
-        yy = cam[1] * cam[1]
-        zz = cam[2] * cam[2]
-        s = xx + yy
-        s = s + zz
+        s = fma32(cam[1], cam[1], xx)
+        s = fma32(cam[2], cam[2], s)
         nrm = np.sqrt(s)
         cx = cam[0] / nrm
         cy = cam[1] / nrm

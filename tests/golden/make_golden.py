@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE's own code (build container only).
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py        # the base set
-    ... make_golden.py --round2 | --model-flags | --more-layers | --teacher | --psnr-view | --grads | --grads --teacher     # one group each;
+    ... make_golden.py --round2 | --model-flags | --more-layers | --teacher | --psnr-view | --grads | --grads --teacher | --real-counts     # one group each;
     every file regenerates byte for byte (--grads: train_c3 / train_coarse_only / train_c4 / train_flags / train_same_spacenet / train_bkgd_time,
     one iteration of the reference's do_train inner loop each, with the thread count pinned; --grads --teacher: train_tf_c3 and
     train_tf_trainer -- 2000 rays, 90 + 30 --, the same iteration with the fine depths and deformed points it ran on recorded)
@@ -18,6 +18,8 @@ The fixtures are the pin for ``oracle/stnerf_oracle.py`` (the reference has no g
 its own for this path).  ``/root/reference`` does not exist on the GPU box; nothing at test time
 reads it -- only these committed ``.npz`` files.
 """
+import contextlib
+import io
 import json
 import os
 import sys
@@ -300,6 +302,118 @@ def g_path():
     save("path", dict(C=int(gt_poses.shape[0]), L=2, frame_num=21), gt_poses=gt_poses, gt_Ks=torch.stack(gt_Ks, 0), **arrays)
 
 
+# ----------------------------------------------------------------------------- helpers of the --real-counts group
+PART_BYTES = 1000 * 1024          # below the size limit of a committed file (1 MiB)
+
+
+def _npz_bytes(out):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **out)
+    return buf.getvalue()
+
+
+def save_parts(name, meta, **arrays):
+    """``save`` for fixtures larger than a committed file may be: the arrays go, in their order, into name.npz, name.part2.npz, ...
+    each at most PART_BYTES; meta["parts"] says how many.  tests/golden_io.py puts them together again."""
+    out = {k: (v.detach().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    groups, size = [[]], 4096
+    for k, v in out.items():
+        b = len(_npz_bytes({k: v})) + 256
+        assert b <= PART_BYTES - 4096, (name, k, b)
+        if size + b > PART_BYTES and groups[-1]:
+            groups.append([])
+            size = 4096
+        groups[-1].append(k)
+        size += b
+    meta = dict(meta, parts=len(groups))
+    total = 0
+    for g, keys in enumerate(groups):
+        part = {k: out[k] for k in keys}
+        if g == 0:
+            part["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+        path = os.path.join(HERE, name + (".npz" if g == 0 else f".part{g + 1}.npz"))
+        data = _npz_bytes(part)
+        assert len(data) <= 1 << 20, (path, len(data))
+        with open(path, "wb") as f:
+            f.write(data)
+        total += len(data)
+    print(f"wrote {name}.npz in {len(groups)} part(s), {total} B ({sum(a.nbytes for a in out.values())} B raw)")
+
+
+def spare_rays(h, w, orbit):
+    """Rays that are in no h x w view of this camera position: the first rows of a view four rows taller."""
+    K, T = syn.camera(h + 4, w, orbit)
+    return ref_utils.generate_rays(K, T, None, h + 4, w)[0]
+
+
+class TieWatch:
+    """While active: the rows (of the whole call, over its reference chunks) on which a merged depth list -- a torch.sort over all
+    rays of a chunk and more than one layer's samples -- holds two EXACTLY equal depths (see rays_with_depth_ties)."""
+
+    def __init__(self, model, per_layer):
+        self.model, self.per_layer, self.offset, self.rows, self.found, self.sorts = model, per_layer, 0, 0, set(), 0
+
+    def __enter__(self):
+        self._orig = torch.sort
+
+        def start(module, inputs):
+            self.offset, self.rows = self.offset + self.rows, inputs[0].shape[0]
+
+        def sort(*a, **k):
+            out = self._orig(*a, **k)
+            v = out[0]
+            if v.dim() == 3 and v.shape[-1] == 1:
+                v = v[..., 0]
+            if v.dim() == 2 and v.shape[0] == self.rows and v.shape[1] > self.per_layer:
+                tie = ((v[:, 1:] == v[:, :-1]) & (v[:, 1:] > -999.0)).any(-1)
+                self.found.update((tie.nonzero().flatten() + self.offset).tolist())
+                self.sorts += 1
+            return out
+        self._hook = self.model.register_forward_pre_hook(start)
+        torch.sort = sort
+        return self
+
+    def __exit__(self, *exc):
+        torch.sort = self._orig
+        self._hook.remove()
+
+    def tied_rows(self):
+        assert self.sorts >= 1, "no merged list was sorted"
+        return sorted(self.found)
+
+
+def swap_tied_rays(name, rays, first, run, spare):
+    """Replace the (origin, direction) of every ray with an exact depth tie by the next spare ray (the frame-id columns stay the
+    row's own) and run again, until no tie is left; at most 0.5 % of the rays.  -> (rays, out, draws, [(row, spare index)])."""
+    out, rr, tied = first
+    swapped, nxt = [], 0
+    for _ in range(20):
+        if not tied:
+            break
+        rays = rays.clone()
+        for r in tied:
+            rays[r, :6] = spare[nxt]
+            swapped.append((int(r), nxt))
+            nxt += 1
+        out, rr, tied = run(rays)
+    else:
+        raise RuntimeError("depth ties keep turning up")
+    print(f"{name}: {len(swapped)} of {rays.shape[0]} rays with exact depth ties replaced: {swapped}")
+    assert len(swapped) <= 0.005 * rays.shape[0], (name, len(swapped))
+    return rays, out, rr, swapped
+
+
+def check_real_counts(name, out, n, swapped):
+    """What a --real-counts fixture must show to be worth committing: every performer layer hit by at least 8 rays, something
+    composited, no more than 0.5 % of the rays swapped for depth ties."""
+    masks = out[4]
+    hits = [int(mk.sum()) for mk in masks[1:]]
+    print(f"{name}: rays hit per performer layer {hits} of {n}; fine mixed acc max {float(out[0][2].max()):.3f}")
+    assert min(hits) >= 8, (name, hits)
+    assert float(out[0][2].max()) > 0.1
+    assert len(swapped) <= 0.005 * n
+
+
 # ----------------------------------------------------------------------------- whole-path fixtures
 def build_ref_model(L, n1, n2, st, dt, seed, flags=None):
     flags = flags or {}
@@ -312,7 +426,12 @@ def build_ref_model(L, n1, n2, st, dt, seed, flags=None):
 
 
 def g_forward(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, per_ray_frames=False, edit=None,
-              call_kwargs=None, chunk=None, only_coarse=False, flags=None, bkgd_frame=1.0, extra_rays=None):
+              call_kwargs=None, chunk=None, only_coarse=False, flags=None, bkgd_frame=1.0, extra_rays=None,
+              chunk_frames=None, row_frames=None, orbit=20.0, real_counts=False):
+    """``chunk_frames``: one tuple of performer frame ids per reference chunk (written to every row of that chunk);
+    ``row_frames``: {row: {column: id}} single entries on top.  ``real_counts`` (the --real-counts group): seeded draws (stored as
+    seeds and shapes), rays with an exact depth tie in a merged list swapped out, the conditions of ``check_real_counts`` asserted
+    and the file split into parts below the size limit of a committed file."""
     model = build_ref_model(L, n1, n2, st, dt, seed, flags)
     edit = edit or {}
     for k in ("scale", "shift", "alpha", "near"):
@@ -320,30 +439,51 @@ def g_forward(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, per_ray_frames=Fal
             setattr(model, k, edit[k])
     for i in edit.get("hide", []):
         model.hide_layer(i)
-    rays = view_rays(h, w, L, frame=frame, per_ray_frames=per_ray_frames, bkgd_frame=bkgd_frame)
+    rays = view_rays(h, w, L, orbit=orbit, frame=frame, per_ray_frames=per_ray_frames, bkgd_frame=bkgd_frame)
     if extra_rays is not None:      # hand-made (origin, direction) rows appended to the view
         ex = torch.tensor(extra_rays, dtype=torch.float32)
         rays = torch.cat([rays, torch.cat([ex, syn.frame_id_columns(ex.shape[0], L, frame, bkgd_frame)], -1)], 0)
     n = rays.shape[0]
+    if chunk_frames is not None:    # every reference chunk with frame ids of its own (its boxes follow its row 0)
+        assert chunk is not None and len(chunk_frames) == -(-n // chunk)
+        for c, ids in enumerate(chunk_frames):
+            rays[c * chunk:(c + 1) * chunk, 7:7 + len(ids)] = torch.tensor(ids, dtype=torch.float32)
+    for row, cols in (row_frames or {}).items():
+        for col, fid in cols.items():
+            rays[int(row), 6 + int(col)] = float(fid)
     labels, bb, nf = torch.zeros(n), torch.zeros(n, 8, 3), torch.zeros(n, 2)
     kw = dict(call_kwargs or {})
-    torch.manual_seed(100 + seed)
-    with RandRecorder() as rr, torch.no_grad():
-        if chunk is None:
-            out = model(rays, labels, bb, only_coarse=only_coarse, near_far=nf, **kw)
-        else:
-            out = ref_utils.layered_batchify_ray(model, rays, labels, bb, chuncks=chunk, near_far=nf, **kw)
+
+    def run(rays):
+        torch.manual_seed(100 + seed)
+        watch = TieWatch(model, n1 + n2) if real_counts else contextlib.nullcontext()
+        with (SeededDraws(7000 + 100 * seed) if real_counts else RandRecorder()) as rr, watch, torch.no_grad():
+            if chunk is None:
+                out = model(rays, labels, bb, only_coarse=only_coarse, near_far=nf, **kw)
+            else:
+                out = ref_utils.layered_batchify_ray(model, rays, labels, bb, chuncks=chunk, near_far=nf, **kw)
+        return out, rr, (watch.tied_rows() if real_counts else [])
+
+    swapped = []
+    out, rr, tied = run(rays)
+    if real_counts:
+        rays, out, rr, swapped = swap_tied_rays(name, rays, (out, rr, tied), run, spare_rays(h, w, orbit))
     meta = dict(L=L, n1=n1, n2=n2, space_time=st, deform_time=dt, weight_seed=seed, h=h, w=w,
                 edit={k: v for k, v in edit.items()}, call_kwargs=kw, chunk=chunk, only_coarse=only_coarse,
                 n_draws=len(rr.draws), flags=dict(flags or {}))
     arrays = flatten_out(out)
+    if real_counts:
+        meta.update(orbit=orbit, draw_seed_base=rr.base, draw_shapes=rr.shapes, swapped_rays=swapped)
+        check_real_counts(name, out, n, swapped)
+        save_parts(name, meta, rays=rays, **arrays)
+        return
     for i, dr in enumerate(rr.draws):
         arrays[f"draw{i}"] = dr
     save(name, meta, rays=rays, **arrays)
 
 
 # ----------------------------------------------------------------------------- teacher-forced fine stage
-def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, edit=None):
+def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, edit=None, real_counts=False):
     """The reference's OWN intermediates of one forward call (one chunk), so that the fine stage of the HIP path can be fed
     the reference's fine samples instead of its own (a last-ulp cdf difference moves a fine sample through the
     ``den < 1e-5`` switch of utils/sample_pdf.py:59 and, times 2^9 in the encoding, moves a pixel: with the reference's
@@ -357,7 +497,9 @@ def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, 
     * ``raw_rgb_fine{i}`` / ``raw_sigma_fine{i}``: the fine SpaceNet's outputs as returned (before thresholds / alpha);
     * ``xyz_fine_post{i}`` / ``density_fine_post{i}``: the stashes of :610-611 (after deformation / after the density edits);
     * ``coarse_weights{i}``: the per-layer coarse weights (:437-444), whole rows;
-    plus the rays, every draw and all final outputs (same keys as the fwd_* fixtures)."""
+    plus the rays, every draw and all final outputs (same keys as the fwd_* fixtures).  ``real_counts``: as in g_forward (the draws
+    and the ``u{i}``, which are draws, stored as seeds and shapes; ``xyz_fine_post`` / ``density_fine_post``, which no test reads,
+    left out)."""
     import modeling.layered_rfrender as lr
     model = build_ref_model(L, n1, n2, st, dt, seed)
     edit = edit or {}
@@ -398,19 +540,35 @@ def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, 
         handles.append(model.spacenets_fine[i].register_forward_hook(hook(f"space{i + 1}")))
         if dt:
             handles.append(model.time_deform_nets[i].register_forward_hook(hook(f"motion{i + 1}")))
-    torch.manual_seed(100 + seed)
-    lr.sample_pdf, torch.sort, model.volume_render.forward = pdf, sort, vr
+    def run(rays):
+        for store in (rec["pdf"], rec["sorts"], rec["weights"]):
+            store.clear()
+        calls.clear()
+        torch.manual_seed(100 + seed)
+        lr.sample_pdf, torch.sort, model.volume_render.forward = pdf, sort, vr
+        try:
+            with (SeededDraws(7000 + 100 * seed) if real_counts else RandRecorder()) as rr, torch.no_grad():
+                out = model(rays, labels, bb, near_far=nf, **kw)
+        finally:
+            lr.sample_pdf, torch.sort, model.volume_render.forward = orig_pdf, orig_sort, orig_vr
+        merged = [x[..., 0] if x.dim() == 3 else x for x in rec["sorts"] if x.shape[0] == n and x.dim() >= 2 and x.shape[1] > S]
+        assert len(merged) == 2, [tuple(x.shape) for x in rec["sorts"]]
+        tied = [((v[:, 1:] == v[:, :-1]) & (v[:, 1:] > -999.0)).any(-1) for v in merged]
+        return out, rr, (tied[0] | tied[1]).nonzero().flatten().tolist()
+
+    swapped = []
     try:
-        with RandRecorder() as rr, torch.no_grad():
-            out = model(rays, labels, bb, near_far=nf, **kw)
+        out, rr, tied = run(rays)
+        if real_counts:
+            rays, out, rr, swapped = swap_tied_rays(name, rays, (out, rr, tied), run, spare_rays(h, w, 20.0))
     finally:
-        lr.sample_pdf, torch.sort, model.volume_render.forward = orig_pdf, orig_sort, orig_vr
         for hd in handles:
             hd.remove()
     masks = out[4]
     arrays = flatten_out(out)
-    for i, dr in enumerate(rr.draws):
-        arrays[f"draw{i}"] = dr
+    if not real_counts:
+        for i, dr in enumerate(rr.draws):
+            arrays[f"draw{i}"] = dr
     assert len(rec["pdf"]) == l and len(rr.draws) == 2 * l
     fine_sorts = [x for x in rec["sorts"] if x.dim() == 2 and x.shape == (n, S)]
     assert len(fine_sorts) == l, [tuple(x.shape) for x in rec["sorts"]]
@@ -418,12 +576,14 @@ def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, 
     for i in range(l):
         t_c, w_c, z = rec["pdf"][i]
         arrays[f"pdf_t{i}"], arrays[f"pdf_w{i}"], arrays[f"pdf_z{i}"] = t_c, w_c, z
-        arrays[f"u{i}"] = rr.draws[l + i]
+        if not real_counts:
+            arrays[f"u{i}"] = rr.draws[l + i]
         arrays[f"z_vals_fine{i}"] = fine_sorts[i]
         arrays[f"coarse_weights{i}"] = rec["weights"][i].reshape(n, n1)
         assert torch.equal(arrays[f"coarse_weights{i}"][:, 1:-1], w_c)
-        arrays[f"xyz_fine_post{i}"] = model.xyz_fine_temp[i]
-        arrays[f"density_fine_post{i}"] = model.density_fine_temp[i]
+        if not real_counts:
+            arrays[f"xyz_fine_post{i}"] = model.xyz_fine_temp[i]
+            arrays[f"density_fine_post{i}"] = model.density_fine_temp[i]
         idx = masks[i] if i > 0 else torch.ones(n, dtype=torch.bool)
         pre = torch.zeros(n, S, 3)
         rgb, sig = torch.zeros(n, S, 3), torch.zeros(n, S, 1)
@@ -442,6 +602,11 @@ def g_teacher(name, L, n1, n2, st, dt, seed, h, w, frame=2.5, call_kwargs=None, 
         arrays[f"xyz_fine_pre{i}"], arrays[f"raw_rgb_fine{i}"], arrays[f"raw_sigma_fine{i}"] = pre, rgb, sig
     meta = dict(L=L, n1=n1, n2=n2, space_time=st, deform_time=dt, weight_seed=seed, h=h, w=w, edit=dict(edit), call_kwargs=kw,
                 chunk=None, only_coarse=False, n_draws=len(rr.draws), flags={}, frame=frame)
+    if real_counts:
+        meta.update(draw_seed_base=rr.base, draw_shapes=rr.shapes, swapped_rays=swapped)
+        check_real_counts(name, out, n, swapped)
+        save_parts(name, meta, rays=rays, **arrays)
+        return
     save(name, meta, rays=rays, **arrays)
 
 
@@ -809,7 +974,62 @@ def g_train_teacher_cases():
 
 
 
+def g_generate_rays_views():
+    """Ray generation at production view sizes, where the order of the norm's sum shows: (a) the whole 270 x 480 view, (b) a seeded
+    list of 32,768 pixels of a 1080p view.  The origin (T[:3, 3] on every row) is stored once; the directions of (a) in row blocks."""
+    arrays, meta = {}, {}
+    for tag, (h, w, orbit) in dict(a=(270, 480, 17.0), b=(1080, 1920, 20.0)).items():
+        K, T = syn.camera(h, w, orbit)
+        rays, _ = ref_utils.generate_rays(K, T, None, h, w)
+        assert torch.equal(rays[:, :3], T[:3, 3].expand(h * w, 3))
+        # how many rays tell ATen's norm from an unfused one: utils/render_helpers.py:95-114 again, with sqrt(x x + y y + z z) at :108
+        gx, gy = torch.meshgrid(torch.linspace(0, h - 1, steps=h), torch.linspace(0, w - 1, steps=w), indexing="ij")
+        cam = torch.matmul(torch.inverse(K), torch.stack([gy, gx, torch.ones(h, w)], -1).unsqueeze(-1))        # (h, w, 3, 1)
+        assert torch.equal(torch.matmul(T, torch.cat([cam / torch.norm(cam, dim=2, keepdim=True), torch.zeros(h, w, 1, 1)], 2))[:, :, :3, 0]
+                           .reshape(-1, 3), rays[:, 3:6])
+        unfused = torch.sqrt(cam[:, :, 0:1] * cam[:, :, 0:1] + cam[:, :, 1:2] * cam[:, :, 1:2] + cam[:, :, 2:3] * cam[:, :, 2:3])
+        other = torch.matmul(T, torch.cat([cam / unfused, torch.zeros(h, w, 1, 1)], 2))[:, :, :3, 0].reshape(-1, 3)
+        differ = (other != rays[:, 3:6]).any(1)
+        if tag == "b":
+            pix = torch.from_numpy(np.sort(np.random.RandomState(54).choice(h * w, size=32768, replace=False)).astype(np.int32))
+            rays, differ = rays[pix.long()], differ[pix.long()]
+            arrays["pixels_b"] = pix
+        print(f"generate_rays_views {tag}: {h} x {w}, {rays.shape[0]} rays, {int(differ.sum())} of them differ in a bit of their direction under an unfused norm")
+        meta[f"h_{tag}"], meta[f"w_{tag}"], meta[f"orbit_{tag}"], meta[f"norms_differ_{tag}"] = h, w, orbit, int(differ.sum())
+        arrays[f"K_{tag}"], arrays[f"T_{tag}"] = K, T
+        blocks = 2 if tag == "a" else 1
+        meta[f"blocks_{tag}"] = blocks
+        for b, rows in enumerate(torch.chunk(rays[:, 3:6], blocks, 0)):
+            arrays[f"dirs_{tag}{b}"] = rows
+    assert meta["norms_differ_a"] + meta["norms_differ_b"] >= 100
+    save_parts("generate_rays_views", meta, **arrays)
+
+
+def g_real_counts():
+    """--real-counts: the BASELINE configurations C1, C4 and C5 at their OWN sample and layer counts, the chunked call at its
+    default chunk with thresholds and per-chunk frame ids, and ray generation at production view sizes."""
+    # C1: one performer, space-time only, 32 + 0 through the full forward, 4096 rays = two reference chunks
+    g_forward("fwd_c1_full", 1, 32, 0, True, False, 50, 64, 64, chunk=3584, real_counts=True)
+    # C4: four performers, deformation only, 64 + 64
+    g_forward("fwd_c4_64_64", 4, 64, 64, False, True, 51, 6, 12, real_counts=True)
+    g_teacher("tf_c4_64_64", 4, 64, 64, False, True, 51, 6, 12, real_counts=True)
+    # C5: eight performers, 128 + 64 (seed 58: with 9 x 192 depths per ray about one ray in 64 has an exact tie, and one ray is more
+    # than 0.5 % of this view -- seeds 52, 56, 57 and 60 each gave one, 58 and 59 none)
+    g_forward("fwd_c5_128_64", 8, 128, 64, False, True, 58, 4, 16, call_kwargs=dict(density_threshold=0.05), real_counts=True)
+    g_teacher("tf_c5_128_64", 8, 128, 64, False, True, 58, 4, 16, call_kwargs=dict(density_threshold=0.05), real_counts=True)
+    # layered_batchify_ray's chunked branch at its default chunk, with both thresholds: 7200 rays = 3584 + 3584 + 32; every chunk
+    # with performer frame ids of its own (its boxes follow ITS row 0, modeling/layered_rfrender.py:195-200), and one ray that is no
+    # row 0 with an id of its own (its time input follows, its box does not)
+    g_forward("batchify_default_chunk", 2, 12, 6, True, True, 53, 90, 80, chunk=3584,
+              call_kwargs=dict(density_threshold=0.05, bkgd_density_threshold=0.02),
+              chunk_frames=[(2.5, 2.5), (1.0, 2.75), (3.0, 1.5)], row_frames={4000: {1: 3.0}}, real_counts=True)
+    g_generate_rays_views()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--real-counts":
+        g_real_counts()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--psnr-view":
         g_psnr_view()
         return

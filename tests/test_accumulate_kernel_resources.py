@@ -58,7 +58,8 @@ def test_the_accumulate_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
     # test's check (no fused multiply-add at all) needs one allowance here: a correctly rounded fp32 quotient and square root are
     # themselves EXPANDED into fused operations (the ray generator divides three times and takes one root, the accumulator
     # divides once).  So a probe kernel of one quotient and one of one root are compiled with the same flags, and every kernel
-    # must hold exactly the fused operations of its quotients and roots -- one more would be a contracted product of ours
+    # must hold exactly the fused operations of its quotients and roots -- one more would be a contracted product of ours.  The ray
+    # generator adds the two fmaf it WRITES: the squared norm in torch.norm's order, fmaf(z, z, fmaf(y, y, x x))
     probe = tmp_path / "probe.hip"
     probe.write_text("#include <hip/hip_runtime.h>\n"
                      "__global__ void probe_div(const float* a, const float* b, float* o) { o[threadIdx.x] = a[threadIdx.x] / b[threadIdx.x]; }\n"
@@ -82,6 +83,7 @@ def test_the_accumulate_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
         want = next((v for k, v in expected.items() if k in name), (0, 0))
         print(f"{name}: {n_fused} fused operations, {n_div} quotients, {n_sqrt} roots")
         assert (n_div, n_sqrt) == want, (name, n_div, n_sqrt)
-        assert n_fused == per_div * n_div + per_sqrt * n_sqrt, (name, n_fused, per_div, per_sqrt)
+        written = 2 if "generate_rays_list_kernel" in name else 0
+        assert n_fused == per_div * n_div + per_sqrt * n_sqrt + written, (name, n_fused, per_div, per_sqrt, written)
     from stnerf_amd import build
     assert ("accumulate.hip", ["-ffp-contract=off"]) in [(s, f) for s, f in build.SOURCES]

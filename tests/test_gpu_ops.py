@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from golden_io import load_golden, load_ray_views
 from oracle import stnerf_oracle as O
 from stnerf_amd import synthetic as syn
 
@@ -41,17 +41,33 @@ def test_device_is_gfx950():
 
 
 def test_generate_rays(ops):
+    """Bit for bit the reference's rays (utils/render_helpers.py:42-128): the norm is ATen's fused sum, sqrt(fma(z, z, fma(y, y, x x)))."""
     meta, a = load_golden("generate_rays")
     h, w = meta["h"], meta["w"]
     rays = ops.generate_rays(a["K"], a["T"], h, w, frame_ids=[1.0, 2.5, 3.0])
     assert rays.shape == (h * w, 9)
-    torch.testing.assert_close(rays[:, :6].cpu(), a["rays"], rtol=0, atol=1e-6)
+    assert torch.equal(rays[:, :6].cpu(), a["rays"])
     assert torch.equal(rays[:, 6:].cpu(), torch.tensor([1.0, 2.5, 3.0]).repeat(h * w, 1))
+    # production view sizes (generate_rays_views: at least 100 rays on which an unfused norm differs in the last bit)
+    views = load_ray_views()
+    assert sum(v["norms_differ"] for v in views.values()) >= 100
+    va, vb = views["a"], views["b"]
+    whole = ops.generate_rays(va["K"], va["T"], va["h"], va["w"]).cpu()
+    print(f"270 x 480 view: {int((whole != va['rays']).any(1).sum())} of {whole.shape[0]} rays differ from the reference's")
+    assert torch.equal(whole, va["rays"])
+    # the pixel list of the 1080p view: through pixels= (the listed generator) and through first_ray / n windows (the plain one)
+    pix = vb["pixels"]
+    listed = ops.generate_rays(vb["K"], vb["T"], vb["h"], vb["w"], pixels=pix.cuda()).cpu()
+    print(f"1080p pixel list: {int((listed != vb['rays']).any(1).sum())} of {listed.shape[0]} rays differ from the reference's")
+    assert torch.equal(listed, vb["rays"])
+    lo, hi = int(pix[0]), int(pix[-1]) + 1                                  # (the list is sorted)
+    window = ops.generate_rays(vb["K"], vb["T"], vb["h"], vb["w"], first_ray=lo, n=hi - lo).cpu()
+    assert torch.equal(window[pix.long() - lo], vb["rays"])
     # a window of a large view == the same rows of the oracle's full view
     K, T = syn.camera(270, 480, 17.0)
     full = O.generate_rays(K, T, 270, 480)
     part = ops.generate_rays(K, T, 270, 480, first_ray=1000, n=5000)
-    torch.testing.assert_close(part.cpu(), full[1000:6000], rtol=0, atol=1e-6)
+    assert torch.equal(part.cpu(), full[1000:6000])
 
 
 def test_sampler_golden_bit_exact(ops):

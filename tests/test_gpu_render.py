@@ -22,13 +22,16 @@ import types
 import pytest
 import torch
 
-from conftest import load_golden
+from golden_io import load_golden
 from stnerf_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
 FWD_CASES = ["fwd_c1", "fwd_c3", "fwd_edit", "fwd_hide", "fwd_nonretime", "fwd_only_coarse",
-             "batchify_chunked", "batchify_small", "fwd_bkgd_time", "fwd_bkgd_time_mixed_ids", "fwd_same_spacenet", "fwd_deep_rgb", "fwd_no_raw_no_dir", "fwd_c4", "fwd_c5"]
+             "batchify_chunked", "batchify_small", "fwd_bkgd_time", "fwd_bkgd_time_mixed_ids", "fwd_same_spacenet", "fwd_deep_rgb", "fwd_no_raw_no_dir", "fwd_c4", "fwd_c5",
+             # BASELINE C1 / C4 / C5 at their own sample and layer counts (32 + 0 over two reference chunks, L = 4 at 64 + 64, L = 8 at
+             # 128 + 64), and the chunked call at its default chunk of 3584 with thresholds and frame ids of its own in every chunk
+             "fwd_c1_full", "fwd_c4_64_64", "fwd_c5_128_64", "batchify_default_chunk"]
 COLOR_ATOL, DEPTH_ATOL = 5e-5, 5e-4
 
 
@@ -188,6 +191,49 @@ def run_forward_case(name, precision):
             bars.append(fine_stage_bar(g, a[k], exact[k], tol, f"{name}/{k}"))
     print(f"{name}: max abs err vs the reference " + ", ".join(f"{k}={v:.2e}" for k, v in worst.items())
           + (f"; fine-stage rays above tol vs fp64 (HIP / reference): {sum(b[0] for b in bars)} / {sum(b[1] for b in bars)}" if bars else ""))
+
+
+def composite_plan(l, S, scratch=True):
+    """stnerf_composite_plan -> dict(staged, single, tiers, cap, clear): what the compositor launches for l layers of S samples."""
+    import ctypes as C
+    from stnerf_amd import hip
+    out = (C.c_int64 * 9)()
+    hip.check(hip.lib().stnerf_composite_plan(l, S, int(scratch), 0, out), "stnerf_composite_plan")
+    return dict(zip(("staged", "single", "tiers", "cap", "clear"), list(out)[:5]))
+
+
+@pytest.mark.parametrize("name", ["fwd_c4_64_64", "fwd_c5_128_64"])
+def test_real_count_cases_launch_what_they_are_there_for(name):
+    """The real-count fixtures reach the code the miniatures (10 + 6, 12 + 4) never run.  The launch records name a kernel family,
+    the rays and the samples per layer of every launch, not a template instantiation: the records show that the stages ran at the
+    fixture's counts, and the instantiation follows from the launch plan (stnerf_composite_plan, the function the launch itself
+    consults with the scratch bytes the pipeline lends it) and from the resampler's dispatch on (n1, n2)."""
+    from stnerf_amd import ops
+    meta, a = load_golden(name)
+    l, n1, S, n = meta["L"] + 1, meta["n1"], meta["n1"] + meta["n2"], a["rays"].shape[0]
+    model = build_model(meta).set_precision("fp32")
+    model.replay = assemble_replay(meta, a, n)
+    ops.profile_begin()
+    try:
+        with torch.no_grad():
+            model(a["rays"].cuda(), None, None, **meta["call_kwargs"])
+        torch.cuda.synchronize()
+    finally:
+        recs = [(r["kernel"], r["n_rays"], r["ns"]) for r in ops.profile_end()]
+    assert ("sample_coarse", n, n1) in recs and ("resample", n, S) in recs, recs
+    assert ("composite", n, n1) in recs and ("composite", n, S) in recs, recs
+    assert all(ns in (n1, S) for k, _, ns in recs if k == "mlp_stage") and any(k == "mlp_stage" and ns == S for k, _, ns in recs), recs
+    coarse, fine = composite_plan(l, n1), composite_plan(l, S)
+    print(f"{name}: composite plan coarse {coarse}, fine {fine}; launches {sorted(set(recs))}")
+    assert not coarse["staged"] and not fine["staged"]                 # the register / insertion-merge kernels: S = 64 nblk, `full`
+    assert S % 64 == 0 and S // 64 == (2 if name == "fwd_c4_64_64" else 3)
+    if name == "fwd_c4_64_64":
+        assert fine["single"] == 2 and fine["tiers"] == 1 and fine["cap"] == l          # composite_single_kernel<3, 24>, one merge launch
+    else:
+        assert fine["tiers"] == 2 and fine["cap"] == 4 and fine["single"] == 2          # 9 x 192: lists of four layers first, then of nine
+        assert fine["cap"] < l
+    # the resampler's compile-time flavour (csrc/resample.hip: n2 = 64 and n1 = 64 | 128, device draws, no debug outputs, no edits)
+    assert meta["n2"] == 64 and n1 == (64 if name == "fwd_c4_64_64" else 128) and not meta["edit"]
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])

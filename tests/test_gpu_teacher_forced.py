@@ -19,12 +19,13 @@ Both arithmetics (bf16x3 = the library default, exact f32).  Needs an MI355X: `p
 import pytest
 import torch
 
-from conftest import load_golden
+from golden_io import load_golden
 from stnerf_amd import synthetic as syn
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["tf_c3_64_64", "tf_c3_90_30", "tf_c4", "tf_c5", "tf_edit"]
+CASES = ["tf_c3_64_64", "tf_c3_90_30", "tf_c4", "tf_c5", "tf_edit",
+         "tf_c4_64_64", "tf_c5_128_64"]        # BASELINE C4 / C5 at their own counts: L = 4 at 64 + 64, L = 8 at 128 + 64
 COLOR_ATOL, DEPTH_ATOL = 5e-5, 5e-4            # the stated fp32 tolerance of the path (tests/test_gpu_render.py)
 # network outputs against the reference's fp32 evaluation (both sides round: twice the vs-fp64 bar of tests/test_gpu_stage.py)
 NET_RTOL, NET_ATOL_RGB, NET_ATOL_SIGMA = 4e-5, 4e-5 * 4.0, 4e-5 * 60.0
@@ -101,6 +102,32 @@ def test_resampler_on_reference_coarse_outputs_is_bit_equal(ops, name):
         assert torch.equal(tf[rows, i], a[f"z_vals_fine{i}"][rows]), f"layer {i}: sorted fine depths differ"
         hit = mask[:, i].bool() if i else rows
         assert torch.equal(xyz[hit, i], a[f"xyz_fine_pre{i}"][hit]), f"layer {i}: fine sample points differ"
+
+
+@pytest.mark.parametrize("name", ["tf_c3_64_64", "tf_c4_64_64", "tf_c5_128_64"])
+def test_compile_time_resampler_equals_the_pinned_flavour_on_reference_coarse_outputs(ops, name):
+    """resample_kernel<1, true, true> / <2, true, true> (n2 = 64, n1 = 64 | 128 as compile-time constants) run only on the production
+    call -- device draws, no debug outputs -- so no recorded draw can be replayed into them.  The flavour the test above holds to the
+    reference bit for bit draws the same numbers from the same seed: on the reference's own coarse depths and weights, at L = 2, 4
+    and 8, both give the same depths and points, bit for bit.  (The launch records name the kernel family and the sample counts,
+    not the instantiation; which one runs follows from csrc/resample.hip's dispatch on (n1, n2) and the absent options.)"""
+    meta, a, l, stack, mask = _load(name)
+    n1, n2 = meta["n1"], meta["n2"]
+    assert n2 == 64 and n1 in (64, 128) and _edits(meta, l) is None
+    t, w, rays = dev(stack("pdf_t")), dev(stack("coarse_weights")), dev(a["rays"])
+    ops.profile_begin()
+    try:
+        tf_a, xyz_a = ops.resample(t, w, n2, rays, seed=4321, ray_index_base=5)
+        torch.cuda.synchronize()
+    finally:
+        recs = [(r["kernel"], r["n_rays"], r["ns"]) for r in ops.profile_end()]
+    assert recs == [("resample", a["rays"].shape[0], n1 + n2)], recs
+    tf_b, xyz_b, z_b, _, _ = ops.resample(t, w, n2, rays, seed=4321, ray_index_base=5, debug=True)
+    live = mask.bool().clone()
+    live[:, 0] = True
+    live = live.cuda()
+    assert torch.equal(tf_a[live], tf_b[live]) and torch.equal(xyz_a[live], xyz_b[live])
+    assert bool((tf_a[live][:, 1:] >= tf_a[live][:, :-1]).all()) and float(z_b[live].std()) > 0.01
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "fp32"])

@@ -4,19 +4,29 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from golden_io import load_golden, load_ray_views
 from oracle import stnerf_oracle as O
 from stnerf_amd import synthetic as syn
 
 FWD_CASES = ["fwd_c1", "fwd_c3", "fwd_edit", "fwd_hide", "fwd_nonretime", "fwd_only_coarse",
              "batchify_chunked", "batchify_small", "fwd_bkgd_time", "fwd_same_spacenet", "fwd_deep_rgb", "fwd_no_raw_no_dir", "fwd_c4", "fwd_c5",
-             "fwd_c3_90_30", "fwd_c3_90_30_chunked", "fwd_c3_64_64", "fwd_grazing", "fwd_bkgd_time_mixed_ids"]
+             "fwd_c3_90_30", "fwd_c3_90_30_chunked", "fwd_c3_64_64", "fwd_grazing", "fwd_bkgd_time_mixed_ids",
+             # the BASELINE configurations at their own sample and layer counts, and the chunked call at its default chunk
+             "fwd_c1_full", "fwd_c4_64_64", "fwd_c5_128_64", "batchify_default_chunk", "tf_c4_64_64", "tf_c5_128_64"]
+TF_ONLY = ("pdf_", "u", "z_vals_fine", "coarse_weights", "xyz_fine_", "density_fine_", "raw_")   # a tf_ fixture's intermediates
 
 
 def test_generate_rays():
     meta, a = load_golden("generate_rays")
     rays = O.generate_rays(a["K"], a["T"], meta["h"], meta["w"])
     assert torch.equal(rays, a["rays"])
+    # production view sizes, where the order of torch.norm's sum shows (fused, x first): a whole 270 x 480 view and a pixel list of
+    # a 1080p view, with at least 100 rays on which the unfused order gives another norm
+    views = load_ray_views()
+    assert sum(v["norms_differ"] for v in views.values()) >= 100
+    for v in views.values():
+        rays = O.generate_rays(v["K"], v["T"], v["h"], v["w"])
+        assert torch.equal(rays if v["pixels"] is None else rays[v["pixels"].long()], v["rays"])
 
 
 def test_sampler_bit_exact():
@@ -133,8 +143,9 @@ def _flatten(out):
     return d
 
 
-@pytest.mark.parametrize("name", FWD_CASES)
-def test_forward_matches_reference(name):
+def _compare_with_reference(name, batchify=None):
+    """Render fixture ``name`` with the oracle and hold every output to the reference's.  ``batchify``: a stand-in for
+    O.layered_batchify_ray (the tests that show a fixture can fail)."""
     meta, a = load_golden(name)
     m = _model_from_meta(meta)
     draws = [a[f"draw{i}"] for i in range(meta["n_draws"])]
@@ -144,9 +155,9 @@ def test_forward_matches_reference(name):
         if meta["chunk"] is None:
             out = O.render_chunk(m, a["rays"], only_coarse=meta["only_coarse"], rand=rand, **kw)
         else:
-            out = O.layered_batchify_ray(m, a["rays"], chuncks=meta["chunk"], rand=rand, **kw)
+            out = (batchify or O.layered_batchify_ray)(m, a["rays"], chuncks=meta["chunk"], rand=rand, **kw)
     got = _flatten(out)
-    keys = [k for k in a if k not in ("rays",) and not k.startswith("draw")]
+    keys = [k for k in a if k not in ("rays",) and not k.startswith("draw") and not (name.startswith("tf_") and k.startswith(TF_ONLY))]
     assert set(keys) == set(got)
     for k in keys:
         if k.startswith("mask"):
@@ -156,3 +167,58 @@ def test_forward_matches_reference(name):
             torch.testing.assert_close(got[k], a[k], rtol=1e-5, atol=2e-6, msg=lambda s, k=k: f"{k}: {s}")
     # fixtures are not numerically trivial: something is actually composited
     assert float(a["fine_mixed_acc"].max()) > 0.1
+    return meta, a
+
+
+@pytest.mark.parametrize("name", FWD_CASES)
+def test_forward_matches_reference(name):
+    _compare_with_reference(name)
+
+
+def test_real_count_fixtures_reach_every_layer_without_depth_ties():
+    """What tests/golden/make_golden.py --real-counts asserts when it writes them, read back from the files: every performer
+    layer hit by at least 8 rays, at most 0.5 % of the rays swapped for an exact depth tie, the sample counts the names say."""
+    counts = dict(fwd_c1_full=(1, 32, 0), fwd_c4_64_64=(4, 64, 64), tf_c4_64_64=(4, 64, 64), fwd_c5_128_64=(8, 128, 64),
+                  tf_c5_128_64=(8, 128, 64), batchify_default_chunk=(2, 12, 6))
+    for name, want in counts.items():
+        meta, a = load_golden(name)
+        assert (meta["L"], meta["n1"], meta["n2"]) == want
+        assert min(int(a[f"mask{i}"].sum()) for i in range(1, meta["L"] + 1)) >= 8, name
+        assert len(meta["swapped_rays"]) <= 0.005 * a["rays"].shape[0], name
+    meta, a = load_golden("batchify_default_chunk")
+    n, chunk = a["rays"].shape[0], meta["chunk"]
+    assert chunk == 3584 and n >= 2 * chunk + 1 and meta["call_kwargs"] == dict(density_threshold=0.05, bkgd_density_threshold=0.02)
+    assert a["rays"][[0, chunk, 2 * chunk], 7:].tolist() == [[2.5, 2.5], [1.0, 2.75], [3.0, 1.5]]
+    assert a["rays"][4000, 7:].tolist() == [3.0, 2.75] and a["rays"][3999, 7:].tolist() == [1.0, 2.75]
+    assert load_golden("fwd_c1_full")[1]["rays"].shape[0] > 3584        # two reference chunks
+
+
+def test_default_chunk_fixture_refuses_boxes_taken_from_the_first_chunk():
+    """batchify_default_chunk can fail (a): an oracle whose every chunk takes its boxes from the CALL's row 0, not from its own
+    (modeling/layered_rfrender.py:195-200 reads row 0 of what the model is handed, which is one chunk), is refused -- on the masks."""
+    _, a = load_golden("batchify_default_chunk")
+    orig = O.layer_boxes
+
+    def boxes_of_chunk0(m, rays):
+        mine = orig(m, rays)
+        first = orig(m, a["rays"][:rays.shape[0]])
+        return (first[0], first[1]) + tuple(mine[2:])
+
+    def batchify(m, rays, **kw):
+        O.layer_boxes = boxes_of_chunk0
+        try:
+            return O.layered_batchify_ray(m, rays, **kw)
+        finally:
+            O.layer_boxes = orig
+    with pytest.raises(AssertionError, match="mask|coarse|fine"):
+        _compare_with_reference("batchify_default_chunk", batchify)
+    assert O.layer_boxes is orig
+
+
+def test_default_chunk_fixture_refuses_dropped_thresholds():
+    """batchify_default_chunk can fail (b): an oracle that drops both thresholds in the chunked branch, as the small-call branch
+    does (utils/batchify_rays.py:52-54), is refused."""
+    def batchify(m, rays, chuncks, rand, density_threshold, bkgd_density_threshold):
+        return O.layered_batchify_ray(m, rays, chuncks=chuncks, rand=rand, density_threshold=0.0001, bkgd_density_threshold=0.0)
+    with pytest.raises(AssertionError, match="coarse|fine"):
+        _compare_with_reference("batchify_default_chunk", batchify)
