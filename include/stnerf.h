@@ -1084,6 +1084,51 @@ int64_t stnerf_accumulate_select_workspace_bytes(int64_t n_pixels);
 int stnerf_accumulate_select(const float* m2, const int32_t* count, int64_t n_pixels, int V, int min_spp, int max_spp, float tol2,
                              int32_t* pixels_out, int32_t* n_out, void* workspace, int64_t workspace_bytes, stnerf_stream_t stream);
 
+/* ---- A lens model in ray generation (csrc/lens.hip): the rays of a pixel list through a lens that distorts
+ * and has an aperture.  Every *, /, + and - below is one IEEE fp32 operation in the order written (no contraction).
+ *
+ * pix, u, v and the camera vector (cx, cy, cz) = Kinv (u, v, 1) are those of the pixel-list entry above, the skip of a list entry
+ * outside [0, h w) included.  Then
+ *   distort != 0 -- Brown-Conrady on normalised image coordinates, inverted by a FIXED number of fixed-point rounds (no exit that
+ *   depends on the data: a restatement is bit-equal):
+ *     xd = cx / cz;  yd = cy / cz;  x = xd;  y = yd;  STNERF_LENS_ITERS rounds of
+ *         xx = x*x;  yy = y*y;  xy = x*y;  r2 = xx + yy
+ *         rad = ((k3*r2 + k2)*r2 + k1)*r2 + 1.0f
+ *         tx  = p1*(xy + xy) + p2*(r2 + (xx + xx))
+ *         ty  = p1*(r2 + (yy + yy)) + p2*(xy + xy)
+ *         x   = (xd - tx) / rad;   y = (yd - ty) / rad
+ *     cx = x * cz;  cy = y * cz                                  (cz is unchanged)
+ *   points != NULL -- a thin lens.  The table row is j = phase, or with decorrelate
+ *     j = ((hash(pix ^ key) % n_points) + phase) % n_points   in uint32, with the 32-bit mixer
+ *     hash: x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16
+ *   so that over n_points passes a pixel uses every row exactly once.  (ax, ay) = points[j].  With ax == 0 && ay == 0 the row takes
+ *   the pinhole operations and nothing else (a pass through the lens centre is the pinhole ray, bit for bit); otherwise
+ *     s = focus / cz;  dx = cx*s - ax;  dy = cy*s - ay;  dz = cz*s;   (cx, cy, cz) = (dx, dy, dz)
+ *     o[r] = (T[4r]*ax + T[4r+1]*ay) + T[4r+3]                   r = 0, 1, 2
+ *   Without a lens point o[r] = T[4r+3].
+ * Normalisation (the squared norm is fmaf(cz, cz, fmaf(cy, cy, cx*cx))), rotation and the frame-id columns are those of the
+ * pixel-list entry.  A record with distort == 0 and points == NULL, or lens_host == NULL, IS that entry (the call is forwarded).
+ * One lane per row; HBM-bound on the 24 + 4 n_frame_cols bytes a row writes; no LDS.
+ * STNERF_EINVAL before any launch: everything the pixel-list entry refuses; a struct_size that is not the size of the record
+ * (checked first); with distort a NaN or infinite coefficient; with the lens enabled a third row of Kinv that is not (0, 0, k),
+ * k != 0 (the plane in focus and the division by cz assume one cz for the view); with points n_points < 1, phase outside
+ * [0, n_points), a focus that is zero, not finite or of the opposite sign to k. */
+#define STNERF_LENS_ITERS 20
+typedef struct stnerf_lens {
+    int32_t struct_size;      /* the size of this record in bytes; anything else: STNERF_EINVAL, checked first */
+    int32_t distort;          /* != 0: the five coefficients below are applied */
+    float k1, k2, k3, p1, p2; /* Brown-Conrady (the OpenCV order), on normalised image coordinates */
+    float focus;              /* camera-space z of the plane in focus; read only with points != NULL */
+    const float* points;      /* device [n_points][2]: lens points in camera x, y, world units (already times the aperture radius), or NULL: pinhole */
+    int32_t n_points;         /* >= 1 with points */
+    int32_t phase;            /* 0 <= phase < n_points: the pass */
+    int32_t decorrelate;      /* != 0: every pixel walks the table from its own start */
+    uint32_t key;             /* xor-ed into the pixel before hashing */
+} stnerf_lens;
+int stnerf_generate_rays_lens(const float* Kinv_host, const float* T_host, int h, int w, const int32_t* pixels, int64_t n,
+                              float du, float dv, const stnerf_lens* lens_host, const float* frame_ids_host, int n_frame_cols,
+                              float* rays, int ray_stride, stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

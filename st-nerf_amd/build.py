@@ -27,6 +27,7 @@ SOURCES = [
     ("termination.hip", ["-ffp-contract=off"]),
     ("background_rows.hip", ["-ffp-contract=off"]),
     ("accumulate.hip", ["-ffp-contract=off"]),
+    ("lens.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

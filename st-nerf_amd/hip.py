@@ -99,6 +99,17 @@ class RenderOptions(C.Structure):
         super().__init__(struct_size=C.sizeof(RenderOptions), **fields)
 
 
+class LensRecord(C.Structure):
+    """stnerf_lens (include/stnerf.h): the distortion coefficients, the plane in focus, the device table of lens points and the
+    pass's place in it.  ``LensRecord()`` is "no lens": all zero, struct_size set."""
+    _fields_ = [("struct_size", C.c_int32), ("distort", C.c_int32), ("k1", C.c_float), ("k2", C.c_float), ("k3", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("focus", C.c_float), ("points", c_f32p), ("n_points", C.c_int32),
+                ("phase", C.c_int32), ("decorrelate", C.c_int32), ("key", C.c_uint32)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=C.sizeof(LensRecord), **fields)
+
+
 BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
 LAYER_CACHE_OFF, LAYER_CACHE_CAPTURE, LAYER_CACHE_REUSE = 0, 1, 2   # STNERF_LAYER_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
@@ -212,6 +223,8 @@ _PROTOS = {
     "stnerf_occluder_stop": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_void_p]),
     "stnerf_generate_rays_list": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
                                             C.c_float, C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
+    "stnerf_generate_rays_lens": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
+                                            C.c_float, C.POINTER(LensRecord), C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_accumulate": (C.c_int, [c_f32p, c_i64, C.c_int, c_i64, C.c_void_p, c_i64, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
     "stnerf_accumulate_select_workspace_bytes": (c_i64, [c_i64]),
     "stnerf_accumulate_select": (C.c_int, [c_f32p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,

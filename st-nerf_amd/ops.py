@@ -99,9 +99,25 @@ def window_size(total: int, first: int, stripe: int, period: int) -> int:
     return full * stripe + min(rem, stripe)
 
 
+def _lens_record(lens, k: float, phase: int, points: Optional[Tensor]) -> "hip.LensRecord":
+    """The stnerf_lens of an enabled ``Lens`` for one pass.  k = K^-1's [2][2]: the library's focus is a camera-space z, of k's sign.
+    Without an aperture there is no table (``points`` is not read)."""
+    rec = hip.LensRecord(distort=int(lens.distorts), k1=lens.k1, k2=lens.k2, k3=lens.k3, p1=lens.p1, p2=lens.p2, key=lens.key)
+    if lens.aperture > 0.0:
+        if points is None:
+            raise ValueError("generate_rays: a lens with aperture > 0 needs lens_points=, the device table lens.table(n_points)")
+        if points.dim() != 2 or points.shape[1] != 2 or points.shape[0] < 1:
+            raise ValueError(f"generate_rays: lens_points must be (n_points, 2) float32, got {tuple(points.shape)}")
+        rec.points = hip.dptr(points, name="lens_points").value
+        rec.n_points, rec.phase, rec.decorrelate = points.shape[0], int(phase), int(lens.decorrelate)
+        rec.focus = -lens.focus if k < 0 else lens.focus
+    return rec
+
+
 def generate_rays(K: Tensor, T: Tensor, h: int, w: int, frame_ids: Optional[Sequence[float]] = None,
                   first_ray: int = 0, n: Optional[int] = None, device="cuda", stripe: int = 0, period: int = 0,
-                  pixels: Optional[Tensor] = None, offset: Sequence[float] = (0.0, 0.0)) -> Tensor:
+                  pixels: Optional[Tensor] = None, offset: Sequence[float] = (0.0, 0.0), lens=None, lens_phase: int = 0,
+                  lens_points: Optional[Tensor] = None) -> Tensor:
     """Rays of a view, generated on the device: (n, 6 + len(frame_ids)).  (first_ray, stripe, period) = the ray
     window of include/stnerf.h: a contiguous piece of the view (stripe = 0) or interleaved stripes.
     utils/render_helpers.py:42-128 + data/datasets/ray_dataset.py:276-281.
@@ -109,7 +125,18 @@ def generate_rays(K: Tensor, T: Tensor, h: int, w: int, frame_ids: Optional[Sequ
     ``pixels`` / ``offset`` (stnerf_generate_rays_list; progressive multi-sample frames): row i is pixel ``pixels[i]`` of the
     view -- a device int32 list naming a pixel at most once; None with ``n``: the contiguous pixels 0..n-1 -- moved by
     ``offset`` = (du, dv) pixels.  With a zero offset row i is bit-identical to row ``pixels[i]`` of the plain call.  They do
-    not combine with a ray window."""
+    not combine with a ray window.
+
+    ``lens`` (stnerf_generate_rays_lens; ``stnerf_amd.lens.Lens`` or the dict of its arguments): the rays of a lens that distorts
+    and / or has an aperture.  With ``lens.aperture > 0`` the ray of pass ``lens_phase`` starts at a row of ``lens_points``, the
+    device (n_points, 2) float32 table ``lens.table(n_points)`` (uploaded once per frame by the caller) -- row ``lens_phase``, or
+    with ``lens.decorrelate`` a row every pixel picks from its own start.  ``pixels`` / ``offset`` keep their meaning; a ray
+    window does not combine with an enabled lens.  None, or a lens that changes no ray: exactly the calls above."""
+    from stnerf_amd.lens import as_lens
+    lens = as_lens(lens)
+    lensed = lens is not None and lens.enabled
+    if lensed and (first_ray or stripe or period):
+        raise ValueError("generate_rays: lens= does not combine with a ray window (first_ray, stripe, period)")
     listed = pixels is not None or tuple(float(x) for x in offset) != (0.0, 0.0)
     if listed and (first_ray or stripe or period):
         raise ValueError("generate_rays: pixels= / offset= do not combine with a ray window (first_ray, stripe, period)")
@@ -125,6 +152,12 @@ def generate_rays(K: Tensor, T: Tensor, h: int, w: int, frame_ids: Optional[Sequ
     kin = (C.c_float * 9)(*kinv.reshape(-1).tolist())
     tin = (C.c_float * 16)(*Tm.reshape(-1).tolist())
     fin = (C.c_float * max(len(fids), 1))(*(fids or [0.0]))
+    if lensed:
+        rec = _lens_record(lens, float(kinv[2, 2]), lens_phase, lens_points)
+        hip.check(hip.lib().stnerf_generate_rays_lens(kin, tin, h, w, hip.dptr(pixels, torch.int32, "pixels"), n, float(offset[0]),
+                                                      float(offset[1]), C.byref(rec), fin if fids else None, len(fids), hip.dptr(rays),
+                                                      rays.shape[1], hip.stream_ptr()), "stnerf_generate_rays_lens")
+        return rays
     if listed:
         hip.check(hip.lib().stnerf_generate_rays_list(kin, tin, h, w, hip.dptr(pixels, torch.int32, "pixels"), n, float(offset[0]),
                                                       float(offset[1]), fin if fids else None, len(fids), hip.dptr(rays),

@@ -372,13 +372,26 @@ def render_rays_sharded(model, rays, chuncks: int, density_threshold=0.0, bkgd_d
                          only_coarse, density_threshold, bkgd_density_threshold, chuncks, model.replay)
 
 
-def _view_key(model, K, T, h, w, frame_ids):
+def _view_key(model, K, T, h, w, frame_ids, lens=None):
     """The view key of rays generated from this camera, for a model with a background cache or a layer cache attached (else None:
-    no cost)."""
+    no cost).  An enabled ``lens`` joins the view's identity with its fingerprint: the caches miss when only the lens changes."""
     if getattr(model, "_bkgd_cache", None) is None and getattr(model, "_layer_cache", None) is None:
         return None
     from stnerf_amd.bkgd_cache import view_key
-    return view_key(K, T, h, w, frame_ids)
+    view, bkgd_frame = view_key(K, T, h, w, frame_ids)
+    if lens is not None and lens.enabled:
+        view = view + (("lens",) + lens.fingerprint(),)
+    return view, bkgd_frame
+
+
+def _checked_lens(lens, K, h, w):
+    """``lens`` (None | Lens | dict) -> the Lens when it changes any ray, checked against the view (``Lens.check``), else None."""
+    from stnerf_amd.lens import as_lens
+    lens = as_lens(lens)
+    if lens is None or not lens.enabled:
+        return None
+    lens.check(K, h, w)
+    return lens
 
 
 def _view_frame_ids(model, frame_ids):
@@ -391,7 +404,7 @@ def _view_frame_ids(model, frame_ids):
 
 def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, bkgd_density_threshold=0.0,
                 chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda", gather: Optional[str] = None, scene: bool = False,
-                occluder=None, occluder_stops: bool = False):
+                occluder=None, occluder_stops: bool = False, lens=None):
     """One view from its camera: rays generated on the device (no CPU ray tensor), ``layered_batchify_ray`` semantics, the
     reference's 5-tuple on every rank.  Without a process group: the whole view on this GPU.  With one: interleaved
     stripes of ``stripe_rows`` image rows over the ranks (rank r generates and renders rows r, r + G, ... only), one
@@ -399,16 +412,23 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     ``render.render_pose`` calls (with gather="fine": the images it returns).  ``scene``: (5-tuple, scene) of
     ``LayeredRFRender.render_rays_scene`` instead -- on one rank only (the gather modes have fixed widths; it raises otherwise).
     ``occluder``: (h w, 5) rows {r, g, b, a, z} of the view's rays, z a ray parameter -> (5-tuple, scene, occluded) of
-    ``LayeredRFRender.render_rays_occluded`` (``occluder_stops``: its ``stops``); one rank only, as ``scene``."""
+    ``LayeredRFRender.render_rays_occluded`` (``occluder_stops``: its ``stops``); one rank only, as ``scene``.
+    ``lens``: a ``stnerf_amd.lens.Lens`` (or the dict of its arguments) that distorts -- the rays come from
+    ``stnerf_generate_rays_lens`` and everything downstream is unchanged, the caches keyed by the lens too; one rank only.  A lens
+    with an aperture needs several passes: ValueError here, ``render_view_accumulated`` renders it."""
     from stnerf_amd import ops
     from stnerf_amd.utils.batchify_rays import layered_batchify_ray
+    lens = _checked_lens(lens, K, h, w)
+    if lens is not None and lens.aperture > 0.0:
+        raise ValueError("render_view(lens=...) with aperture > 0: defocus is the mean of several passes through the lens; render it "
+                         "with accumulate= (render_view_accumulated)")
     act = active_group(model)
     n_total = h * w
     if act is None or n_total < chuncks:
-        rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device)
+        rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device, **(dict(lens=lens) if lens is not None else {}))
         saved_key, saved_ids = getattr(model, "view_key", None), getattr(model, "view_frame_ids", None)
         try:
-            model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids), _view_frame_ids(model, frame_ids)
+            model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids, lens), _view_frame_ids(model, frame_ids)
             with torch.no_grad():
                 if occluder is not None:
                     if n_total < chuncks:
@@ -423,6 +443,9 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
                                             bkgd_density_threshold=bkgd_density_threshold)
         finally:
             model.view_key, model.view_frame_ids = saved_key, saved_ids
+    if lens is not None:
+        raise RuntimeError("render_view(lens=...) on a view sharded over more than one rank: a lens in the windowed ray generator is out "
+                           "of scope; render through a lens on one rank (model.shard_views = False)")
     if occluder is not None:
         raise RuntimeError("render_view(occluder=...) on a view sharded over more than one rank: a \"scene\" gather mode is out of scope; "
                            "render with an occluder on one rank (model.shard_views = False)")
@@ -442,7 +465,7 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
 
 
 def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, density_threshold=0.0, bkgd_density_threshold=0.0,
-                            chuncks: int = 512 * 7, device="cuda", scene: bool = False, occluder=None):
+                            chuncks: int = 512 * 7, device="cuda", scene: bool = False, occluder=None, lens=None):
     """One view as a progressive multi-sample frame (``stnerf_amd.accumulate.AccumulateSpec``): the
     per-pixel mean of up to ``spec.max_spp`` passes -> (the reference's 5-tuple built from the means, coarse entries None as in
     gather mode "fine", stats).  Inference only, one rank.
@@ -457,10 +480,16 @@ def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, densit
     returned are pass 0's (the plain frame's).  On return the seed is s0 + passes if ``model.fresh_draws_per_call``, else s0.
 
     stats: ``spp`` (h w,) int32 and ``variance`` (h w, 3) = m2 / (c (c - 1)) of the mixed colour's mean, 0 where c < 2, on
-    the device; ``passes`` and ``rays_rendered``, Python ints."""
+    the device; ``passes`` and ``rays_rendered``, Python ints.
+
+    ``lens``: a ``stnerf_amd.lens.Lens`` (or the dict of its arguments).  Pass p generates its rays through it with
+    ``lens_phase = p`` and the table ``lens.table(spec.max_spp)``, uploaded once: distortion on every pass, and with
+    ``aperture > 0`` depth of field -- the third effect of distributed ray tracing, by the mechanism of the other two.  Pass 0
+    goes through the lens centre.  Everything else in the loop is unchanged."""
     from stnerf_amd import ops
     from stnerf_amd.accumulate import as_spec
     spec = as_spec(spec)
+    lens = _checked_lens(lens, K, h, w)
     if active_group(model) is not None:
         raise RuntimeError("render_view_accumulated under shard_views with more than one rank: the per-pixel state lives on one "
                            "device and multi-rank accumulation is out of scope; render on one rank (model.shard_views = False)")
@@ -484,6 +513,11 @@ def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, densit
     s0 = int(model.seed) & mask64
     state = ops.accumulate_state(n_total, 5 + 5 * l, 3, device)
     pixels, n_active, bits = None, n_total, None
+    through = {}
+    if lens is not None:
+        through = dict(lens=lens)
+        if lens.aperture > 0.0:
+            through["lens_points"] = torch.from_numpy(lens.table(spec.max_spp)).to(device)
     p = rays_rendered = 0
     try:
         with torch.no_grad():
@@ -494,7 +528,7 @@ def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, densit
                         break
                 model.seed = (s0 + p) & mask64
                 rays = ops.generate_rays(K, T, h, w, frame_ids=spec.frame_ids(p, frame_ids), device=device, pixels=pixels,
-                                         offset=spec.offset(p))
+                                         offset=spec.offset(p), **(dict(through, lens_phase=p) if through else {}))
                 if n_total < chuncks:     # (layered_batchify_ray's small-call rule, decided by the view)
                     raw = model.render_rays_raw(rays)
                 else:

@@ -34,7 +34,7 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False, accumulate=None):
+                 occluder=None, occluder_stops=False, accumulate=None, lens=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -98,6 +98,11 @@ class LayeredNeuralRenderer:
             self.accumulate = as_spec(accumulate)
         self.spp_maps = []
         self._frame_stats = None
+        # lens: an stnerf_amd.lens.Lens or the dict of its arguments -- the camera's lens for every frame of the path (render_pose's
+        # `lens`): its distortion bends the rays, its aperture (with accumulate) gives depth of field.  on_frame and the stats are
+        # unchanged.  Not in the reference (keyword-only, off by default)
+        from stnerf_amd.lens import as_lens
+        self.lens = as_lens(lens)
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -398,15 +403,17 @@ class LayeredNeuralRenderer:
 
     # ---- rendering -------------------------------------------------------------------------------------------
     def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None,
-                    accumulate=None):
+                    accumulate=None, lens=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
         element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
         also holds the occluded results; with ``accumulate`` = a spec the frame is a progressive multi-sample one and the fifth
-        element is its ``stats``."""
+        element is its ``stats``.  ``lens``: the camera's lens for this frame (default: the renderer's ``lens``)."""
+        lens = self.lens if lens is None else lens
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
                             bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
                             **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}),
-                            **(dict(accumulate=accumulate) if accumulate is not None else {}))
+                            **(dict(accumulate=accumulate) if accumulate is not None else {}),
+                            **(dict(lens=lens) if lens is not None else {}))
 
     def _render_frame(self, idx, density_threshold, bkgd_density_threshold, inverse_y_axis):
         """Frame ``idx`` of the path -> (color, depth, color_layer, depth_layer, passes): ``render_pose``, flipped on request;

@@ -15,7 +15,7 @@ from stnerf_amd.parallel import render_view, total_layers
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
                 density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
-                occluder=None, occluder_stops: bool = False, accumulate=None):
+                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -48,7 +48,12 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     of several passes -- anti-aliasing, motion blur, adaptive samples per pixel (``parallel.render_view_accumulated``; DESIGN.md
     section 7).  The depth post-processing above is applied to the means, and a fifth element ``stats`` is returned: ``spp``
     (H,W) int32, ``variance`` (H,W,3) of the mixed colour's mean, ``passes``, ``rays_rendered``.  It does not combine with
-    ``scene_passes`` or an occluder (ValueError).  One rank only."""
+    ``scene_passes`` or an occluder (ValueError).  One rank only.
+
+    ``lens`` = an ``stnerf_amd.lens.Lens`` (or the dict of its arguments): the camera's lens.  Its distortion
+    bends the rays of this frame so that it lines up with a plate shot through that lens -- nothing is resampled, and scene passes,
+    an occluder and the caches work as without it.  Its ``aperture`` gives depth of field and needs ``accumulate`` (ValueError
+    without): every pass then starts its rays at another point of the lens.  One rank only."""
     if accumulate is not None:
         from stnerf_amd.parallel import render_view_accumulated
         frame_ids = [0.0] * total_layers(model)
@@ -56,7 +61,8 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
             frame_ids[layer_id] = float(frame_id)
         (stage2, _, stage2_layer, _, _), stats = render_view_accumulated(
             model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width, frame_ids,
-            accumulate, density_threshold, bkgd_density_threshold, device=device, scene=bool(scene_passes), occluder=occluder)
+            accumulate, density_threshold, bkgd_density_threshold, device=device, scene=bool(scene_passes), occluder=occluder,
+            **(dict(lens=lens) if lens is not None else {}))
         stats = dict(stats, spp=stats["spp"].reshape(height, width), variance=stats["variance"].reshape(height, width, 3))
         return (stage2[0].reshape(height, width, 3), stage2[1].reshape(height, width, 1).clamp_min(0) / far,
                 [t[0].reshape(height, width, 3) for t in stage2_layer], [t[1].reshape(height, width, 1) / far for t in stage2_layer],
@@ -74,7 +80,8 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     out = render_view(model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width,
                       frame_ids, density_threshold, bkgd_density_threshold, device=device, gather="fine",
                       **(dict(scene=True) if scene_passes else {}),
-                      **(dict(occluder=occ_rows, occluder_stops=occluder_stops) if occ_rows is not None else {}))
+                      **(dict(occluder=occ_rows, occluder_stops=occluder_stops) if occ_rows is not None else {}),
+                      **(dict(lens=lens) if lens is not None else {}))
     occluded = None
     if occ_rows is not None:
         (stage2, _, stage2_layer, _, _), scene, occluded = out

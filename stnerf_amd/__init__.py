@@ -35,4 +35,7 @@ def __getattr__(name):
     if name == "AccumulateSpec":
         from stnerf_amd.accumulate import AccumulateSpec
         return AccumulateSpec
+    if name == "Lens":
+        from stnerf_amd.lens import Lens
+        return Lens
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
