@@ -1129,6 +1129,56 @@ int stnerf_generate_rays_lens(const float* Kinv_host, const float* T_host, int h
                               float du, float dv, const stnerf_lens* lens_host, const float* frame_ids_host, int n_frame_cols,
                               float* rays, int ray_stride, stnerf_stream_t stream);
 
+/* ---- Reprojection of a key view's rows into a nearby view (csrc/reproject.hip): a forward splat with a depth
+ * test, a resolve that turns cracks and silhouettes into holes, and the ascending list of the holes.  Three helpers around the
+ * render entries; every *, /, +, - and sqrtf below is one IEEE fp32 operation in the order written (no contraction).
+ *
+ * Splat.  Row q of a source view (Kinv_s, T_s, h_s, w_s), q = 0..n-1 with n <= h_s w_s, carries a ray parameter t = t_src[q].  The
+ * row is absent unless t is finite and t > 0.  (o, d) is the ray of pixel q exactly as stnerf_generate_rays_list gives it with
+ * du = dv = 0 (the same device function).  With Wd[12] the world-to-camera 3x4 of the destination pose (the caller inverts T_d in
+ * fp64 and rounds to fp32), o_d[3] the destination camera's centre (T_d[4r+3]) and K_d[9] its intrinsics, all row-major:
+ *     p[r]   = t * d[r] + o[r]
+ *     c[r]   = ((Wd[4r]*p[0] + Wd[4r+1]*p[1]) + Wd[4r+2]*p[2]) + Wd[4r+3]          skipped if  c[2] <= z_min
+ *     pix[r] = (K_d[3r]*c[0] + K_d[3r+1]*c[1]) + K_d[3r+2]*c[2]
+ *     u = pix[0] / pix[2];  v = pix[1] / pix[2];  iu = (int)rintf(u);  iv = (int)rintf(v)   (pixel centres sit at integers)
+ *     skipped if u or v is not finite or (iu, iv) is outside [0, w_d) x [0, h_d)
+ *     e[r]   = p[r] - o_d[r];   t' = sqrtf(fmaf(e[2], e[2], fmaf(e[1], e[1], e[0]*e[0])))      (the ray generator's norm order)
+ *     key    = ((uint64)bits(t') << 32) | (uint32)(id_base + q);   keys[iv * w_d + iu] = min(keys[..], key)   (a 64-bit atomic)
+ * A positive float's bits order as the float does: the nearest surface wins, on an exact tie the lower id, whatever the order of
+ * lanes and launches.  The caller fills keys[h_d w_d] with all-ones (= empty) and may splat up to STNERF_REPROJECT_MAX_SOURCES
+ * sources into it before resolving; source s uses id_base = n_0 + .. + n_(s-1), and every id stays below 2^31.
+ * STNERF_EINVAL before any launch: a null pointer, h w of either view outside 1..INT32_MAX, n < 0 or n > h_s w_s, id_base < 0 or
+ * id_base + n > 2^31, z_min not finite or < 0.
+ *
+ * Resolve.  One lane per destination pixel j.  An empty key is a hole.  Otherwise m = the smallest t' among the non-empty keys of
+ * the 3x3 neighbourhood inside the image (j included), and j is a hole as well if  t'_j > m * guard,  guard = 1.0f + rel in fp32:
+ * a far surface seen through the cracks of a magnified near one, and the far side of every silhouette, are rendered again.  A filled
+ * pixel copies the C floats of row (id - base_s) of its source s (sources_host: n_sources records {values, row_stride, n}, device
+ * pointers, base_s as above) to values_out[j][C] and writes t_out[j] = t', src_out[j] = id; a hole gets zeros, a NaN t_out and
+ * src_out[j] = -1 (so does a key whose id no record holds).  STNERF_EINVAL before any launch: a null pointer, h_d w_d outside
+ * 1..INT32_MAX, C outside 1..64, rel < 0 or NaN, n_sources outside 1..STNERF_REPROJECT_MAX_SOURCES, a record with n < 0 or
+ * row_stride < C, n_0 + .. > 2^31 - 1.
+ *
+ * Hole list.  holes_out[0 .. *n_out) = the j with src[j] < 0, ascending (room for n_pixels entries); n_out: one device int32.  The
+ * three launches of stnerf_accumulate_select (csrc/ordered_compact.h), deterministic; workspace as there.  STNERF_EINVAL before any
+ * launch: a null pointer, n_pixels outside 1..INT32_MAX, a workspace too small.
+ * One lane per row in all three; HBM- and atomics-bound (about 12 B per source row, 4 C + 12 B per destination pixel); no LDS in
+ * splat and resolve. */
+#define STNERF_REPROJECT_MAX_SOURCES 4
+typedef struct stnerf_reproject_source {
+    const float* values;  /* device [n][row_stride]: the first C floats of a row are copied */
+    int64_t row_stride;   /* floats between rows, >= C */
+    int64_t n;            /* rows; the ids of this source are base .. base + n - 1 */
+} stnerf_reproject_source;
+int stnerf_reproject_splat(const float* Kinv_s_host, const float* T_s_host, int h_s, int w_s, const float* t_src, int64_t n,
+                           int64_t id_base, const float* K_d_host, const float* Wd_host, const float* o_d_host, int h_d, int w_d,
+                           float z_min, uint64_t* keys, stnerf_stream_t stream);
+int stnerf_reproject_resolve(const uint64_t* keys, int h_d, int w_d, float rel, const stnerf_reproject_source* sources_host,
+                             int n_sources, int C, float* values_out, float* t_out, int32_t* src_out, stnerf_stream_t stream);
+int64_t stnerf_reproject_holes_workspace_bytes(int64_t n_pixels);
+int stnerf_reproject_holes(const int32_t* src, int64_t n_pixels, int32_t* holes_out, int32_t* n_out, void* workspace,
+                           int64_t workspace_bytes, stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

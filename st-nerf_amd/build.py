@@ -28,6 +28,7 @@ SOURCES = [
     ("background_rows.hip", ["-ffp-contract=off"]),
     ("accumulate.hip", ["-ffp-contract=off"]),
     ("lens.hip", ["-ffp-contract=off"]),
+    ("reproject.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

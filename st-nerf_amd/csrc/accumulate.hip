@@ -5,6 +5,8 @@
 // ordered, deterministic compaction of the pixels that are still active.
 // Compiled with -ffp-contract=off: every product, quotient and sum of the definitions is one fp32 operation.
 #include "common.h"
+#include "ordered_compact.h"
+#include "pinhole_ray.h"
 
 namespace stnerf {
 
@@ -16,30 +18,22 @@ struct RayListArgs {
 };
 
 // generate_rays_kernel (csrc/sampler.hip) with the pixel taken from a list and moved by (du, dv); every other operation in
-// that kernel's order.  One lane per row; a list entry outside [0, h w) leaves its row unwritten.
+// that kernel's order (csrc/pinhole_ray.h).  One lane per row; a list entry outside [0, h w) leaves its row unwritten.
 __global__ void generate_rays_list_kernel(RayListArgs a, int w, int64_t n_pixels, const int32_t* __restrict__ pixels, int64_t n,
                                           float du, float dv, int n_frame_cols, float* __restrict__ rays, int ray_stride) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t pix = pixels ? (int64_t)pixels[i] : i;
     if (pix < 0 || pix >= n_pixels) return;
-    const int p32 = (int)pix;               // (h w <= INT32_MAX: the host checks)
-    const float u = (float)(p32 % w) + du;  // column
-    const float v = (float)(p32 / w) + dv;  // row
-    float cx = a.kinv[0] * u + a.kinv[1] * v + a.kinv[2];
-    float cy = a.kinv[3] * u + a.kinv[4] * v + a.kinv[5];
-    float cz = a.kinv[6] * u + a.kinv[7] * v + a.kinv[8];
-    const float nrm = sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx)));  // torch.norm's order (utils/render_helpers.py:108)
-    cx = cx / nrm;
-    cy = cy / nrm;
-    cz = cz / nrm;
+    float o[3], d[3];
+    pinhole_pixel_ray(a.kinv, a.T, (int)pix, w, du, dv, o, d);  // (h w <= INT32_MAX: the host checks)
     float* r = rays + i * ray_stride;
-    r[0] = a.T[3];
-    r[1] = a.T[7];
-    r[2] = a.T[11];
-    r[3] = a.T[0] * cx + a.T[1] * cy + a.T[2] * cz;
-    r[4] = a.T[4] * cx + a.T[5] * cy + a.T[6] * cz;
-    r[5] = a.T[8] * cx + a.T[9] * cy + a.T[10] * cz;
+    r[0] = o[0];
+    r[1] = o[1];
+    r[2] = o[2];
+    r[3] = d[0];
+    r[4] = d[1];
+    r[5] = d[2];
     for (int c = 0; c < n_frame_cols; ++c) r[6 + c] = a.frame_ids[c];
 }
 
@@ -87,8 +81,7 @@ __global__ void __launch_bounds__(256) accumulate_count_kernel(int64_t n, const 
 }
 
 // ------------------------------------------------------------------------------------- the pixels still active
-constexpr int kSelectBlock = 256;   // pixels per workgroup of launches 1 and 3
-constexpr int kScanBlock = 1024;    // workgroup popcounts per pass of launch 2
+// (the three launches of the ordered compaction: csrc/ordered_compact.h)
 
 // The rule of include/stnerf.h, as written there.
 __device__ __forceinline__ bool pixel_active(const float* __restrict__ m2, const int32_t* __restrict__ count, int64_t q, int V,
@@ -102,72 +95,13 @@ __device__ __forceinline__ bool pixel_active(const float* __restrict__ m2, const
     return any;
 }
 
-// Launch 1: block_count[b] = active pixels of [256 b, 256 b + 256).
-__global__ void __launch_bounds__(kSelectBlock) select_count_kernel(const float* __restrict__ m2, const int32_t* __restrict__ count,
-                                                                    int64_t P, int V, int min_spp, int max_spp, float tol2,
-                                                                    int32_t* __restrict__ block_count) {
-    __shared__ int wave_total[kSelectBlock / 64];
-    const int64_t q = (int64_t)blockIdx.x * kSelectBlock + threadIdx.x;
-    const bool act = q < P && pixel_active(m2, count, q, V, min_spp, max_spp, tol2);
-    const unsigned long long ball = __ballot(act);
-    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = __popcll(ball);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int i = 0; i < kSelectBlock / 64; ++i) tot += wave_total[i];
-        block_count[blockIdx.x] = tot;
-    }
-}
-
-// Launch 2: ONE workgroup turns the nb popcounts into exclusive offsets, in place, 1024 per pass with a running carry, and
-// writes the total.  It waits on no other workgroup: there is none.
-__global__ void __launch_bounds__(kScanBlock) select_scan_kernel(int32_t* __restrict__ block_count, int64_t nb, int32_t* __restrict__ total) {
-    __shared__ int wave_sum[kScanBlock / 64];
-    __shared__ int carry_s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nb; base += kScanBlock) {
-        const int64_t b = base + threadIdx.x;
-        const int v = b < nb ? block_count[b] : 0;
-        int inc = v;  // inclusive scan of the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
-        }
-        if (lane == 63) wave_sum[wave] = inc;
-        __syncthreads();
-        int before = carry_s;
-        for (int i = 0; i < wave; ++i) before += wave_sum[i];
-        if (b < nb) block_count[b] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == kScanBlock - 1) carry_s = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry_s;
-}
-
-// Launch 3: the predicate again, the pixel's place = its workgroup's offset + the waves before it + the lanes before it.
-__global__ void __launch_bounds__(kSelectBlock) select_write_kernel(const float* __restrict__ m2, const int32_t* __restrict__ count,
-                                                                    int64_t P, int V, int min_spp, int max_spp, float tol2,
-                                                                    const int32_t* __restrict__ block_offset,
-                                                                    int32_t* __restrict__ pixels_out) {
-    __shared__ int wave_total[kSelectBlock / 64];
-    const int64_t q = (int64_t)blockIdx.x * kSelectBlock + threadIdx.x;
-    const bool act = q < P && pixel_active(m2, count, q, V, min_spp, max_spp, tol2);
-    const unsigned long long ball = __ballot(act);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_total[wave] = __popcll(ball);
-    __syncthreads();
-    if (!act) return;
-    int at = block_offset[blockIdx.x];
-    for (int i = 0; i < wave; ++i) at += wave_total[i];
-    at += __popcll(ball & ((1ull << lane) - 1ull));
-    pixels_out[at] = (int32_t)q;     // at < the total <= P: as many places as active pixels
-}
-
-static inline int64_t select_blocks(int64_t P) { return (P + kSelectBlock - 1) / kSelectBlock; }
+struct PixelActive {
+    const float* m2;
+    const int32_t* count;
+    int V, min_spp, max_spp;
+    float tol2;
+    __device__ __forceinline__ bool operator()(int64_t q) const { return pixel_active(m2, count, q, V, min_spp, max_spp, tol2); }
+};
 
 }  // namespace stnerf
 
@@ -219,7 +153,7 @@ extern "C" int stnerf_accumulate(const float* values, int64_t n, int C, int64_t 
 
 extern "C" int64_t stnerf_accumulate_select_workspace_bytes(int64_t n_pixels) {
     STNERF_REQUIRE(n_pixels >= 1 && n_pixels <= INT32_MAX, "accumulate_select_workspace_bytes: bad pixel count %lld", (long long)n_pixels);
-    return (select_blocks(n_pixels) * (int64_t)sizeof(int32_t) + 255) / 256 * 256;
+    return select_workspace_bytes(n_pixels);
 }
 
 extern "C" int stnerf_accumulate_select(const float* m2, const int32_t* count, int64_t n_pixels, int V, int min_spp, int max_spp,
@@ -233,15 +167,7 @@ extern "C" int stnerf_accumulate_select(const float* m2, const int32_t* count, i
     STNERF_REQUIRE(tol2 >= 0.f, "accumulate_select: tol2 must be >= 0");
     STNERF_REQUIRE(workspace_bytes >= stnerf_accumulate_select_workspace_bytes(n_pixels), "accumulate_select: workspace too small (%lld B, %lld needed)",
                    (long long)workspace_bytes, (long long)stnerf_accumulate_select_workspace_bytes(n_pixels));
-    const int64_t nb = select_blocks(n_pixels);
-    int32_t* blocks = reinterpret_cast<int32_t*>(workspace);
-    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)nb), dim3(kSelectBlock), 0, as_stream(stream), m2, count, n_pixels, V, min_spp,
-                       max_spp, tol2, blocks);
-    STNERF_CHECK_LAUNCH("accumulate_select (count)");
-    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kScanBlock), 0, as_stream(stream), blocks, nb, n_out);
-    STNERF_CHECK_LAUNCH("accumulate_select (scan)");
-    hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)nb), dim3(kSelectBlock), 0, as_stream(stream), m2, count, n_pixels, V, min_spp,
-                       max_spp, tol2, (const int32_t*)blocks, pixels_out);
-    STNERF_CHECK_LAUNCH("accumulate_select (write)");
-    return STNERF_OK;
+    const PixelActive pred{m2, count, V, min_spp, max_spp, tol2};
+    return ordered_compact(pred, n_pixels, reinterpret_cast<int32_t*>(workspace), pixels_out, n_out, as_stream(stream),
+                           "accumulate_select (count)", "accumulate_select (scan)", "accumulate_select (write)");
 }

@@ -110,6 +110,12 @@ class LensRecord(C.Structure):
         super().__init__(struct_size=C.sizeof(LensRecord), **fields)
 
 
+class ReprojectSource(C.Structure):
+    """stnerf_reproject_source (include/stnerf.h): one source's rows on the device, the floats between rows, and how many."""
+    _fields_ = [("values", c_f32p), ("row_stride", C.c_int64), ("n", C.c_int64)]
+
+
+REPROJECT_MAX_SOURCES = 4   # STNERF_REPROJECT_MAX_SOURCES
 BKGD_CACHE_OFF, BKGD_CACHE_CAPTURE, BKGD_CACHE_REUSE = 0, 1, 2   # STNERF_BKGD_CACHE_*
 LAYER_CACHE_OFF, LAYER_CACHE_CAPTURE, LAYER_CACHE_REUSE = 0, 1, 2   # STNERF_LAYER_CACHE_*
 MOTION_ADD_TO_XYZ, MOTION_PLAIN_TIME = 1, 2   # STNERF_MOTION_* bits of stnerf_motionnet_fwd's add_to_xyz argument
@@ -229,6 +235,13 @@ _PROTOS = {
     "stnerf_accumulate_select_workspace_bytes": (c_i64, [c_i64]),
     "stnerf_accumulate_select": (C.c_int, [c_f32p, C.c_void_p, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                            C.c_void_p, c_i64, C.c_void_p]),
+    "stnerf_reproject_splat": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, c_f32p, c_i64, c_i64,
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float,
+                                         C.c_void_p, C.c_void_p]),
+    "stnerf_reproject_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(ReprojectSource), C.c_int, C.c_int, c_f32p,
+                                           c_f32p, C.c_void_p, C.c_void_p]),
+    "stnerf_reproject_holes_workspace_bytes": (c_i64, [c_i64]),
+    "stnerf_reproject_holes": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
     "stnerf_copy_layer_raw_listed": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                                C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),

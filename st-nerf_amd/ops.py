@@ -1173,6 +1173,100 @@ def accumulate_select(state: AccumulateState, min_spp: int, max_spp: int, tol: f
     return out[:n].clone(), n      # (the buffer is the next call's too)
 
 
+# ---------------------------------------------------------------------------------------- reprojection into a nearby view
+def world_to_camera(T) -> "np.ndarray":
+    """Wd (3,4) float32 of a camera-to-world pose T (4,4): the inverse taken in fp64 on the host, rounded once (include/stnerf.h)."""
+    import numpy as np
+    Tm = np.asarray(torch.as_tensor(T).detach().cpu().numpy(), dtype=np.float64).reshape(4, 4)
+    return np.ascontiguousarray(np.linalg.inv(Tm)[:3, :4].astype(np.float32))
+
+
+def reproject_keys(h_d: int, w_d: int, device="cuda") -> Tensor:
+    """The splat target of an h_d x w_d view, all empty: (h_d w_d,) int64 holding the all-ones 64-bit key."""
+    return torch.full((h_d * w_d,), -1, dtype=torch.int64, device=device)
+
+
+def reproject_splat(keys: Tensor, K_s: Tensor, T_s: Tensor, h_s: int, w_s: int, t_src: Tensor, id_base: int, K_d: Tensor, T_d: Tensor,
+                    h_d: int, w_d: int, z_min: float = 1e-6) -> Tensor:
+    """Splat the rows of one source view into ``keys`` IN PLACE (stnerf_reproject_splat): row q of t_src (n,), n <= h_s w_s, is
+    the ray parameter of pixel q of the source; the nearest surface wins a destination pixel, on a tie the lower id.  -> keys."""
+    import numpy as np
+    if t_src.dim() != 1:
+        raise ValueError(f"reproject_splat: t must be (n,), got {tuple(t_src.shape)}")
+    kinv = torch.inverse(K_s.detach().to("cpu", torch.float32)).contiguous()   # as generate_rays takes it
+    Ts = torch.as_tensor(T_s, dtype=torch.float32).detach().cpu().contiguous()
+    Kd = K_d.detach().to("cpu", torch.float32).contiguous()
+    Td = torch.as_tensor(T_d, dtype=torch.float32).detach().cpu().contiguous()
+    Wd = world_to_camera(Td)
+    od = np.ascontiguousarray(Td.numpy()[:3, 3])
+    hip.check(hip.lib().stnerf_reproject_splat((C.c_float * 9)(*kinv.reshape(-1).tolist()), (C.c_float * 16)(*Ts.reshape(-1).tolist()),
+                                               h_s, w_s, hip.dptr(t_src, name="t"), t_src.shape[0], int(id_base),
+                                               (C.c_float * 9)(*Kd.reshape(-1).tolist()), (C.c_float * 12)(*Wd.reshape(-1).tolist()),
+                                               (C.c_float * 3)(*od.tolist()), h_d, w_d, float(z_min), hip.dptr(keys, torch.int64, "keys"),
+                                               hip.stream_ptr()), "stnerf_reproject_splat")
+    return keys
+
+
+def reproject_resolve(keys: Tensor, h_d: int, w_d: int, rel: float, values: Sequence[Tensor], out=None):
+    """Resolve splatted keys (stnerf_reproject_resolve): values = the sources' rows, (n_s, C) float32 device views with dense
+    columns, in the order of their id bases.  -> (values (h_d w_d, C), t (h_d w_d,), src (h_d w_d,) int32); a hole has zeros, a NaN
+    t and src = -1.  ``out``: the three buffers to write instead of new ones."""
+    if not 1 <= len(values) <= hip.REPROJECT_MAX_SOURCES:
+        raise ValueError(f"reproject_resolve: {len(values)} sources (1..{hip.REPROJECT_MAX_SOURCES})")
+    C_ = values[0].shape[1] if values[0].dim() == 2 else 0
+    table = (hip.ReprojectSource * len(values))()
+    for i, v in enumerate(values):
+        if v.dim() != 2 or v.shape[1] != C_:
+            raise ValueError(f"reproject_resolve: every source must be (n, {C_}), got {tuple(v.shape)}")
+        vp, stride = _mat(v, "values")
+        table[i].values, table[i].row_stride, table[i].n = vp.value, (stride if v.shape[0] > 1 else C_), v.shape[0]
+    P = h_d * w_d
+    dev = keys.device
+    vals, t, src = out if out is not None else (torch.empty(P, C_, dtype=torch.float32, device=dev),
+                                                torch.empty(P, dtype=torch.float32, device=dev),
+                                                torch.empty(P, dtype=torch.int32, device=dev))
+    hip.check(hip.lib().stnerf_reproject_resolve(hip.dptr(keys, torch.int64, "keys"), h_d, w_d, float(rel), table, len(values), C_,
+                                                 hip.dptr(vals, name="values_out"), hip.dptr(t, name="t_out"),
+                                                 hip.dptr(src, torch.int32, "src"), hip.stream_ptr()), "stnerf_reproject_resolve")
+    return vals, t, src
+
+
+def reproject_holes(src: Tensor) -> Tuple[Tensor, int]:
+    """The pixels with src < 0, ascending (stnerf_reproject_holes).  -> (holes (n,) int32 on the device, n): n is a Python int,
+    read back with one small D2H."""
+    P = src.shape[0]
+    nbytes = hip.lib().stnerf_reproject_holes_workspace_bytes(P)
+    if nbytes < 0:
+        hip.check(int(nbytes), "stnerf_reproject_holes_workspace_bytes")
+    dev = src.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(P, dtype=torch.int32, device=dev)
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    hip.check(hip.lib().stnerf_reproject_holes(hip.dptr(src, torch.int32, "src"), P, hip.dptr(out, torch.int32), hip.dptr(n_out, torch.int32),
+                                               hip.dptr(work, torch.uint8), work.numel(), hip.stream_ptr()), "stnerf_reproject_holes")
+    n = int(n_out.item())
+    return out[:n], n
+
+
+def reproject(sources, K_d: Tensor, T_d: Tensor, h_d: int, w_d: int, rel: float, z_min: float = 1e-6):
+    """Warp the rows of up to four source views into the view (K_d, T_d, h_d, w_d): splat every source, resolve, list the holes.
+    sources: a list of (K, T, h, w, values (n,C), t (n,)) -- row q belongs to pixel q of its view, t is its ray parameter (NaN or
+    <= 0: absent).  -> (values (h_d w_d, C), t (h_d w_d,), src (h_d w_d,) int32, holes (n_holes,) int32 ascending, n_holes).
+    src is the id of the row a pixel took: its row number plus the row counts of the sources before it; -1 for a hole."""
+    if not 1 <= len(sources) <= hip.REPROJECT_MAX_SOURCES:
+        raise ValueError(f"reproject: {len(sources)} sources (1..{hip.REPROJECT_MAX_SOURCES})")
+    keys = reproject_keys(h_d, w_d, sources[0][4].device)
+    base = 0
+    for (K_s, T_s, h_s, w_s, values, t_src) in sources:
+        if values.dim() != 2 or tuple(t_src.shape) != (values.shape[0],):
+            raise ValueError(f"reproject: a source needs values (n,C) and t (n,), got {tuple(values.shape)} and {tuple(t_src.shape)}")
+        reproject_splat(keys, K_s, T_s, h_s, w_s, t_src, base, K_d, T_d, h_d, w_d, z_min)
+        base += values.shape[0]
+    vals, t, src = reproject_resolve(keys, h_d, w_d, rel, [s[4] for s in sources])
+    holes, n_holes = reproject_holes(src)
+    return vals, t, src, holes, n_holes
+
+
 # ---------------------------------------------------------------------------------------- 8(f)4: training GEMMs
 def _mat(t: Tensor, name: str, vec: bool = False):
     """(pointer, row stride) of a 2-D fp32 device view whose columns are dense; `vec`: read with 16-byte vectors."""

@@ -547,6 +547,54 @@ def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, densit
     return model.as_reference_tuple(unpack_outputs(torch.cat([state.mean, bits], 1), l, "fine")), stats
 
 
+def render_view_reprojected(model, K, T, h: int, w: int, frame_ids, plates, spec, density_threshold=0.0, bkgd_density_threshold=0.0,
+                            chuncks: int = 512 * 7, device="cuda", occluder=None, lens=None, only_coarse: bool = False):
+    """One view whose background is warped from the key plates of nearby views (``stnerf_amd.reproject``)
+    -> (5-tuple, scene, occluded, stats), the first three as ``render_view(occluder=)`` returns them; the frame is
+    ``occluded["mixed"]``.  Inference only, one rank, the fused pipeline only.
+
+    1. ``ops.reproject`` of the plates' rows into this view (``spec.rel``: the guard) -- unless a plate IS of this view (the same K,
+    T, h, w bit for bit): then the warp is the identity by definition, that plate's rows are taken as they are and nothing is
+    launched or rendered for the background.  2. The holes' rays come from
+    ``ops.generate_rays(pixels=holes)``, are rendered with only layer 0 shown, turned into plate rows by the function that made
+    the keys' (``reproject.plate_rows``) and scattered into the warped rows.  3. ``model.render_rays_occluded`` of the view's rays
+    with the finished plate as the occluder and layer 0 hidden, which skips its networks; the caches, occupancy grids,
+    termination, instances, rotation and opacity of the performers act inside that call as in any other.
+    ``display_layers``, the view key and the seed are restored in a ``finally``.  A plate whose identity differs from this
+    frame's (``reproject.background_identity``) is refused with ValueError.
+
+    stats: ``holes`` and ``reused`` (pixels rendered and pixels warped; they add up to h w), ``rays_background`` (the layer-0
+    rays this frame cost), ``keys`` (the plates' path indices), Python values."""
+    from stnerf_amd import ops, reproject as rp
+    spec = rp.as_spec(spec)
+    what = "render_view_reprojected"
+    if occluder is not None:
+        raise ValueError(f"{what} with an occluder of the caller's: the warped background IS the frame's occluder plate and a call "
+                         "composites one; render the frame without reproject= or without occluder=")
+    if only_coarse:
+        raise ValueError(f"{what} with only_coarse: the plate is layer 0's fine render; render coarse previews without reproject=")
+    if _checked_lens(lens, K, h, w) is not None:
+        raise ValueError(f"{what} with an enabled lens: the warp is a pinhole's; render through a lens without reproject=")
+    rp.refuse(model, what)
+    frame_ids = [float(f) for f in frame_ids]
+    rows, holes, n_holes, _ = rp.warp_plates(model, K, T, h, w, frame_ids, plates, spec, density_threshold, bkgd_density_threshold,
+                                             chuncks, device)
+    rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device)
+    saved_key, saved_ids, saved_seed = getattr(model, "view_key", None), getattr(model, "view_frame_ids", None), model.seed
+    shown = model.display_layers[0]
+    try:
+        model.display_layers[0] = 0
+        model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids), _view_frame_ids(model, frame_ids)
+        with torch.no_grad():
+            five, scene, occluded = model.render_rays_occluded(rays, rows, **rp.view_thresholds(h, w, chuncks, density_threshold,
+                                                                                                bkgd_density_threshold))
+    finally:
+        model.display_layers[0] = shown
+        model.view_key, model.view_frame_ids, model.seed = saved_key, saved_ids, saved_seed
+    stats = dict(holes=n_holes, reused=h * w - n_holes, rays_background=n_holes, keys=tuple(p.index for p in plates))
+    return five, scene, occluded, stats
+
+
 def render_view_share(model, K, T, h: int, w: int, frame_ids, rank: int, world: int, density_threshold=0.0,
                       bkgd_density_threshold=0.0, chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda",
                       mode: str = "all") -> torch.Tensor:

@@ -34,7 +34,7 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False, accumulate=None, lens=None):
+                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -103,6 +103,27 @@ class LayeredNeuralRenderer:
         # unchanged.  Not in the reference (keyword-only, off by default)
         from stnerf_amd.lens import as_lens
         self.lens = as_lens(lens)
+        # reproject: an stnerf_amd.reproject.ReprojectSpec or the dict of its arguments -- the background of every frame of
+        # render_path / render_path_walking is warped from key plates at path indices 0, N, 2N, ... (N = key_every), rendered
+        # lazily and dropped once passed; only the holes of the warp are rendered, and the finished plate is composited into the
+        # scene with layer 0 hidden (render_pose's `reproject`).  Every frame goes through the plate path, the
+        # keys included (at a key's own camera the warp is the identity), so the look does not pop between keys and in-betweens.
+        # The frame's stats go to on_frame as the keyword `reprojected` and are kept in reproject_stats.  Approximate; it does not
+        # combine with accumulate, an occluder or an enabled lens.  Not in the reference (keyword-only, off by default)
+        self.reproject = None
+        if reproject is not None:
+            from stnerf_amd.reproject import as_spec as as_reproject_spec
+            self.reproject = as_reproject_spec(reproject)
+            if self.accumulate is not None:
+                raise ValueError("reproject= with accumulate=: plates for the passes of a progressive frame are out of scope")
+            if self.occluder is not None:
+                raise ValueError("reproject= with occluder=: the warped background is the frame's occluder plate and a call composites one")
+            if self.lens is not None and self.lens.enabled:
+                raise ValueError("reproject= with an enabled lens: the warp is a pinhole's")
+            if self.scene_passes:
+                raise ValueError("reproject= with scene_passes: layer 0 is hidden in a reprojected frame; its passes are in the stats")
+        self.reproject_stats = []
+        self._plates = {}
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -403,17 +424,42 @@ class LayeredNeuralRenderer:
 
     # ---- rendering -------------------------------------------------------------------------------------------
     def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None,
-                    accumulate=None, lens=None):
+                    accumulate=None, lens=None, reproject=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
         element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
         also holds the occluded results; with ``accumulate`` = a spec the frame is a progressive multi-sample one and the fifth
-        element is its ``stats``.  ``lens``: the camera's lens for this frame (default: the renderer's ``lens``)."""
+        element is its ``stats``.  ``lens``: the camera's lens for this frame (default: the renderer's ``lens``).
+        ``reproject`` = (spec, plates): the background is warped from those key plates (stnerf_amd.render.render_pose); the fifth
+        element is the frame's ``stats``."""
         lens = self.lens if lens is None else lens
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
                             bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
                             **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}),
                             **(dict(accumulate=accumulate) if accumulate is not None else {}),
-                            **(dict(lens=lens) if lens is not None else {}))
+                            **(dict(lens=lens) if lens is not None else {}),
+                            **(dict(reproject=reproject) if reproject is not None else {}))
+
+    def _key_plates(self, idx, density_threshold, bkgd_density_threshold):
+        """The key plates frame ``idx`` uses (``ReprojectSpec.keys_of``) -> (plates, how many were rendered for this frame).  A
+        key is rendered on first use, at its own pose, under the model's state and frame ids of the frame that needs it; one whose
+        identity differs from this frame's (a time-dependent background, an edit of layer 0) is rendered again -- re-keyed; keys
+        the path has passed are dropped."""
+        from stnerf_amd.reproject import BackgroundPlate, background_identity
+        keys = self.reproject.keys_of(idx, len(self.poses))
+        for k in [k for k in self._plates if k < keys[0]]:
+            del self._plates[k]
+        frame_ids = [0.0] * self.total_layers
+        for layer_id, frame_id in self.layer_frame_pairs[idx]:
+            frame_ids[layer_id] = float(frame_id)
+        ident = background_identity(self.model, frame_ids, self.height, self.width, 512 * 7, density_threshold, bkgd_density_threshold)
+        rendered = 0
+        for k in keys:
+            plate = self._plates.get(k)
+            if plate is None or plate.identity != ident:
+                self._plates[k] = BackgroundPlate.render(self.model, self.Ks[k], self.poses[k], self.height, self.width, frame_ids,
+                                                         self.reproject, density_threshold, bkgd_density_threshold, index=k)
+                rendered += 1
+        return [self._plates[k] for k in keys], rendered
 
     def _render_frame(self, idx, density_threshold, bkgd_density_threshold, inverse_y_axis):
         """Frame ``idx`` of the path -> (color, depth, color_layer, depth_layer, passes): ``render_pose``, flipped on request;
@@ -422,7 +468,18 @@ class LayeredNeuralRenderer:
         passes = None
         self._frame_stats = None
         occ = self.occluder(idx, self.poses[idx], self.Ks[idx]) if self.occluder is not None else None
-        if self.accumulate is not None:
+        if self.reproject is not None:
+            plates, rendered = self._key_plates(idx, density_threshold, bkgd_density_threshold)
+            color, depth, color_layer, depth_layer, stats = self.render_pose(self.poses[idx], self.Ks[idx], self.layer_frame_pairs[idx],
+                                                                            density_threshold, bkgd_density_threshold,
+                                                                            reproject=(self.reproject, plates))
+            stats = dict(stats, keys_rendered=rendered, rays_keys=rendered * self.height * self.width)
+            if inverse_y_axis:
+                flip = lambda v: torch.flip(v, [0]) if torch.is_tensor(v) else type(v)(flip(i) for i in v)
+                stats["passes"] = {k: flip(v) for k, v in stats["passes"].items()}
+            self._frame_stats = stats
+            self.reproject_stats.append({k: v for k, v in stats.items() if k != "passes"})
+        elif self.accumulate is not None:
             color, depth, color_layer, depth_layer, stats = self.render_pose(self.poses[idx], self.Ks[idx], self.layer_frame_pairs[idx],
                                                                             density_threshold, bkgd_density_threshold,
                                                                             scene_passes=self.scene_passes, occluder=occ,
@@ -454,6 +511,8 @@ class LayeredNeuralRenderer:
         kw = dict(scene=passes) if self.scene_passes else {}
         if self.accumulate is not None:
             kw["accumulated"] = self._frame_stats
+        if self.reproject is not None:
+            kw["reprojected"] = self._frame_stats
         if self.occluder is not None:
             has = passes is not None and "color_occluded" in passes
             kw["occluded"] = {k: v for k, v in passes.items() if "occlude" in k} if has else None
@@ -464,7 +523,7 @@ class LayeredNeuralRenderer:
             self.images_occluded.append(passes["color_occluded"].cpu())
 
     def _keep_spp(self):
-        if self._frame_stats is not None:
+        if self._frame_stats is not None and "spp" in self._frame_stats:
             self.spp_maps.append(self._frame_stats["spp"].cpu())
 
     def _keep_scene(self, passes, layer_id):
@@ -487,6 +546,7 @@ class LayeredNeuralRenderer:
         self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.images_occluded = []
         self.spp_maps = []
+        self.reproject_stats, self._plates = [], {}
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -532,6 +592,7 @@ class LayeredNeuralRenderer:
         self.alphas_scene = [[] for _ in range(self.total_layers)]
         self.images_occluded = []
         self.spp_maps = []
+        self.reproject_stats, self._plates = [], {}
         self.image_num = 0
         for idx in range(len(self.poses)):
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,

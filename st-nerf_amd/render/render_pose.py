@@ -15,7 +15,7 @@ from stnerf_amd.parallel import render_view, total_layers
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
                 density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
-                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None):
+                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None, reproject=None):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -53,7 +53,43 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     ``lens`` = an ``stnerf_amd.lens.Lens`` (or the dict of its arguments): the camera's lens.  Its distortion
     bends the rays of this frame so that it lines up with a plate shot through that lens -- nothing is resampled, and scene passes,
     an occluder and the caches work as without it.  Its ``aperture`` gives depth of field and needs ``accumulate`` (ValueError
-    without): every pass then starts its rays at another point of the lens.  One rank only."""
+    without): every pass then starts its rays at another point of the lens.  One rank only.
+
+    ``reproject`` = (spec, plates): the background of this frame is warped from the key plates of nearby views
+    (``stnerf_amd.reproject``: a ``ReprojectSpec`` or the dict of its arguments, a list of ``BackgroundPlate``), only its holes
+    are rendered, and the finished plate is composited into the scene as an occluder with layer 0 hidden
+    (``parallel.render_view_reprojected``).  color and depth are the occluded mixed image's; the per-layer
+    lists are the render's own (layer 0 was hidden in it).  A fifth element ``stats`` is returned: ``holes``,
+    ``reused``, ``rays_background``, ``keys``, and ``passes`` = the dict an occluder returns.  It does not combine with
+    ``accumulate``, an occluder of the caller's or an enabled lens (ValueError).  Approximate; inference only; one rank only."""
+    if reproject is not None:
+        from stnerf_amd.parallel import render_view_reprojected
+        if accumulate is not None:
+            raise ValueError("render_pose(reproject=...) with accumulate=: plates for the passes of a progressive frame are out of "
+                             "scope; render the frame with one of the two")
+        if scene_passes:
+            raise ValueError("render_pose(reproject=...) with scene_passes: layer 0 is hidden in a reprojected frame, so its pass "
+                             "would be empty; the passes of the frame are in stats[\"passes\"]")
+        spec, plates = reproject
+        frame_ids = [0.0] * total_layers(model)
+        for layer_id, frame_id in layer_frame_pair:
+            frame_ids[layer_id] = float(frame_id)
+        out = render_view_reprojected(model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height,
+                                      width, frame_ids, plates, spec, density_threshold, bkgd_density_threshold, device=device,
+                                      **(dict(occluder=occluder) if occluder is not None else {}),
+                                      **(dict(lens=lens) if lens is not None else {}))
+        (stage2, _, stage2_layer, _, _), scene, occluded, stats = out
+        img = lambda t, c: t.reshape(height, width, c)
+        mixed, share = occluded["mixed"], occluded["share"]
+        passes = dict(color_scene=[img(t[0], 3) for t in scene], alpha_scene=[img(t[2], 1) for t in scene],
+                      depth_scene=[img(t[1], 1) / far for t in scene],
+                      color_occluded=img(mixed[0], 3), alpha_occluded=img(mixed[2], 1), depth_occluded=img(mixed[1], 1) / far,
+                      color_scene_occluded=[img(t[0], 3) for t in occluded["scene"]],
+                      alpha_scene_occluded=[img(t[2], 1) for t in occluded["scene"]],
+                      depth_scene_occluded=[img(t[1], 1) / far for t in occluded["scene"]],
+                      occluder_share=(img(share[0], 3), img(share[2], 1), img(share[1], 1) / far))
+        return (img(mixed[0], 3), img(mixed[1], 1).clamp_min(0) / far, [img(t[0], 3) for t in stage2_layer],
+                [img(t[1], 1) / far for t in stage2_layer], dict(stats, passes=passes))
     if accumulate is not None:
         from stnerf_amd.parallel import render_view_accumulated
         frame_ids = [0.0] * total_layers(model)

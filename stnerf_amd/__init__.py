@@ -38,4 +38,7 @@ def __getattr__(name):
     if name == "Lens":
         from stnerf_amd.lens import Lens
         return Lens
+    if name in ("ReprojectSpec", "BackgroundPlate"):
+        from stnerf_amd import reproject
+        return getattr(reproject, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
