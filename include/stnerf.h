@@ -50,7 +50,7 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
  * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
- * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop), 13 copy_layer_raw_listed;
+ * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop | 2 the per-ray flavour), 13 copy_layer_raw_listed;
  * kind: the net kind for 0/1, to_dense for 6 and 13, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
  * 4 the row-list flavour (stnerf_mlp_stage_rows with at least one listed layer);
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
@@ -1032,9 +1032,36 @@ typedef struct stnerf_render_options {
     float* occluded_mixed;                  /* device [n][5]; required with an occluder, refused without                            */
     float* occluded_scene;                  /* device [n][l][5] or NULL                                                             */
     float* occluder_share;                  /* device [n][5] or NULL                                                                */
+    const uint8_t* bkgd_rays;               /* device uint8 [n] or NULL: the per-ray background mask (below); no named entry         */
 } stnerf_render_options;
-/* The workspace of stnerf_render_rays_opts for n rays.  Reads struct_size, samples, terminate and bkgd_grid (a grid with bits grows
- * the workspace as `background` != 0 does above); opts_host NULL = an all-zero record = stnerf_render_workspace_bytes. */
+/* ---- Per-ray background mask (csrc/background_rays.hip) --------------------------------------------------
+ * Opt-in, inference only, not in the reference: the caller says ray by ray whether layer 0 is evaluated -- what a frame needs whose
+ * background comes from another source on some of its rays (a reprojected plate) and from the networks on the others.
+ * bkgd_rays: device uint8 [n], one byte per ray of the call; nonzero = evaluate layer 0 on this ray.  NULL: the option is absent.
+ *   On a ray whose byte is 0 every sample of layer 0 gets raw = {0, 0, 0, 0}, four exact zero words, in BOTH stages, and no SpaceNet
+ *   or MotionNet row: what the background's sample cull does to a sample in an empty cell.  Layer 0's depths and points are made as
+ *   ever and take part in the merge as they do there; evaluated[0] stays 2.  On a ray whose byte is nonzero nothing changes.  Rays do
+ *   not influence each other, so both statements hold bit for bit.
+ *   It composes with the other two culls of layer 0 in the ONE rows launch layer 0 gets per stage: a sample is listed if and only if
+ *   its ray's byte is nonzero AND (with a bkgd_grid with bits) its point lies in an occupied cell or has a NaN coordinate AND (with
+ *   layer 0's fine stage terminated) !(t > t_stop[ray]).  only_coarse: the coarse stage's rows.
+ *   stnerf_render_workspace_bytes_opts: a non-NULL bkgd_rays grows the workspace as a grid with bits does (layer 0's row list).
+ *   STNERF_EINVAL before any launch: params->precision == 2; n1 + n2 > 256 or n > 2^23; a background cache (cache->mode) in CAPTURE
+ *   or REUSE -- the cached raw would hold the zeros of one mask.  The layer cache is unaffected.
+ * stnerf_background_ray_rows makes that row list: stnerf_background_rows' arguments, contract and host checks with two differences.
+ *   grid_host_or_null may be NULL: no cell test (a grid that is given must have bits);
+ *   ray_flags: device uint8 [n], required: a ray whose byte is 0 lists nothing, gets ns zero float4 and loads no point, no depth and
+ *   no grid word.  counts: a masked ray's samples are both tested and not listed.
+ * One launch of the same shape as the sibling's: runs of 16 rays per wave, the run's 16 flag bytes loaded once and balloted into a
+ * wave-uniform mask, ballots in scalar registers, one vector atomic add per run.  With every byte nonzero and a grid the listed set
+ * and the zeros are stnerf_background_rows'. */
+int stnerf_background_ray_rows(int64_t n, const float* xyz, int64_t xyz_ray_stride, int ns, const stnerf_occupancy* grid_host_or_null,
+                               const float* t_or_null, int64_t t_ray_stride, const float* t_stop_or_null, float* raw,
+                               int64_t raw_ray_stride, int32_t* row_list, int64_t capacity, int32_t* row_count,
+                               int64_t* counts_or_null, const uint8_t* ray_flags, stnerf_stream_t stream);
+/* The workspace of stnerf_render_rays_opts for n rays.  Reads struct_size, samples, terminate, bkgd_grid (a grid with bits grows
+ * the workspace as `background` != 0 does above) and bkgd_rays (non-NULL: the same growth); opts_host NULL = an all-zero record =
+ * stnerf_render_workspace_bytes. */
 int64_t stnerf_render_workspace_bytes_opts(int64_t n, int l, int n1, int n2, int only_coarse, const stnerf_render_options* opts_host);
 /* stnerf_render_rays with a record of options; opts_host NULL = no feature.  The one render call with a body: new callers should
  * use this pair. */

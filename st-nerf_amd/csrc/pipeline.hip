@@ -154,7 +154,7 @@ extern "C" int64_t stnerf_render_workspace_bytes_opts(int64_t n, int l, int n1, 
     }
     const stnerf_render_options& o = opts ? *opts : kNoOptions;
     return make_plan(n, l, n1, n2, only_coarse).bytes() +
-           make_row_plan(n, l, n1, n2, only_coarse, o.samples, o.terminate, o.bkgd_grid && o.bkgd_grid->bits).bytes(n);
+           make_row_plan(n, l, n1, n2, only_coarse, o.samples, o.terminate, (o.bkgd_grid && o.bkgd_grid->bits) || o.bkgd_rays).bytes(n);
 }
 
 // The mask the caller gets back is the reference's ray_mask (0 / 1): the sampler's "missed" hint (bit 1) served the compositor and
@@ -310,6 +310,7 @@ struct Call {
     int n_sampled;            // sample-culled layers
     bool flagged;             // a terminate flag is set
     bool bg;                  // the background's grid has bits
+    bool bg_rows;             // layer 0 walks a row list of its own launch: under its grid, under the per-ray mask, or both
     int cache_mode;           // the background cache's
     uint32_t lcap, lreuse;    // bit i: performer i's slices go to / come from its layer cache entry (a hidden layer's entry is ignored)
     uint32_t term;            // bit i: layer i's fine stage is terminated
@@ -376,7 +377,16 @@ int check_call(RENDER_PARAMS, const stnerf_render_options& o, Call* call) {
         STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23), "render_rays: the background grid packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
         STNERF_REQUIRE(((uintptr_t)o.bkgd_counts & 7) == 0, "render_rays: background counts must be 8-byte aligned");
     }
-    call->rows = make_row_plan(n, l, n1, n2, p->only_coarse, o.samples, o.terminate, bg);
+    if (o.bkgd_rays) {
+        STNERF_REQUIRE(p->precision != 2, "render_rays: the per-ray background mask is not built for precision 2 (one launch per network)");
+        STNERF_REQUIRE(S <= 256 && n <= ((int64_t)1 << 23),
+                       "render_rays: the per-ray background mask packs (ray << 8 | k): n1 + n2 <= 256, n <= 2^23 per call");
+        STNERF_REQUIRE(!o.cache || o.cache->mode == STNERF_BKGD_CACHE_OFF,
+                       "render_rays: the per-ray background mask with a background cache in CAPTURE or REUSE: the cached raw would hold the zeros of one mask");
+        STNERF_REQUIRE(((uintptr_t)o.bkgd_counts & 7) == 0, "render_rays: background counts must be 8-byte aligned");
+    }
+    const bool bg_rows = call->bg_rows = bg || o.bkgd_rays != nullptr;
+    call->rows = make_row_plan(n, l, n1, n2, p->only_coarse, o.samples, o.terminate, bg_rows);
     const int64_t need = make_plan(n, l, n1, n2, p->only_coarse).bytes() + call->rows.bytes(n);
     STNERF_REQUIRE(workspace_bytes >= need, "render_rays: workspace of %lld B, need %lld", (long long)workspace_bytes,
                    (long long)need);
@@ -451,6 +461,9 @@ int check_call(RENDER_PARAMS, const stnerf_render_options& o, Call* call) {
 // list.  Where layer 0's fine stage is terminated too the same launch takes t_f / t_stop, in place of stnerf_visibility_rows, and
 // the two share the list.  A background cache REUSE frame makes no rows launch (layer 0 is in no stage); a CAPTURE frame is culled
 // by the grid and still not terminated, so the cached raw is a function of view and grid only.
+// bkgd_rays: the same rows launch with one more test in front, the ray's byte (stnerf_background_ray_rows), run wherever the grid's
+// runs and also without a grid; a masked ray's layer-0 samples get their zeros in both stages and are on no list.  The background
+// cache is refused in CAPTURE and REUSE (check_call): the cached raw would hold the zeros of one mask.
 // layers: a performer's raw outputs are a function of the view and of its own inputs, as the background's are, so a layer in REUSE
 // is in no network stage: no stage item, no stand-alone MotionNet or MotionNet-reuse fill (its `reuse` bit is cleared), no ray-bias
 // and no rows launch -- its slices are copied in by stnerf_copy_layer_raw_listed where the background's are, for the rays the slice
@@ -526,10 +539,14 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const Call& c
                     e.motion_flags = i == 0 ? STNERF_MOTION_PLAIN_TIME : 0;
                     e.rotation = o.rot ? o.rot + i : nullptr;
                     const bool culled = o.samples && o.samples[i];
-                    if (i == 0 && c.bg) {   // the background's grid: every ray; with termination the same launch drops the hidden samples
+                    if (i == 0 && c.bg_rows) {   // the background's grid: every ray; with termination the same launch drops the hidden samples
                         const bool stop = fine && (term & 1);
-                        const int r1 = stnerf_background_rows(n, e.xyz, xs, ns, o.bkgd_grid, stop ? w.t_f : nullptr, (int64_t)l * ns, stop ? w.t_stop : nullptr,
-                                                              e.raw, ws_, w.row_list[0], row_cap, w.row_count, o.bkgd_counts, stream);
+                        const int r1 = o.bkgd_rays   // the per-ray mask: the same launch with the ray's byte in front, the grid optional
+                                           ? stnerf_background_ray_rows(n, e.xyz, xs, ns, c.bg ? o.bkgd_grid : nullptr, stop ? w.t_f : nullptr, (int64_t)l * ns,
+                                                                        stop ? w.t_stop : nullptr, e.raw, ws_, w.row_list[0], row_cap, w.row_count, o.bkgd_counts,
+                                                                        o.bkgd_rays, stream)
+                                           : stnerf_background_rows(n, e.xyz, xs, ns, o.bkgd_grid, stop ? w.t_f : nullptr, (int64_t)l * ns, stop ? w.t_stop : nullptr,
+                                                                    e.raw, ws_, w.row_list[0], row_cap, w.row_count, o.bkgd_counts, stream);
                         if (r1) return r1;
                     } else if (fine && (term >> i & 1)) {   // termination: the rows that are not hidden (and, sample-culled too, in an occupied cell)
                         const int r1 = stnerf_visibility_rows(e.ray_list, e.ray_count, n, i, e.xyz, xs, w.t_f + (int64_t)i * ns, (int64_t)l * ns, w.t_stop, ns,

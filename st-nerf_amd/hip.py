@@ -93,7 +93,8 @@ class RenderOptions(C.Structure):
                 ("samples", C.POINTER(C.c_int32)), ("sample_counts", C.c_void_p), ("tau", C.c_float),
                 ("terminate", C.POINTER(C.c_int32)), ("visibility_counts", C.c_void_p), ("bkgd_grid", C.POINTER(Occupancy)),
                 ("bkgd_counts", C.c_void_p), ("layers", C.POINTER(LayerCache)), ("mismatch", C.c_void_p), ("occluder", c_f32p),
-                ("occluder_stops", C.c_int32), ("occluded_mixed", c_f32p), ("occluded_scene", c_f32p), ("occluder_share", c_f32p)]
+                ("occluder_stops", C.c_int32), ("occluded_mixed", c_f32p), ("occluded_scene", c_f32p), ("occluder_share", c_f32p),
+                ("bkgd_rays", C.c_void_p)]
 
     def __init__(self, **fields):
         super().__init__(struct_size=C.sizeof(RenderOptions), **fields)
@@ -222,6 +223,8 @@ _PROTOS = {
     "stnerf_render_workspace_bytes_terminated": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "stnerf_background_rows": (C.c_int, [c_i64, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64, c_f32p, c_f32p, c_i64,
                                          C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stnerf_background_ray_rows": (C.c_int, [c_i64, c_f32p, c_i64, C.c_int, C.POINTER(Occupancy), c_f32p, c_i64, c_f32p, c_f32p, c_i64,
+                                             C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stnerf_render_workspace_bytes_background": (c_i64, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                          C.c_int]),
     "stnerf_scene_occluder": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), c_f32p, c_f32p,

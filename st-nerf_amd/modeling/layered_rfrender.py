@@ -663,7 +663,7 @@ class LayeredRFRender(nn.Module):
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
-                       scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False):
+                       scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False, background_rays=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache or the layer cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
@@ -673,7 +673,9 @@ class LayeredRFRender(nn.Module):
         background_id: the chunk group's background frame id, passed only while the attached grids cull the background: its grid
         is looked up or built and travels with the call as an argument of its own.  occluder: the piece's rows (n,5) of
         ``render_rays_occluded`` (with scene): three more tensors come back; occluder_stops: its opaque rows lower the stop depth of
-        the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached)."""
+        the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached).
+        background_rays: the piece's entries (n,) of the per-ray background mask; such a call neither captures into nor reuses the
+        background cache (the cached raw would hold the zeros of one mask); the layer cache is unaffected."""
         from stnerf_amd import hip
         n, l, dev = rays.shape[0], self.total_layers, rays.device
         p = self._render_params(rays.shape[1], pivot, retiming, only_coarse, thr, bthr, window)
@@ -686,11 +688,12 @@ class LayeredRFRender(nn.Module):
         kw.update(self._termination_keywords(dev, only_coarse, lkeys))
         need = ops.render_workspace_bytes(n, l, p.n1, p.n2, only_coarse, occupancy_samples=kw.get("occupancy_samples"),
                                           **(dict(terminate=kw["terminate"]) if "terminate" in kw else {}),
-                                          **(dict(background=True) if "background_grid" in kw else {}))
+                                          **(dict(background=True) if "background_grid" in kw else {}),
+                                          **(dict(background_rays=True) if background_rays is not None else {}))
         ws = getattr(self, "_workspace", None)
         if ws is None or ws.numel() < need or ws.device != dev:
             self._workspace = ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        cache = self._bkgd_cache if piece is not None else None
+        cache = self._bkgd_cache if piece is not None and background_rays is None else None
         key, cache_arg = self._plan_background_cache(cache, piece, window, retiming, only_coarse, pivot, n, dev)
         lc_kw, wanted, capturing = self._plan_layer_caches(lcache, lkeys, only_coarse, dev)
         kw.update(lc_kw)
@@ -699,6 +702,8 @@ class LayeredRFRender(nn.Module):
             kw.update(scene=True)
         if occluder is not None:
             kw.update(occluder=occluder, occluder_stops=bool(occluder_stops) and "terminate" in kw)
+        if background_rays is not None:
+            kw.update(background_rays=background_rays)
         table = self._layer_alpha_table()
         if table is not None:
             kw.update(layer_alpha=table)
@@ -845,20 +850,22 @@ class LayeredRFRender(nn.Module):
                                f"have fixed widths and a \"scene\" gather mode is out of scope; {how} (model.shard_views = False)")
 
     def render_rays_scene(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
-                          ref_chunk: Optional[int] = None):
+                          ref_chunk: Optional[int] = None, background_rays=None):
         """``render_rays`` plus the in-scene layer passes of the final stage -> (the reference 5-tuple, scene).  ``scene`` is a
         list of l (colour (n,3), depth (n,1), alpha (n,1)) triples: layer i's share of the MIXED image -- premultiplied colour,
         weighted depth and alpha with the other layers occluding it and being occluded by it (fine_layer[i] is layer i alone).
         Their sum over the layers is the mixed triple up to fp32 summation order; a hidden layer's is exact zeros.  The five
-        standard outputs are the bits of ``render_rays``.  Inference only: no backward is defined for the pass."""
+        standard outputs are the bits of ``render_rays``.  Inference only: no backward is defined for the pass.
+        ``background_rays``: the per-ray background mask of ``render_rays_raw``."""
         self._refuse_scene_call("render_rays_scene", "the in-scene layer passes have", "render the passes on one rank")
-        raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True)
+        raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True,
+                                    background_rays=background_rays)
         sc = raw[5]
         scene = [(sc[:, i, 0:3], sc[:, i, 3:4], sc[:, i, 4:5]) for i in range(self.total_layers)]
         return self.as_reference_tuple(raw[:5]), scene
 
     def render_rays_occluded(self, rays, occluder, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
-                             ref_chunk: Optional[int] = None, stops=False):
+                             ref_chunk: Optional[int] = None, stops=False, background_rays=None):
         """``render_rays_scene`` with a depth-tested occluder in the scene -> (the reference 5-tuple, scene, occluded).
         ``occluder`` (n,5) fp32 on the device: one row {r, g, b, a, z} per ray -- a CG prop, a title card, a plate with a z-buffer;
         z is a RAY PARAMETER, in the units of the depth outputs (``ops.ray_parameter`` turns a camera-space z-buffer into it); a row
@@ -870,7 +877,9 @@ class LayeredRFRender(nn.Module):
         ``stops=True``: an opaque row (a >= 1) also lowers early ray termination's stop depth to z, so the fine samples behind it
         are not evaluated; it needs an attached termination (``set_termination``; ValueError otherwise).  The occluded outputs keep
         their bits; the 5-tuple and ``scene`` become those of the terminated scene.  Without it they are the bits of
-        ``render_rays_scene``.  Inference only, one rank, the fused pipeline only."""
+        ``render_rays_scene``.  ``background_rays``: the per-ray background mask of ``render_rays_raw``, sliced as the occluder rows
+        are -- with it a frame takes its background from the occluder where a row is present and from the networks where it is not
+        (``stnerf_amd.reproject``).  Inference only, one rank, the fused pipeline only."""
         self._refuse_scene_call("render_rays_occluded", "the occluder composite has", "render on one rank")
         if stops and getattr(self, "_termination", None) is None:
             raise ValueError("render_rays_occluded(stops=True) without early ray termination: the occluder lowers the stop depth the "
@@ -879,7 +888,7 @@ class LayeredRFRender(nn.Module):
             raise ValueError(f"render_rays_occluded: the occluder must be a ({rays.shape[0]},5) tensor of (r, g, b, a, z) rows, got "
                              f"{tuple(occluder.shape) if torch.is_tensor(occluder) else type(occluder).__name__}")
         raw = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True,
-                                    occluder=occluder, occluder_stops=stops)
+                                    occluder=occluder, occluder_stops=stops, background_rays=background_rays)
         l = self.total_layers
         trip = lambda x: (x[..., 0:3], x[..., 3:4], x[..., 4:5])
         scene = [trip(raw[5][:, i]) for i in range(l)]
@@ -918,15 +927,25 @@ class LayeredRFRender(nn.Module):
             self.seed = (int(self.seed) + 1) & 0xFFFFFFFFFFFFFFFF   # the next call draws new jitter / resampling numbers
 
     def render_rays_raw(self, rays, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
-                        ref_chunk: Optional[int] = None):
+                        ref_chunk: Optional[int] = None, background_rays=None):
         """``render_rays`` before the outputs are cut into the reference's triples: the five tensors the library
-        wrote (what stnerf_amd.parallel packs into its one all-gather)."""
-        return self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk)
+        wrote (what stnerf_amd.parallel packs into its one all-gather).
+        ``background_rays``: None | an (n,) uint8 or bool device tensor, the per-ray background mask (include/stnerf.h states the
+        rule): the background is evaluated only on the rays whose entry is nonzero; on the others every sample of layer 0 has zero
+        network outputs in both stages -- what the background's sample cull does in an empty cell -- and costs no network row.  It
+        is sliced by launch piece and chunk group exactly as an occluder's rows are, and composes with a background grid and with
+        early ray termination.  Such a call neither captures into nor reuses the background cache; the layer cache is unaffected.
+        Inference only, one rank, the fused pipeline only."""
+        if background_rays is not None:
+            self._refuse_scene_call("render_rays_raw(background_rays=)", "the per-ray background mask has", "render on one rank")
+        return self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk,
+                                     background_rays=background_rays)
 
     def _render_rays_raw(self, rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=False, occluder=None,
-                         occluder_stops=False):
+                         occluder_stops=False, background_rays=None):
         """``render_rays_raw``; scene: a sixth tensor, the in-scene layer passes (n,l,5) of ``render_rays_scene``; occluder (with
-        scene): the rows (N,5) of ``render_rays_occluded``, three more tensors (occluded mixed, scene, share)."""
+        scene): the rows (N,5) of ``render_rays_occluded``, three more tensors (occluded mixed, scene, share); background_rays: the
+        (N,) per-ray background mask of ``render_rays_raw``."""
         if not rays.is_cuda:
             raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
         rays = rays.contiguous().float()
@@ -955,6 +974,18 @@ class LayeredRFRender(nn.Module):
             raise NotImplementedError("an occluder on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
                                       "op-by-op path, which has no occluder composite -- a render-time edit, as rotation is; render one "
                                       "background frame id per call")
+        if background_rays is not None:
+            if (not torch.is_tensor(background_rays) or tuple(background_rays.shape) != (N,)
+                    or background_rays.dtype not in (torch.uint8, torch.bool)):
+                raise ValueError(f"background_rays must be a ({N},) uint8 or bool tensor, one entry per ray, got "
+                                 f"{(tuple(background_rays.shape), background_rays.dtype) if torch.is_tensor(background_rays) else type(background_rays).__name__}")
+            if per_sample_bkgd_time:
+                raise NotImplementedError("a per-ray background mask on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call "
+                                          "takes the op-by-op path, which has no row lists -- a render-time edit, as rotation is; render one "
+                                          "background frame id per call")
+            if self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
+                raise ValueError("a per-ray background mask with mlp_schedule = 'per_net' (one launch per network): the mask walks row "
+                                 "lists in the persistent stage kernels; use mlp_schedule = 'stage' or drop background_rays")
         if scene and per_sample_bkgd_time:
             raise RuntimeError("render_rays_scene on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
                                "op-by-op path, which has no in-scene layer passes; render one background frame id per call")
@@ -993,6 +1024,8 @@ class LayeredRFRender(nn.Module):
         self._warn_if_eval_with_grad()
         if occluder is not None:
             occluder = occluder.to(rays.device, torch.float32).contiguous()
+        if background_rays is not None:
+            background_rays = background_rays.to(rays.device).contiguous()
         step = N if ref_chunk is None else ref_chunk
         rotated = self._rotation_specs() is not None
         groups = []  # (start, end, boxes, pivot[, rotations])
@@ -1049,7 +1082,8 @@ class LayeredRFRender(nn.Module):
                                                     **(dict(occupancy_ids=occ_ids[gi]) if occ_ids is not None else {}),
                                                     **(dict(background_id=bg_ids[gi]) if bg_ids is not None else {}),
                                                     **(dict(occluder=occluder[s:e], occluder_stops=occluder_stops)
-                                                       if occluder is not None else {})))
+                                                       if occluder is not None else {}),
+                                                    **(dict(background_rays=background_rays[s:e]) if background_rays is not None else {})))
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range((9 if occluder is not None else 6) if scene else 5))
         self.advance_seed()

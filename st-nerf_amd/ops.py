@@ -690,14 +690,17 @@ _SOME_GRID[0].bits = C.addressof(_SOME_GRID)
 
 
 def render_workspace_bytes(n: int, l: int, n1: int, n2: int, only_coarse: bool, occupancy_samples=None, terminate=None,
-                           background: bool = False) -> int:
+                           background: bool = False, background_rays: bool = False) -> int:
     """Bytes of ``render_rays``'s workspace.  ``occupancy_samples``: the per-layer flags of the sample cull or None -- only
     with a flag set does the workspace grow, by the flagged layers' row lists (stnerf_render_workspace_bytes_samples).
     ``terminate``: the per-layer flags of early ray termination or None -- with a flag set (and a fine stage) the workspace grows
     by the stop depths and the flagged layers' fine row lists (stnerf_render_workspace_bytes_terminated).
     ``background``: a background grid will be given -- the workspace grows by layer 0's row list unless termination has given it one
-    (stnerf_render_workspace_bytes_background)."""
+    (stnerf_render_workspace_bytes_background).  ``background_rays``: a per-ray background mask will be given -- the same growth
+    (the query reads only whether stnerf_render_options.bkgd_rays is set)."""
     opts = hip.RenderOptions()
+    if background_rays:
+        opts.bkgd_rays = C.addressof(_SOME_GRID)
     if occupancy_samples is not None and any(occupancy_samples):
         opts.samples = _layer_flags(occupancy_samples, l, "occupancy_samples")
     if terminate is not None:
@@ -894,6 +897,48 @@ def background_rows(xyz: Tensor, raw: Tensor, grid, t: Optional[Tensor] = None, 
     return row_list, row_count
 
 
+def background_ray_rows(xyz: Tensor, raw: Tensor, ray_flags: Tensor, grid=None, t: Optional[Tensor] = None, t_stop: Optional[Tensor] = None,
+                        row_list: Optional[Tensor] = None, row_count: Optional[Tensor] = None, counts: Optional[Tensor] = None):
+    """Layer 0's row list of one stage under a per-ray mask (stnerf_background_ray_rows; include/stnerf.h states the rule):
+    ``background_rows`` with ``ray_flags`` (n,) uint8 or bool in front of its tests and the grid optional.  Sample k of ray r is
+    listed when ``ray_flags[r]`` is nonzero and -- with ``grid`` = (bits, res, lo, inv_cell) -- its point lies in an occupied cell (or
+    has a NaN coordinate) and -- with t (n,ns) and t_stop (n,) -- ``not t[r, k] > t_stop[r]``; the others get four zero words in
+    raw.  A ray whose flag is zero lists nothing and loads nothing.  counts: int64 (2,) | None accumulates (samples tested, not
+    listed).  -> (row_list, row_count)."""
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
+        raise ValueError(f"background_ray_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
+    n, ns = xyz.shape[0], xyz.shape[1]
+    flags = _ray_flags(ray_flags, n, "background_ray_rows")
+    if t is not None and tuple(t.shape) != (n, ns):
+        raise ValueError(f"background_ray_rows: t must be ({n},{ns}), got {tuple(t.shape)}")
+    if t_stop is not None and tuple(t_stop.shape) != (n,):
+        raise ValueError(f"background_ray_rows: t_stop must be ({n},), got {tuple(t_stop.shape)}")
+    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
+    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
+    tp, ts = _strided_view_ptr(t, (ns,), "t") if t is not None else (C.c_void_p(0), 0)
+    if row_list is None:
+        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
+    if row_count is None:
+        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
+    if counts is not None and tuple(counts.shape) != (2,):
+        raise ValueError(f"background_ray_rows: counts must be int64 (2,), got {tuple(counts.shape)}")
+    entry = None if grid is None else _occupancy_table([grid], 1)
+    hip.check(hip.lib().stnerf_background_ray_rows(n, xp, xs, ns, entry, tp, ts, hip.dptr(t_stop, name="t_stop"), rp, rs,
+                                                   hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
+                                                   hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+                                                   hip.dptr(flags, torch.uint8, "ray_flags"), hip.stream_ptr()), "stnerf_background_ray_rows")
+    return row_list, row_count
+
+
+def _ray_flags(flags: Tensor, n: int, what: str) -> Tensor:
+    """A per-ray mask as the library takes it: (n,) uint8, contiguous, on the device (bool is reinterpreted, not copied)."""
+    if not torch.is_tensor(flags) or tuple(flags.shape) != (n,) or flags.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{what}: the per-ray background mask must be a ({n},) uint8 or bool tensor, got "
+                         f"{(tuple(flags.shape), flags.dtype) if torch.is_tensor(flags) else type(flags).__name__}")
+    flags = flags.contiguous()
+    return flags.view(torch.uint8) if flags.dtype == torch.bool else flags
+
+
 def ray_stop(t: Tensor, merged_weights: Tensor, tau: float) -> Tensor:
     """The stop depth of early ray termination (stnerf_ray_stop; include/stnerf.h states the rule): t (n,l,n1) coarse depths and
     merged_weights (n,l,n1), ``composite_scene``'s coarse merged weights, -> t_stop (n,): the depth of the merged sample after the
@@ -944,7 +989,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
                 visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None,
                 layer_caches=None, layer_mismatch: Optional[Tensor] = None, occluder: Optional[Tensor] = None,
-                occluder_stops: bool = False):
+                occluder_stops: bool = False, background_rays: Optional[Tensor] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -975,7 +1020,12 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     ``occluder``: (n,5) rows {r, g, b, a, z} | None, a depth-tested occluder composited into the final stage (stnerf_render_rays_occluded;
     include/stnerf.h states the rules; z in ray-parameter units, ``ray_parameter``).  It needs ``scene=True`` and appends
     occluded_mixed (n,5), occluded_scene (n,l,5) and occluder_share (n,5) to the returned tuple.  ``occluder_stops``: an opaque row
-    also lowers the stop depth of early ray termination (needs a ``terminate`` flag); the three occluded outputs keep their bits."""
+    also lowers the stop depth of early ray termination (needs a ``terminate`` flag); the three occluded outputs keep their bits.
+    ``background_rays``: (n,) uint8 or bool | None, the per-ray background mask (stnerf_render_options.bkgd_rays; include/stnerf.h
+    states the rule): layer 0 is evaluated only on the rays whose entry is nonzero, the others get zero outputs for it in both
+    stages.  It composes with ``background_grid`` and with termination of layer 0 in the one rows launch layer 0 gets per stage.  The
+    workspace is ``render_workspace_bytes(..., background_rays=True)``.  The library refuses precision 2 and a background cache in
+    CAPTURE or REUSE."""
     n, l = rays.shape[0], params.l
     if occluder is not None:
         if not scene:
@@ -1033,6 +1083,9 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     opts.mismatch = hip.dptr(layer_mismatch, torch.int64, "layer_mismatch")
     if background_grid is not None:   # (an entry whose bits are None is no grid)
         opts.bkgd_grid = (hip.Occupancy * 1)() if background_grid[0] is None else _occupancy_table([background_grid], 1)
+    if background_rays is not None:
+        background_rays = _ray_flags(background_rays, n, "render_rays")
+        opts.bkgd_rays = hip.dptr(background_rays, torch.uint8, "background_rays")
     if layer_caches is not None:
         opts.layers = _layer_cache_table(layer_caches, l, params.n1, params.n2, bool(params.only_coarse))
     occ_out = None

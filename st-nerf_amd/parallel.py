@@ -558,13 +558,23 @@ def render_view_reprojected(model, K, T, h: int, w: int, frame_ids, plates, spec
     launched or rendered for the background.  2. The holes' rays come from
     ``ops.generate_rays(pixels=holes)``, are rendered with only layer 0 shown, turned into plate rows by the function that made
     the keys' (``reproject.plate_rows``) and scattered into the warped rows.  3. ``model.render_rays_occluded`` of the view's rays
-    with the finished plate as the occluder and layer 0 hidden, which skips its networks; the caches, occupancy grids,
-    termination, instances, rotation and opacity of the performers act inside that call as in any other.
+    with the finished plate as the occluder and ``display_layers[0] = 0``.  That flag does NOT skip layer 0's networks: the
+    pipeline evaluates the background on every ray of every call, so this step costs a full frame and composites the real
+    background beside the plate (the plate sits at the background's expected depth and the colours agree).  The caches, occupancy
+    grids, termination, instances, rotation and opacity of the performers act inside that call as in any other.
     ``display_layers``, the view key and the seed are restored in a ``finally``.  A plate whose identity differs from this
     frame's (``reproject.background_identity``) is refused with ValueError.
 
+    ``spec.exclusive``: one source of background per ray.  1. as above.  2. no hole is rendered separately (no
+    ``generate_rays(pixels=)``, no layer-0-only render, no scatter).  3. ``flags`` = 1 where the row is absent by the occluder's own
+    rule (a <= 0 or NaN, or z not finite: the holes and the plate rows below ``a_min``), and
+    ``model.render_rays_occluded(rays, rows, background_rays=flags)`` with ``display_layers`` untouched: the networks supply the
+    background on the flagged rays, the plate on the others, where layer 0 costs no network row and has no share in the frame.  A
+    hole ray is keyed by its pixel like every other ray of the frame.
+
     stats: ``holes`` and ``reused`` (pixels rendered and pixels warped; they add up to h w), ``rays_background`` (the layer-0
-    rays this frame cost), ``keys`` (the plates' path indices), Python values."""
+    rays this frame cost), ``keys`` (the plates' path indices), Python values.  Exclusive: ``holes`` = ``rays_background`` = the
+    flagged rays, ``reused`` the rest."""
     from stnerf_amd import ops, reproject as rp
     spec = rp.as_spec(spec)
     what = "render_view_reprojected"
@@ -578,16 +588,22 @@ def render_view_reprojected(model, K, T, h: int, w: int, frame_ids, plates, spec
     rp.refuse(model, what)
     frame_ids = [float(f) for f in frame_ids]
     rows, holes, n_holes, _ = rp.warp_plates(model, K, T, h, w, frame_ids, plates, spec, density_threshold, bkgd_density_threshold,
-                                             chuncks, device)
+                                             chuncks, device, render_holes=not spec.exclusive)
     rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device)
     saved_key, saved_ids, saved_seed = getattr(model, "view_key", None), getattr(model, "view_frame_ids", None), model.seed
     shown = model.display_layers[0]
+    mask_kw = {}
+    if spec.exclusive:     # the networks where the plate has no row, the plate elsewhere
+        flags = rp.absent_rows(rows).to(torch.uint8)
+        n_holes = int(flags.sum().item())
+        mask_kw = dict(background_rays=flags)
     try:
-        model.display_layers[0] = 0
+        if not spec.exclusive:
+            model.display_layers[0] = 0
         model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids), _view_frame_ids(model, frame_ids)
         with torch.no_grad():
             five, scene, occluded = model.render_rays_occluded(rays, rows, **rp.view_thresholds(h, w, chuncks, density_threshold,
-                                                                                                bkgd_density_threshold))
+                                                                                                bkgd_density_threshold), **mask_kw)
     finally:
         model.display_layers[0] = shown
         model.view_key, model.view_frame_ids, model.seed = saved_key, saved_ids, saved_seed

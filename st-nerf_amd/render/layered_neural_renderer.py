@@ -109,7 +109,9 @@ class LayeredNeuralRenderer:
         # scene with layer 0 hidden (render_pose's `reproject`).  Every frame goes through the plate path, the
         # keys included (at a key's own camera the warp is the identity), so the look does not pop between keys and in-betweens.
         # The frame's stats go to on_frame as the keyword `reprojected` and are kept in reproject_stats.  Approximate; it does not
-        # combine with accumulate, an occluder or an enabled lens.  Not in the reference (keyword-only, off by default)
+        # combine with accumulate, an occluder or an enabled lens.  Not in the reference (keyword-only, off by default).
+        # exclusive=True in the spec: no hole is rendered separately; one render call per frame evaluates the background only on the
+        # rays whose plate row is absent (the per-ray background mask) -- one source of background per ray
         self.reproject = None
         if reproject is not None:
             from stnerf_amd.reproject import as_spec as as_reproject_spec

@@ -61,7 +61,10 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     (``parallel.render_view_reprojected``).  color and depth are the occluded mixed image's; the per-layer
     lists are the render's own (layer 0 was hidden in it).  A fifth element ``stats`` is returned: ``holes``,
     ``reused``, ``rays_background``, ``keys``, and ``passes`` = the dict an occluder returns.  It does not combine with
-    ``accumulate``, an occluder of the caller's or an enabled lens (ValueError).  Approximate; inference only; one rank only."""
+    ``accumulate``, an occluder of the caller's or an enabled lens (ValueError).  Approximate; inference only; one rank only.
+    With ``ReprojectSpec(exclusive=True)`` no hole is rendered separately and layer 0 is not hidden: one render call evaluates the
+    background exactly on the rays whose plate row is absent (a per-ray background mask) and takes the plate on the others;
+    ``holes`` = ``rays_background`` = those rays."""
     if reproject is not None:
         from stnerf_amd.parallel import render_view_reprojected
         if accumulate is not None:

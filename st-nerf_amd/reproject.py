@@ -3,9 +3,13 @@
 
 A key view's layer 0, rendered alone, is a ``BackgroundPlate``: straight colour, alpha and the expected ray parameter per pixel.
 Warped into a neighbouring view it covers almost every pixel; the pixels it cannot cover are rendered (layer 0 only) and
-scattered into the warped rows; the finished plate is then an occluder row per ray, composited into the scene with layer 0
-hidden -- which skips its networks.  Approximate by nature (one depth per pixel, the view dependence frozen at the key view):
-opt-in, inference only, one rank."""
+scattered into the warped rows; the finished plate is then an occluder row per ray, composited into the scene with
+``display_layers[0] = 0``.  That flag does NOT skip layer 0's networks inside the render call (the pipeline evaluates the background
+on every ray of every call and never reads its shown flag), so such a frame pays for the whole background again and composites it
+beside the plate.  ``ReprojectSpec(exclusive=True)`` is the mode that saves the work: no hole is rendered separately, and ONE
+``render_rays_occluded(background_rays=)`` call evaluates layer 0 exactly on the rays whose plate row is absent (the per-ray
+background mask, include/stnerf.h) -- one source of background per ray.  Approximate by nature (one depth per pixel, the view
+dependence frozen at the key view): opt-in, inference only, one rank."""
 from __future__ import annotations
 
 import math
@@ -22,9 +26,11 @@ DEFAULT_A_MIN = 0.9
 class ReprojectSpec:
     """``key_every`` = N >= 1: key plates at path indices 0, N, 2N, ...; ``rel`` >= 0: the resolve guard (a warped pixel whose ray
     parameter exceeds the nearest of its 3x3 neighbourhood by more than the factor 1 + rel is rendered instead); ``a_min`` in
-    [0, 1]: a plate row whose alpha is below it carries no depth and is absent."""
+    [0, 1]: a plate row whose alpha is below it carries no depth and is absent.  ``exclusive`` (False: the frames as they always
+    were): the background comes from exactly one source per ray -- the plate where its row is present, the networks where it is
+    absent, in one render call under a per-ray background mask; no hole is rendered separately."""
 
-    def __init__(self, key_every: int = 4, rel: float = DEFAULT_REL, a_min: float = DEFAULT_A_MIN):
+    def __init__(self, key_every: int = 4, rel: float = DEFAULT_REL, a_min: float = DEFAULT_A_MIN, exclusive: bool = False):
         if isinstance(key_every, bool) or not isinstance(key_every, int) or key_every < 1:
             raise ValueError(f"ReprojectSpec: key_every is a whole number >= 1, got {key_every!r}")
         rel, a_min = float(rel), float(a_min)
@@ -32,10 +38,13 @@ class ReprojectSpec:
             raise ValueError(f"ReprojectSpec: rel must be finite and >= 0, got {rel!r}")
         if not (0.0 <= a_min <= 1.0):
             raise ValueError(f"ReprojectSpec: a_min must lie in [0, 1], got {a_min!r}")
-        self.key_every, self.rel, self.a_min = key_every, rel, a_min
+        if not isinstance(exclusive, bool):
+            raise ValueError(f"ReprojectSpec: exclusive is True or False, got {exclusive!r}")
+        self.key_every, self.rel, self.a_min, self.exclusive = key_every, rel, a_min, exclusive
 
     def __repr__(self):
-        return f"ReprojectSpec(key_every={self.key_every}, rel={self.rel}, a_min={self.a_min})"
+        return (f"ReprojectSpec(key_every={self.key_every}, rel={self.rel}, a_min={self.a_min}"
+                + (", exclusive=True)" if self.exclusive else ")"))
 
     def keys_of(self, i: int, n_poses: int) -> Tuple[int, ...]:
         """The key indices frame ``i`` of a path of ``n_poses`` may use: floor(i / N) N, and that plus N where the path has it."""
@@ -52,6 +61,11 @@ def as_spec(spec) -> ReprojectSpec:
     if isinstance(spec, dict):
         return ReprojectSpec(**spec)
     raise TypeError(f"reproject is a ReprojectSpec or the dict of its arguments, got {type(spec).__name__}")
+
+
+def absent_rows(rows: torch.Tensor) -> torch.Tensor:
+    """(n,) bool: the occluder's own rule for an ABSENT row {r, g, b, a, z} (include/stnerf.h): a <= 0 or NaN, or z not finite."""
+    return ~(rows[:, 3] > 0) | ~torch.isfinite(rows[:, 4])
 
 
 def plate_rows(mixed: torch.Tensor, a_min: float) -> torch.Tensor:
@@ -152,10 +166,12 @@ class BackgroundPlate:
 
 
 def warp_plates(model, K, T, h: int, w: int, frame_ids, plates: Sequence[BackgroundPlate], spec, density_threshold=0.0,
-                bkgd_density_threshold=0.0, chuncks: int = 512 * 7, device="cuda"):
+                bkgd_density_threshold=0.0, chuncks: int = 512 * 7, device="cuda", render_holes: bool = True):
     """Steps 1 and 2 of ``parallel.render_view_reprojected``: the plates' rows warped into the view, its holes rendered (layer 0
     only) and scattered in -> (rows (h w, 5) occluder rows, holes (n_holes,) int32, n_holes, warped) with ``warped`` =
-    ``ops.reproject``'s (values, t, src) -- or None where a plate of this very camera was taken as it is (no launch)."""
+    ``ops.reproject``'s (values, t, src) -- or None where a plate of this very camera was taken as it is (no launch).
+    ``render_holes=False`` stops after the warp: no ray is generated or rendered, and a hole's row stays absent (zeros, a NaN
+    depth) -- what the exclusive mode hands to the per-ray background mask."""
     from stnerf_amd import ops
     spec = as_spec(spec)
     if not plates:
@@ -175,7 +191,7 @@ def warp_plates(model, K, T, h: int, w: int, frame_ids, plates: Sequence[Backgro
     values, t, src, holes, n_holes = ops.reproject([p.source() for p in plates], K, T, h, w, spec.rel)
     rows = values.clone()
     rows[:, 4] = t                       # the ray parameter in THIS view (a hole: NaN, absent until it is rendered)
-    if n_holes:
+    if n_holes and render_holes:
         rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device, pixels=holes)
         mixed = render_background_only(model, rays, view_thresholds(h, w, chuncks, density_threshold, bkgd_density_threshold))
         rows[holes.long()] = plate_rows(mixed, spec.a_min)

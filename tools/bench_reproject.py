@@ -2,10 +2,12 @@
 a short camera path costs plainly and with key plates every 4 and 8 frames, and what the frames look like.
 
     python tools/bench_reproject.py [--workload taekwondo-1080p-64+64] [--poses 16] [--degrees 4] [--md profiles/reproject_ab.md]
+    python tools/bench_reproject.py --legs "plain,key_every 4,exclusive" --no-sweep --md profiles/reproject_exclusive_ab.md
 
 An orbit path of ``--poses`` poses over ``--degrees`` degrees in total from bench.py's first camera (orbit 10 degrees, frame ids
 1 / 2.5, thresholds 0), rendered in one process by three ``LayeredNeuralRenderer``s over the same model -- plain, key_every 4,
-key_every 8 -- INTERLEAVED pose by pose, each frame between device events.  Per leg: seconds per frame (the key plates a frame
+key_every 8 -- and a fourth, ``exclusive`` (key_every 4 with ``ReprojectSpec(exclusive=True)``: one source of background per ray, the
+networks only where the plate has no row) -- INTERLEAVED pose by pose, each frame between device events; ``--legs`` picks a subset.  Per leg: seconds per frame (the key plates a frame
 had to render are inside its time), the hole fraction per frame, and the PSNR of every reprojected frame against the plain
 render of the same pose.  Then a small sweep of ``rel`` and ``a_min`` on the first in-between poses (PSNR against hole
 fraction), and the three kernels alone against their traffic floor (12 B per source pixel, 4 C + 12 B per destination pixel).
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--sweep-rel", default="0.02,0.05,0.2")
     ap.add_argument("--sweep-a-min", default="0.1,0.5,0.9")
     ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--legs", default="plain,key_every 4,key_every 8,exclusive", help="the legs to run, comma-separated; plain is always run")
     ap.add_argument("--md", default=None, help="also write the markdown report to this file")
     ap.add_argument("--json", default=None, help="also write the JSON record to this file")
     args = ap.parse_args()
@@ -91,8 +94,11 @@ def main():
     say(f"{args.workload}: {H * W} rays, {n1}+{n2} samples, {L} performers, {args.precision}; {args.poses} poses over {args.degrees} degrees "
         f"({step:.3f} per pose) from orbit {args.orbit_deg}; rel {rel}, a_min {a_min}.")
     say()
-    legs = [("plain", renderer()), ("key_every 4", renderer(reproject=dict(key_every=4, rel=rel, a_min=a_min))),
-            ("key_every 8", renderer(reproject=dict(key_every=8, rel=rel, a_min=a_min)))]
+    specs = {"key_every 4": dict(key_every=4), "key_every 8": dict(key_every=8), "exclusive": dict(key_every=4, exclusive=True)}
+    wanted = [x.strip() for x in args.legs.split(",") if x.strip() and x.strip() != "plain"]
+    if any(x not in specs for x in wanted):
+        sys.exit(f"--legs: choose from plain, {', '.join(specs)}")
+    legs = [("plain", renderer())] + [(x, renderer(reproject=dict(rel=rel, a_min=a_min, **specs[x]))) for x in wanted]
     timed(lambda: legs[0][1]._render_frame(0, 0, 0, False))             # warm-up: packs, workspace, clocks
     seconds = {name: [] for name, _ in legs}
     quality = {name: [] for name, _ in legs[1:]}
@@ -126,6 +132,20 @@ def main():
                 f"{statistics.mean(holes):.4f}, {min(holes):.4f} .. {max(holes):.4f} | {keys} | {statistics.mean(q):.2f}, {min(q):.2f} .. {max(q):.2f} dB |")
         result["legs"][name] = row
     say()
+    if "exclusive" in seconds:
+        # the in-between frames alone (a key frame carries its plates' renders): what the mode was built for
+        r = dict(legs)["exclusive"]
+        between = [i for i, x in enumerate(r.reproject_stats) if x["keys_rendered"] == 0]
+        mean_of = lambda name: statistics.mean(seconds[name][i] for i in between)
+        line = (f"`exclusive` is key_every 4 with one source of background per ray.  Whole path: {statistics.mean(seconds['exclusive']) / base:.3f} x "
+                f"plain.  In-between frames only ({len(between)} of {args.poses}, no key plate rendered): exclusive {mean_of('exclusive'):.3f} s, "
+                f"plain {mean_of('plain'):.3f} s ({mean_of('exclusive') / mean_of('plain'):.3f} x)")
+        if "key_every 4" in seconds:
+            line += (f", key_every 4 {mean_of('key_every 4'):.3f} s ({mean_of('exclusive') / mean_of('key_every 4'):.3f} x of it); whole path "
+                     f"{statistics.mean(seconds['exclusive']) / statistics.mean(seconds['key_every 4']):.3f} x of key_every 4")
+        flagged = statistics.mean(r.reproject_stats[i]["holes"] / (H * W) for i in between)
+        say(line + f".  Flagged rays (holes and plate rows below a_min) on those frames: {flagged:.4f} of the view.")
+        say()
     for name, r in legs[1:]:
         say(f"{name}, per frame (seconds / hole fraction / PSNR dB): "
             + "; ".join(f"{s:.2f} / {x['holes'] / (H * W):.3f} / {q:.1f}" for s, x, q in zip(seconds[name], r.reproject_stats, quality[name])))
