@@ -625,6 +625,8 @@ def composite_bwd(t: Tensor, raw: Tensor, mask: Optional[Tensor], order: Optiona
     stnerf_composite_bwd, the backward of ``composite`` called with the same t / raw / mask / params (order: its output)."""
     n, l, S = t.shape
     d_raw = torch.empty(n, l, S, 4, dtype=torch.float32, device=t.device)
+    if n == 0:                                                         # (an empty tensor has no device pointer to hand over)
+        return d_raw
     hip.check(hip.lib().stnerf_composite_bwd(hip.dptr(t, name="t"), hip.dptr(raw, name="raw"), hip.dptr(mask, torch.uint8, "mask"),
                                              hip.dptr(order, torch.int32, "order"), n, l, S, C.byref(params),
                                              hip.dptr(g_layer, name="g_layer"), hip.dptr(g_mixed, name="g_mixed"), hip.dptr(d_raw),

@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import stnerf_oracle as O                                               # noqa: E402
 from stnerf_amd import synthetic as syn                                             # noqa: E402
+from composite_backward_common import _edited_sigma, _reference_composite            # noqa: E402,F401
 from train_step_common import compare_digest, load_fixture, oracle_step, replay_of, trainer_loss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -31,44 +32,6 @@ def ops():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _edited_sigma(t, sig, layer, fine, cut_neg, thresholds, scale, near):
-    """The reference's in-place density edits on one layer's (n, S) densities (functional form: masked writes -> where)."""
-    s = sig
-    if (not fine) and cut_neg and layer > 0:
-        s = torch.where(t < 0, torch.zeros_like(s), s)                 # :414
-    if thresholds[layer] is not None:
-        s = torch.where(s < thresholds[layer], torch.zeros_like(s), s)  # :416-418 / :538-547 / :564-566
-    s = s * scale[layer]                                               # :575-576
-    if (not fine) and layer == 0:
-        s = torch.where(t < near, torch.zeros_like(s), s)              # :422
-    return s
-
-
-def _reference_composite(t, raw, mask, fine, cut_neg, thresholds, scale, near, evaluated, border=1e10):
-    """fp64 autograd graph of a stage's composites: per-layer (render_layer.py:25-58 on every evaluated layer) and the depth
-    merge (:425-448 / :587-606), from raw (n,l,S,4) requiring grad."""
-    n, l, S = t.shape
-    rgbs, sigs = [], []
-    for i in range(l):
-        have = (torch.ones(n, dtype=torch.bool) if evaluated[i] == 2 else
-                (mask[:, i] != 0) if evaluated[i] == 1 else torch.zeros(n, dtype=torch.bool))
-        hv = have.reshape(n, 1, 1).to(raw.dtype)
-        rgbs.append(raw[:, i, :, :3] * hv + 0.0)
-        s = _edited_sigma(t[:, i], raw[:, i, :, 3], i, fine, cut_neg, thresholds, scale, near) * have.reshape(n, 1).to(raw.dtype)
-        sigs.append(s.unsqueeze(-1))
-    layer = [O.composite(t[:, i].unsqueeze(-1), rgbs[i], sigs[i], border) for i in range(l)]
-    # rgb of a layer without network output is a ZERO tensor in the reference: sigmoid(0) = 0.5, but its sigma = 0 makes it moot
-    t_mix, order = torch.sort(t.reshape(n, l * S), dim=-1, stable=True)
-    rgb_mix = torch.cat(rgbs, 1).gather(1, order.unsqueeze(-1).repeat(1, 1, 3))
-    sig_mix = torch.cat(sigs, 1).gather(1, order.unsqueeze(-1))
-    if fine:
-        sig_mix = torch.where(t_mix.unsqueeze(-1) < near, torch.zeros_like(sig_mix), sig_mix)     # :605
-    mixed = O.composite(t_mix.unsqueeze(-1), rgb_mix, sig_mix, border)
-    layer_out = torch.stack([torch.cat([c[0], c[1], c[2]], -1) for c in layer], 1)                 # (n,l,5)
-    mixed_out = torch.cat([mixed[0], mixed[1], mixed[2]], -1)
-    return layer_out, mixed_out
-
-
 @pytest.mark.parametrize("l, S, fine", [(3, 80, False), (3, 80, True), (1, 64, False), (2, 33, True), (5, 130, True), (9, 192, False)])
 def test_composite_backward_matches_fp64_autograd(ops, l, S, fine):
     g = torch.Generator().manual_seed(7 * l + S + int(fine))
