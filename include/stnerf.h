@@ -1206,6 +1206,55 @@ int64_t stnerf_reproject_holes_workspace_bytes(int64_t n_pixels);
 int stnerf_reproject_holes(const int32_t* src, int64_t n_pixels, int32_t* holes_out, int32_t* n_out, void* workspace,
                            int64_t workspace_bytes, stnerf_stream_t stream);
 
+/* ---- Adaptive lattice frames (csrc/lattice.hip): render a sparse lattice of pixels, refine the cells whose
+ * corners disagree, interpolate the cells whose corners agree.  An approximation, opt-in, inference only.  Every *, + and - below is
+ * one IEEE fp32 operation in the order written (no contraction).
+ *
+ * State of a frame of P = h w pixels, q = y w + x:  values[P][C] (the columns of a packed row; the LAST E of them are exact
+ * columns, the first C - E are tested against tol[C - E], a device array) and status[P] uint8: 0 unknown, 1 rendered, 2 filled,
+ * 3 queued.  levels = K in 0..4, the top stride S = 2^K.
+ *
+ * Covered region.  Wc = (w - 1) / S * S,  Hc = (h - 1) / S * S  (integer division).  Wc == 0 or Hc == 0: there is no cell and every
+ * pixel is margin.  Otherwise the pixels with x <= Wc and y <= Hc are covered and the others are margin; every cell of every
+ * stride s | S with corners on the s-lattice lies inside the covered region.
+ *
+ * Begin.  status[q] = 3 if q is margin, or force[q] != 0 (force: device uint8[P] or NULL), or x % S == 0 and y % S == 0; else 0.
+ *
+ * Flat.  A cell (cx, cy, s) has the corners v00 = (cx, cy), v10 = (cx + s, cy), v01 = (cx, cy + s), v11 = (cx + s, cy + s), all of
+ * status 1 or 2 (not checked).  It is flat if and only if, for every column c < C - E, the four values are finite and
+ * max - min <= tol[c] (one subtraction; a NaN tol[c] is never met), and for every column c >= C - E the four compare equal (==).
+ *
+ * Classify at stride s (a power of two, 2 <= s <= S; the caller goes s = S, S / 2, .., 2).  Every covered pixel of status 0 looks
+ * at the cells of stride s whose closure contains it (one inside a cell, two on an edge, clipped to the covered region).
+ *   all of them flat:  status = 2 and, from the FIRST of them (lowest cy, then lowest cx),
+ *       fx = (x - cx) / s   gx = 1 - fx   fy = (y - cy) / s   gy = 1 - fy                 (exact: s is a power of two)
+ *       top = gx * v00 + fx * v10      bot = gx * v01 + fx * v11      v = gy * top + fy * bot
+ *     for every column c < C - E; a column c >= C - E copies v00.
+ *   else, x % (s / 2) == 0 and y % (s / 2) == 0:  status = 3.
+ *   else it stays 0.
+ * Three launches -- a lane per cell writes a flat byte into `flat` (at least (Wc / s) (Hc / s) bytes of device memory; h w always
+ * suffices; overwritten), a lane per (pixel, column) fills, a lane per pixel writes the status the fill only read -- so no
+ * reader races a writer: a launch reads the values of lattice-s points only, whose status is 1 or 2 and which it never writes, and
+ * writes only the pixel it owns.  No atomics, no order dependence.  After s = 2 no covered pixel has status 0.
+ *
+ * Select.  pixels_out[0 .. *n_out) = the q with status[q] == 3, ascending (room for P entries); n_out: one device int32.  The three
+ * launches of stnerf_accumulate_select (csrc/ordered_compact.h), deterministic; workspace as there.
+ *
+ * Scatter.  Row i of rows (n rows of C floats, row_stride floats apart) becomes values[pixels[i]] and status[pixels[i]] = 1.  An
+ * entry outside [0, P) is skipped; a pixel that is not listed is not touched; a list names a pixel at most once (not checked).
+ *
+ * All kernels are HBM-bound helpers: no LDS beyond the compaction's, no scratch.  STNERF_EINVAL before any launch: a null pointer
+ * (force may be NULL; tol may be NULL only if E == C), h or w < 1 or h w > INT32_MAX, levels outside 0..4, s not a power of two in
+ * [2, S], not 1 <= C <= 4096 or not 0 <= E <= C, too few flat bytes, row_stride < C, n < 0 or n > P, a workspace too small. */
+int stnerf_lattice_begin(int h, int w, int levels, const uint8_t* force, uint8_t* status, stnerf_stream_t stream);
+int stnerf_lattice_classify(float* values, uint8_t* status, int h, int w, int C, int E, int levels, int s, const float* tol,
+                            uint8_t* flat, int64_t flat_bytes, stnerf_stream_t stream);
+int64_t stnerf_lattice_select_workspace_bytes(int64_t n_pixels);
+int stnerf_lattice_select(const uint8_t* status, int64_t n_pixels, int32_t* pixels_out, int32_t* n_out, void* workspace,
+                          int64_t workspace_bytes, stnerf_stream_t stream);
+int stnerf_lattice_scatter(const float* rows, int64_t n, int C, int64_t row_stride, const int32_t* pixels, int64_t n_pixels,
+                           float* values, uint8_t* status, stnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

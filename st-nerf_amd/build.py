@@ -30,6 +30,7 @@ SOURCES = [
     ("accumulate.hip", ["-ffp-contract=off"]),
     ("lens.hip", ["-ffp-contract=off"]),
     ("reproject.hip", ["-ffp-contract=off"]),
+    ("lattice.hip", ["-ffp-contract=off"]),
     ("pack.hip", []),
     ("pack_bf16x3.hip", []),
     ("mlp_raybias.hip", []),

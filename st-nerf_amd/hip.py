@@ -245,6 +245,12 @@ _PROTOS = {
                                            c_f32p, C.c_void_p, C.c_void_p]),
     "stnerf_reproject_holes_workspace_bytes": (c_i64, [c_i64]),
     "stnerf_reproject_holes": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "stnerf_lattice_begin": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stnerf_lattice_classify": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p,
+                                          c_i64, C.c_void_p]),
+    "stnerf_lattice_select_workspace_bytes": (c_i64, [c_i64]),
+    "stnerf_lattice_select": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "stnerf_lattice_scatter": (C.c_int, [c_f32p, c_i64, C.c_int, c_i64, C.c_void_p, c_i64, c_f32p, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw_listed": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                                C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "stnerf_copy_layer_raw": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),

@@ -1026,24 +1026,7 @@ class LayeredRFRender(nn.Module):
             occluder = occluder.to(rays.device, torch.float32).contiguous()
         if background_rays is not None:
             background_rays = background_rays.to(rays.device).contiguous()
-        step = N if ref_chunk is None else ref_chunk
-        rotated = self._rotation_specs() is not None
-        groups = []  # (start, end, boxes, pivot[, rotations])
-        if retiming:
-            row0 = rays[0::step, 6:].cpu()  # one D2H: row-0 frame ids of every reference chunk
-            n_chunks, c0 = row0.shape[0], 0
-            for c in range(1, n_chunks + 1):  # merge runs of reference chunks that share their boxes
-                if c == n_chunks or not torch.equal(row0[c], row0[c0]):
-                    boxes, pivot = self._retimed_boxes(row0[c0])
-                    groups.append((c0 * step, min(c * step, N), boxes.to(rays.device), pivot)
-                                  + ((self.layer_ray_transforms(boxes),) if rotated else ()))
-                    c0 = c
-        else:
-            fid = rays[:, 6].to(torch.int64) - 1
-            bb = self._box_table().to(rays.device).float().index_select(0, fid)                    # :193
-            bk = self.bkgd_bbox.to(rays.device).float().unsqueeze(0).expand(N, 1, 8, 3)
-            boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
-            groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))
+        groups = self._chunk_groups(rays, retiming, ref_chunk)
         occ_ids = self._occupancy_frame_ids(rays, groups, retiming) if culling and self._occupancy.culled_layers(self) else None
         bg_ids = self._background_frame_ids(rays, groups) if bg_culling else None
         outs = []
@@ -1088,6 +1071,53 @@ class LayeredRFRender(nn.Module):
         raw = tuple(cat(j) for j in range((9 if occluder is not None else 6) if scene else 5))
         self.advance_seed()
         return raw
+
+    def _chunk_groups(self, rays, retiming, ref_chunk):
+        """The chunk groups of a call's rays (contiguous float32, on the device): (start, end, edited boxes, pivot[, rotations]) per
+        run of reference chunks that share their boxes -- one group of per-ray boxes for width-7 rays."""
+        N = rays.shape[0]
+        step = N if ref_chunk is None else ref_chunk
+        rotated = self._rotation_specs() is not None
+        groups = []  # (start, end, boxes, pivot[, rotations])
+        if retiming:
+            row0 = rays[0::step, 6:].cpu()  # one D2H: row-0 frame ids of every reference chunk
+            n_chunks, c0 = row0.shape[0], 0
+            for c in range(1, n_chunks + 1):  # merge runs of reference chunks that share their boxes
+                if c == n_chunks or not torch.equal(row0[c], row0[c0]):
+                    boxes, pivot = self._retimed_boxes(row0[c0])
+                    groups.append((c0 * step, min(c * step, N), boxes.to(rays.device), pivot)
+                                  + ((self.layer_ray_transforms(boxes),) if rotated else ()))
+                    c0 = c
+        else:
+            fid = rays[:, 6].to(torch.int64) - 1
+            bb = self._box_table().to(rays.device).float().index_select(0, fid)                    # :193
+            bk = self.bkgd_bbox.to(rays.device).float().unsqueeze(0).expand(N, 1, 8, 3)
+            boxes, pivot = self._edit_boxes(torch.cat([bk, bb], 1).contiguous())
+            groups.append((0, N, boxes, pivot) + ((self._per_ray_box_transforms(rays, boxes),) if rotated else ()))
+        return groups
+
+    def ray_masks(self, rays, ref_chunk: Optional[int] = None):
+        """The pipeline's own ray mask of ``rays`` without rendering them -> (n, l) uint8, 1 where the ray meets layer i's edited (and
+        rotated) box: the coarse sampler's call of ``render_rays_raw`` on the same chunk groups -- the same boxes, edits, pivots and
+        rotations, no points -- before any occupancy cull (which only clears bits).  It draws nothing that matters (a mask does not
+        depend on the jitter) and leaves the seed alone."""
+        if not rays.is_cuda:
+            raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
+        rays = rays.contiguous().float()
+        N, l = rays.shape[0], self.total_layers
+        if rays.shape[1] not in (7, 6 + l):
+            raise ValueError(f"undefined ray format in LayeredRFRender, ray dimension is {rays.shape[1]}")
+        if self.bkgd_bbox is None or self.bboxes is None:
+            raise RuntimeError("set_bkgd_bbox / set_bboxes must be called before rendering")
+        if N == 0:
+            raise IndexError("empty ray batch: LayeredRFRender needs at least one ray")
+        edits = self._point_edits(l, False)
+        masks = []
+        for g0, g1, boxes, pivot, *rot in self._chunk_groups(rays, rays.shape[1] != 7, ref_chunk):
+            bx = boxes if boxes.dim() == 3 else boxes[g0:g1].contiguous()
+            masks.append(ops.sample_coarse(rays[g0:g1], bx, self.coarse_ray_sample, seed=int(self.seed) & 0xFFFFFFFFFFFFFFFF, edits=edits,
+                                           pivot=pivot, want_xyz=False, **(dict(rotations=rot[0]) if rot else {}))[2])
+        return masks[0] if len(masks) == 1 else torch.cat(masks, 0)
 
     def forward(self, rays, labels=None, bboxes=None, only_coarse=False, near_far=None, near_far_points=[],
                 density_threshold=0.0001, bkgd_density_threshold=0):

@@ -1228,6 +1228,93 @@ def accumulate_select(state: AccumulateState, min_spp: int, max_spp: int, tol: f
     return out[:n].clone(), n      # (the buffer is the next call's too)
 
 
+# ---------------------------------------------------------------------------------------- adaptive lattice frames
+class LatticeState:
+    """Per-pixel state of a lattice frame (include/stnerf.h: stnerf_lattice_begin): ``values`` (P,C), ``status`` (P,) uint8 --
+    0 unknown, 1 rendered, 2 filled, 3 queued --, both zero at first; plus the flat bytes ``lattice_classify`` and the buffers
+    ``lattice_select`` write (made on first use)."""
+
+    def __init__(self, h: int, w: int, C_: int, device="cuda"):
+        if h < 1 or w < 1 or C_ < 1:
+            raise ValueError(f"lattice_state: need h, w >= 1 and C >= 1, got h={h}, w={w}, C={C_}")
+        self.h, self.w = int(h), int(w)
+        self.values = torch.zeros(h * w, C_, dtype=torch.float32, device=device)
+        self.status = torch.zeros(h * w, dtype=torch.uint8, device=device)
+        self._flat = self._select = None
+
+    @property
+    def n_pixels(self) -> int:
+        return self.status.shape[0]
+
+
+def lattice_state(h: int, w: int, C_: int, device="cuda") -> LatticeState:
+    """A zeroed ``LatticeState`` for an h x w view of C floats per pixel."""
+    return LatticeState(h, w, C_, device)
+
+
+def lattice_begin(state: LatticeState, levels: int, force: Optional[Tensor] = None) -> LatticeState:
+    """The first queue, IN PLACE (stnerf_lattice_begin): status 3 on the margin, where ``force`` -- None | (h, w) or (h w,) uint8 on
+    the device -- is nonzero and on the points of the top lattice (stride 2^levels), 0 elsewhere.  -> state."""
+    if force is not None:
+        if force.numel() != state.n_pixels or tuple(force.shape) not in ((state.h, state.w), (state.n_pixels,)):
+            raise ValueError(f"lattice_begin: force must be ({state.h},{state.w}) uint8, got {tuple(force.shape)}")
+        force = force.reshape(-1)
+    hip.check(hip.lib().stnerf_lattice_begin(state.h, state.w, int(levels), hip.dptr(force, torch.uint8, "force"),
+                                             hip.dptr(state.status, torch.uint8, "status"), hip.stream_ptr()), "stnerf_lattice_begin")
+    return state
+
+
+def lattice_classify(state: LatticeState, levels: int, stride: int, tol: Tensor, exact: int = 1) -> LatticeState:
+    """One level, IN PLACE (stnerf_lattice_classify): every covered pixel of status 0 whose cells of ``stride`` are all flat is filled
+    from the first of them (status 2); another that is a point of the next lattice is queued (status 3).  tol: (C - exact,) float32
+    on the device, the bound of every tested column; the last ``exact`` columns are compared with ==.  -> state."""
+    C_ = state.values.shape[1]
+    if tuple(tol.shape) != (C_ - int(exact),):
+        raise ValueError(f"lattice_classify: tol must be ({C_ - int(exact)},), one bound per tested column, got {tuple(tol.shape)}")
+    if state._flat is None:
+        state._flat = torch.empty(state.n_pixels, dtype=torch.uint8, device=state.status.device)
+    hip.check(hip.lib().stnerf_lattice_classify(hip.dptr(state.values, name="values"), hip.dptr(state.status, torch.uint8, "status"),
+                                                state.h, state.w, C_, int(exact), int(levels), int(stride),
+                                                hip.dptr(tol if tol.numel() else None, name="tol"), hip.dptr(state._flat, torch.uint8),
+                                                state._flat.numel(), hip.stream_ptr()), "stnerf_lattice_classify")
+    return state
+
+
+def lattice_select(state: LatticeState) -> Tuple[Tensor, int]:
+    """The queued pixels (status 3), ascending (stnerf_lattice_select).  -> (pixels (n,) int32 on the device, n): n is a Python
+    int, read back with one small D2H."""
+    P = state.n_pixels
+    if state._select is None:
+        nbytes = hip.lib().stnerf_lattice_select_workspace_bytes(P)
+        if nbytes < 0:
+            hip.check(int(nbytes), "stnerf_lattice_select_workspace_bytes")
+        dev = state.status.device
+        state._select = (torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                         torch.zeros(1, dtype=torch.int32, device=dev))
+    work, out, n_out = state._select
+    hip.check(hip.lib().stnerf_lattice_select(hip.dptr(state.status, torch.uint8, "status"), P, hip.dptr(out, torch.int32),
+                                              hip.dptr(n_out, torch.int32), hip.dptr(work, torch.uint8), work.numel(),
+                                              hip.stream_ptr()), "stnerf_lattice_select")
+    n = int(n_out.item())
+    return out[:n].clone(), n      # (the buffer is the next call's too)
+
+
+def lattice_scatter(rows: Tensor, state: LatticeState, pixels: Tensor) -> LatticeState:
+    """The rendered rows of some pixels, IN PLACE (stnerf_lattice_scatter): rows (n,C), a 2-D float32 device view with dense columns
+    (any row stride), row i -> ``values[pixels[i]]`` and ``status[pixels[i]]`` = 1; pixels: a device int32 list that names a pixel
+    at most once; an entry outside [0, P) is skipped.  -> state."""
+    if rows.dim() != 2 or rows.shape[1] != state.values.shape[1]:
+        raise ValueError(f"lattice_scatter: rows are {tuple(rows.shape)[1:]} floats wide, the state {state.values.shape[1]}")
+    n, C_ = rows.shape
+    if tuple(pixels.shape) != (n,):
+        raise ValueError(f"lattice_scatter: pixels must be ({n},), got {tuple(pixels.shape)}")
+    rp, stride = _mat(rows, "rows")
+    hip.check(hip.lib().stnerf_lattice_scatter(rp, n, C_, stride if n > 1 else C_, hip.dptr(pixels, torch.int32, "pixels"), state.n_pixels,
+                                               hip.dptr(state.values, name="values"), hip.dptr(state.status, torch.uint8, "status"),
+                                               hip.stream_ptr()), "stnerf_lattice_scatter")
+    return state
+
+
 # ---------------------------------------------------------------------------------------- reprojection into a nearby view
 def world_to_camera(T) -> "np.ndarray":
     """Wd (3,4) float32 of a camera-to-world pose T (4,4): the inverse taken in fp64 on the host, rounded once (include/stnerf.h)."""

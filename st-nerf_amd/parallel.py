@@ -547,6 +547,107 @@ def render_view_accumulated(model, K, T, h: int, w: int, frame_ids, spec, densit
     return model.as_reference_tuple(unpack_outputs(torch.cat([state.mean, bits], 1), l, "fine")), stats
 
 
+def render_view_lattice(model, K, T, h: int, w: int, frame_ids, spec, density_threshold=0.0, bkgd_density_threshold=0.0,
+                        chuncks: int = 512 * 7, device="cuda", lens=None, scene: bool = False, occluder=None, accumulate=None,
+                        reproject=None):
+    """One view as an adaptive lattice frame (``stnerf_amd.lattice.LatticeSpec``): the pixels of a sparse
+    lattice are rendered, the cells whose corners disagree are refined at half the stride, the pixels of the cells whose corners
+    agree are interpolated -> (the reference's 5-tuple built from the per-pixel state, coarse entries None as in gather mode
+    "fine", stats).  An approximation; inference only, one rank.
+
+    ``ops.lattice_begin`` queues the margin, the forced pixels and the top lattice's points.  Then, per level: the ascending list
+    of ``ops.lattice_select`` is rendered -- ``ops.generate_rays(pixels=list)``, ``render_rays_raw``, ``pack_outputs(raw, "fine")``
+    -- and scattered (``ops.lattice_scatter``), and ``ops.lattice_classify`` at the level's stride S, S / 2, .., 2 fills and
+    queues; a last list holds what stride 2 left.  An empty list skips its render call.  Every list renders with seed s0 (=
+    ``model.seed`` on entry) and the ray window at its default, so the RNG key of a ray is its position in its list.  Thresholds
+    follow ``layered_batchify_ray``'s rule by the VIEW's size (h w < chuncks: the model's defaults).  On return the seed is s0 + 1
+    if ``model.fresh_draws_per_call``, else s0.  ``levels = 0``, or a ``force`` of all ones, gives ONE list of every pixel: the
+    plain frame bit for bit.
+
+    ``force="performers"``: the view's rays are generated once and their mask taken from the pipeline's own sampler
+    (``model.ray_masks``); the pixels where any shown performer layer (index >= 1) is hit are rendered whatever their cells say, so
+    the approximation is confined to pixels only the background reaches.
+
+    Occupancy grids, termination, instances, rotation and opacity act inside ``render_rays_raw`` as always.  A distorting
+    ``lens`` passes through ``generate_rays(lens=, pixels=)``.
+
+    stats: ``rendered`` + ``filled`` = h w; ``forced`` and ``margin`` (pixels the force mask and the margin queued; they may
+    overlap each other and the lattice); ``rays_per_level`` (one entry per list, empty ones included); ``status`` (h w,) uint8 on
+    the device (1 rendered, 2 filled)."""
+    from stnerf_amd import ops
+    from stnerf_amd.lattice import EXACT_COLUMNS, as_spec, covered
+    spec = as_spec(spec)
+    what = "render_view_lattice"
+    if accumulate is not None or reproject is not None:
+        raise ValueError(f"{what} with accumulate= or reproject=: a sparse frame of progressive passes or of warped plates is out of "
+                         "scope; render the frame with one of them")
+    lens = _checked_lens(lens, K, h, w)
+    if lens is not None and lens.aperture > 0.0:
+        raise ValueError(f"{what} with a lens of aperture > 0: defocus is the mean of several passes through the lens "
+                         "(render_view_accumulated), which does not combine with the lattice; a distorting lens does")
+    if active_group(model) is not None:
+        raise RuntimeError(f"{what} under shard_views with more than one rank: the per-pixel state lives on one device and a "
+                           "multi-rank lattice is out of scope; render on one rank (model.shard_views = False)")
+    if scene or occluder is not None:
+        raise ValueError(f"{what} with scene passes or an occluder: interpolating those passes is out of scope; render them "
+                         "without lattice=")
+    if getattr(model, "_bkgd_cache", None) is not None or getattr(model, "_layer_cache", None) is not None:
+        raise ValueError(f"{what} with a background cache or a layer cache attached: a cached run is keyed by the whole view's rays, "
+                         "which contradicts a sparse list of them; detach the cache (set_background_cache(None) / set_layer_cache(None))")
+    if getattr(model, "replay", None) is not None:
+        raise ValueError(f"{what} with replayed draws (model.replay): they are recorded per ray of the whole view, which contradicts "
+                         "a sparse list of them; set model.replay = None")
+    l = total_layers(model)
+    frame_ids = [float(f) for f in frame_ids]
+    n_total = h * w
+    force = spec.force
+    if force is not None and not isinstance(force, str) and tuple(force.shape) != (h, w):
+        raise ValueError(f"{what}: the force mask must be ({h},{w}) uint8, got {tuple(force.shape)}")
+    through = dict(lens=lens) if lens is not None else {}
+    mask64 = 0xFFFFFFFFFFFFFFFF
+    s0 = int(model.seed) & mask64
+    state = ops.lattice_state(h, w, packed_width(l, "fine"), device)
+    tol = torch.tensor(spec.tolerances(l), dtype=torch.float32).to(device)
+    rays_per_level = []
+
+    def render_queued():
+        pixels, n = ops.lattice_select(state)
+        rays_per_level.append(n)
+        if n == 0:
+            return
+        model.seed = s0
+        rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device, pixels=pixels, **through)
+        if n_total < chuncks:     # (layered_batchify_ray's small-call rule, decided by the view)
+            raw = model.render_rays_raw(rays)
+        else:
+            raw = model.render_rays_raw(rays, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks)
+        ops.lattice_scatter(pack_outputs(raw, "fine"), state, pixels)
+
+    try:
+        with torch.no_grad():
+            if isinstance(force, str):      # "performers": the pipeline's own mask of the whole view's rays
+                model.seed = s0
+                rays = ops.generate_rays(K, T, h, w, frame_ids=frame_ids, device=device, **through)
+                hit = model.ray_masks(rays, None if n_total < chuncks else chuncks)
+                shown = torch.tensor([int(i >= 1 and model.is_shown_layer(i)) for i in range(l)], dtype=torch.uint8, device=hit.device)
+                force = ((hit != 0) & (shown != 0)).any(1).to(torch.uint8)
+            elif force is not None:
+                force = force.to(device).contiguous()
+            ops.lattice_begin(state, spec.levels, force)
+            for s in spec.strides():
+                render_queued()
+                ops.lattice_classify(state, spec.levels, s, tol, EXACT_COLUMNS)
+            render_queued()
+    finally:
+        model.seed = (s0 + 1) & mask64 if model.fresh_draws_per_call else s0
+    Wc, Hc = covered(h, w, spec.levels)
+    n_filled = int((state.status == 2).sum().item())
+    stats = dict(rendered=n_total - n_filled, filled=n_filled, forced=0 if force is None else int((force != 0).sum().item()),
+                 margin=n_total if Wc == 0 or Hc == 0 else n_total - (Wc + 1) * (Hc + 1), rays_per_level=rays_per_level,
+                 status=state.status)
+    return model.as_reference_tuple(unpack_outputs(state.values, l, "fine")), stats
+
+
 def render_view_reprojected(model, K, T, h: int, w: int, frame_ids, plates, spec, density_threshold=0.0, bkgd_density_threshold=0.0,
                             chuncks: int = 512 * 7, device="cuda", occluder=None, lens=None, only_coarse: bool = False):
     """One view whose background is warped from the key plates of nearby views (``stnerf_amd.reproject``)

@@ -34,7 +34,7 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None):
+                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None, lattice=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -126,6 +126,21 @@ class LayeredNeuralRenderer:
                 raise ValueError("reproject= with scene_passes: layer 0 is hidden in a reprojected frame; its passes are in the stats")
         self.reproject_stats = []
         self._plates = {}
+        # lattice: an stnerf_amd.lattice.LatticeSpec or the dict of its arguments -- every frame of render_path /
+        # render_path_walking is rendered on a sparse lattice of pixels, refined where the corners of a cell disagree and
+        # interpolated where they agree (render_pose's `lattice`).  The frame's stats go to on_frame as the
+        # keyword `lattice` and are kept in lattice_stats (without the status map).  Approximate; it does not combine with
+        # accumulate, reproject, scene_passes or an occluder.  Not in the reference (keyword-only, off by default)
+        self.lattice = None
+        if lattice is not None:
+            from stnerf_amd.lattice import as_spec as as_lattice_spec
+            self.lattice = as_lattice_spec(lattice)
+            if self.accumulate is not None or self.reproject is not None:
+                raise ValueError("lattice= with accumulate= or reproject=: a sparse frame of progressive passes or of warped plates is "
+                                 "out of scope")
+            if self.scene_passes or self.occluder is not None:
+                raise ValueError("lattice= with scene_passes or occluder=: interpolating those passes is out of scope")
+        self.lattice_stats = []
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -426,20 +441,22 @@ class LayeredNeuralRenderer:
 
     # ---- rendering -------------------------------------------------------------------------------------------
     def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None,
-                    accumulate=None, lens=None, reproject=None):
+                    accumulate=None, lens=None, reproject=None, lattice=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
         element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
         also holds the occluded results; with ``accumulate`` = a spec the frame is a progressive multi-sample one and the fifth
         element is its ``stats``.  ``lens``: the camera's lens for this frame (default: the renderer's ``lens``).
         ``reproject`` = (spec, plates): the background is warped from those key plates (stnerf_amd.render.render_pose); the fifth
-        element is the frame's ``stats``."""
+        element is the frame's ``stats``.  ``lattice`` = a spec: the frame is an adaptive lattice one and the fifth element is its
+        ``stats``."""
         lens = self.lens if lens is None else lens
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
                             bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
                             **(dict(occluder=occluder, occluder_stops=self.occluder_stops) if occluder is not None else {}),
                             **(dict(accumulate=accumulate) if accumulate is not None else {}),
                             **(dict(lens=lens) if lens is not None else {}),
-                            **(dict(reproject=reproject) if reproject is not None else {}))
+                            **(dict(reproject=reproject) if reproject is not None else {}),
+                            **(dict(lattice=lattice) if lattice is not None else {}))
 
     def _key_plates(self, idx, density_threshold, bkgd_density_threshold):
         """The key plates frame ``idx`` uses (``ReprojectSpec.keys_of``) -> (plates, how many were rendered for this frame).  A
@@ -489,6 +506,14 @@ class LayeredNeuralRenderer:
             if inverse_y_axis:
                 stats = dict(stats, spp=torch.flip(stats["spp"], [0]), variance=torch.flip(stats["variance"], [0]))
             self._frame_stats = stats
+        elif self.lattice is not None:
+            color, depth, color_layer, depth_layer, stats = self.render_pose(self.poses[idx], self.Ks[idx], self.layer_frame_pairs[idx],
+                                                                            density_threshold, bkgd_density_threshold,
+                                                                            lattice=self.lattice)
+            if inverse_y_axis:
+                stats = dict(stats, status=torch.flip(stats["status"], [0]))
+            self._frame_stats = stats
+            self.lattice_stats.append({k: v for k, v in stats.items() if k != "status"})
         elif self.scene_passes or occ is not None:
             color, depth, color_layer, depth_layer, passes = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                              self.layer_frame_pairs[idx], density_threshold,
@@ -515,6 +540,8 @@ class LayeredNeuralRenderer:
             kw["accumulated"] = self._frame_stats
         if self.reproject is not None:
             kw["reprojected"] = self._frame_stats
+        if self.lattice is not None:
+            kw["lattice"] = self._frame_stats
         if self.occluder is not None:
             has = passes is not None and "color_occluded" in passes
             kw["occluded"] = {k: v for k, v in passes.items() if "occlude" in k} if has else None
@@ -549,6 +576,7 @@ class LayeredNeuralRenderer:
         self.images_occluded = []
         self.spp_maps = []
         self.reproject_stats, self._plates = [], {}
+        self.lattice_stats = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             if self.s_shift is not None:
@@ -595,6 +623,7 @@ class LayeredNeuralRenderer:
         self.images_occluded = []
         self.spp_maps = []
         self.reproject_stats, self._plates = [], {}
+        self.lattice_stats = []
         self.image_num = 0
         for idx in range(len(self.poses)):
             color, depth, color_layer, depth_layer, passes = self._render_frame(idx, density_threshold, bkgd_density_threshold,

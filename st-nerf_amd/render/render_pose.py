@@ -15,7 +15,7 @@ from stnerf_amd.parallel import render_view, total_layers
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
                 density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
-                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None, reproject=None):
+                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None, reproject=None, lattice=None):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -64,7 +64,27 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     ``accumulate``, an occluder of the caller's or an enabled lens (ValueError).  Approximate; inference only; one rank only.
     With ``ReprojectSpec(exclusive=True)`` no hole is rendered separately and layer 0 is not hidden: one render call evaluates the
     background exactly on the rays whose plate row is absent (a per-ray background mask) and takes the plate on the others;
-    ``holes`` = ``rays_background`` = those rays."""
+    ``holes`` = ``rays_background`` = those rays.
+
+    ``lattice`` = an ``stnerf_amd.lattice.LatticeSpec`` (or the dict of its arguments): the frame is rendered on a sparse lattice of
+    pixels, refined where the corners of a cell disagree and interpolated where they agree
+    (``parallel.render_view_lattice``).  The depth post-processing above is applied to the finished state, and
+    a fifth element ``stats`` is returned: ``rendered``, ``filled``, ``forced``, ``margin``, ``rays_per_level`` and ``status`` (H,W)
+    uint8 (1 rendered, 2 filled).  A distorting ``lens`` passes through; it does not combine with ``accumulate``, ``reproject``,
+    ``scene_passes``, an occluder or a lens with an aperture (ValueError).  Approximate; inference only; one rank only."""
+    if lattice is not None:
+        from stnerf_amd.parallel import render_view_lattice
+        frame_ids = [0.0] * total_layers(model)
+        for layer_id, frame_id in layer_frame_pair:
+            frame_ids[layer_id] = float(frame_id)
+        (stage2, _, stage2_layer, _, _), stats = render_view_lattice(
+            model, torch.as_tensor(K, dtype=torch.float32), torch.as_tensor(pose, dtype=torch.float32), height, width, frame_ids,
+            lattice, density_threshold, bkgd_density_threshold, device=device, scene=bool(scene_passes), occluder=occluder,
+            accumulate=accumulate, reproject=reproject, **(dict(lens=lens) if lens is not None else {}))
+        stats = dict(stats, status=stats["status"].reshape(height, width))
+        return (stage2[0].reshape(height, width, 3), stage2[1].reshape(height, width, 1).clamp_min(0) / far,
+                [t[0].reshape(height, width, 3) for t in stage2_layer], [t[1].reshape(height, width, 1) / far for t in stage2_layer],
+                stats)
     if reproject is not None:
         from stnerf_amd.parallel import render_view_reprojected
         if accumulate is not None:

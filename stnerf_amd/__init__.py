@@ -35,6 +35,9 @@ def __getattr__(name):
     if name == "AccumulateSpec":
         from stnerf_amd.accumulate import AccumulateSpec
         return AccumulateSpec
+    if name == "LatticeSpec":
+        from stnerf_amd.lattice import LatticeSpec
+        return LatticeSpec
     if name == "Lens":
         from stnerf_amd.lens import Lens
         return Lens
