@@ -1071,6 +1071,81 @@ int stnerf_render_rays_opts(const float* rays, int64_t n, const float* boxes, in
                             float* mixed_coarse, float* layer_fine, float* layer_coarse, uint8_t* mask,
                             const stnerf_render_options* opts_host, stnerf_stream_t stream);
 
+/* ---- Deep frames (csrc/deep.hip; DESIGN.md sections 4.2 and 7) ---------------------------------------------------------------------
+ * Opt-in, inference only, not in the reference: the final stage's merged weights kept as a per-ray list of DEEP SAMPLES, so that any
+ * number of depth-tested elements can be composited AFTER the render, with no network (the VFX "deep image").
+ *   Kept.  For one ray of the final stage take t[l][S], wM[l][S] and the colour c_k exactly as stnerf_scene_occluder does (the colour
+ *   through the compositor's sample edit with its switches off: sigmoid(rgb), or raw's own with rgb_activated).  Sample k of layer i is
+ *   KEPT iff !(wM <= w_min), w_min >= 0: the exact zeros of culled, terminated, hidden, missed and grazing samples are dropped, a NaN
+ *   weight is kept.  A layer without network output on the ray (the layers scene_out zeroes) has no deep sample.
+ *   Segments, per layer, in source order.  merge_dz == 0: every kept sample is its own segment.  merge_dz > 0: t0 = the depth of the
+ *   layer's first kept sample on the ray, bin_k = floorf((t_k - t0) / merge_dz), the difference, the quotient and the floor one fp32
+ *   operation each; a kept sample STARTS a segment iff it is the layer's first kept sample or bin_k != the previous kept sample's
+ *   bin.  The bins are compared as the floats floorf returns -- the same as comparing (int) bin wherever an int holds it -- so a NaN
+ *   depth, whose bin is NaN and differs from every bin, opens a segment of its own and ends it.  Segments of different layers may
+ *   overlap in depth: wM already carries the layers' mutual occlusion.
+ *   Record.  32 bytes, 8 words {r, g, b, a, zw, zf, zb, meta}: {r, g, b, zw, a} = sum of wM {c.r, c.g, c.b, t, 1} over the segment's
+ *   kept samples in ascending source index, acc = acc + w x from acc = +0 with the product and the sum separate fp32 operations;
+ *   zf, zb = the depths of the segment's first and last kept sample; meta (a uint32 word) = layer | first_k << 8 | count << 16, count
+ *   the segment's kept samples.  Hence S <= 256.
+ *   Layout.  CSR: offsets[n + 1] int64, samples[total][8] fp32; within a ray layer-major, then source index.  int64 because a frame's
+ *   list (1920 x 1080 rays of up to 65535 samples) passes 2^32 records and the offsets are gathered and rebased as tensor indices,
+ *   which are int64; 8 bytes per ray are nothing beside 32 per record.  One CALL holds at most 2^31 - 1 records (n l S < 2^31).
+ *   The offsets are the ordered exclusive scan of the per-ray counts (csrc/ordered_compact.h's one-workgroup scan of 256-ray block
+ *   sums): the layout does not depend on the order in which workgroups run.
+ * stnerf_deep_count: counts[n] int32 = the ray's segments.  One wave per ray over a persistent grid; a layer without output is skipped
+ *   wave-uniformly, every load of a layer (t and wM, S <= 256: four blocks) is issued before the first is used.
+ * stnerf_deep_offsets: counts -> offsets[n + 1]; max_count >= every count (l S), n max_count < 2^31.  workspace: at least
+ *   stnerf_deep_workspace_bytes(n) bytes, overwritten; it is NOT part of the render workspace.  Three launches.
+ * stnerf_deep_fill: the records of ray r at samples[offsets[r] ..).  A ray with offsets[r + 1] > capacity (or offsets that do not
+ *   ascend from >= 0) writes nothing, and no record lands outside [offsets[r], offsets[r + 1]); *deep_total = offsets[n], always: the
+ *   caller compares it with capacity, so an overflow is detected and never silent.  The lane that heads a segment sums it.
+ * stnerf_deep_composite: elements[n][E][5], 0 <= E <= STNERF_DEEP_MAX_ELEMENTS, rows {r, g, b, a, z} with the occluder's conventions
+ *   (a' = clamp(a, 0, 1), a NaN a counts as 0, ABSENT when a' == 0 or z not finite, z a ray parameter).  Per ray the rows are sorted
+ *   ascending by z, stable by index, absent rows last; slot j is the j-th row of that order.  P_0 = 1, P_{j+1} = P_j (1 - a'_j).
+ *   Deep sample d is BEHIND slot j iff zf_d >= z_j (a NaN zf is in front; samples are not clipped): q_d = P_m, m the number of
+ *   present slots d is behind.
+ *     pass_i[c]  = sum over layer i's samples of q_d x_d[c],  x = {r, g, b, zw, a}: lane (d mod 64) of the ray's wave, d the sample's
+ *                  index in the RAY's list, takes its samples of the layer ascending, acc = acc + q x; the 64 sums go through the
+ *                  compositor's in-place wave scan (lanes without a sample of the layer hold +0).  A layer without samples: +0.
+ *     Af_j       = sum over ALL samples of the ray of (behind slot j ? +0 : a_d): lane (d mod 64) ascending, then the same scan.
+ *     T_j = 1 - Af_j where > 0, else 0 (NaN: 0)     s_j = (a'_j T_j) P_j     share_j = {s r, s g, s b, s z, s}; an absent row: five +0
+ *     mixed[c]   = ((((pass_0 + pass_1) + ..) + pass_{l-1}) + share_0) + .. + share_{E-1}, slots in sorted order
+ *   mixed_out[n][5]; scene_out[n][l][5] = pass_i or NULL; shares[n][E][5] by the rows' own index, or NULL.  E == 0 is the flatten; a
+ *   ray with no deep sample and no present row gives five exact zeros.  One launch, one wave per ray, no LDS.
+ * STNERF_EINVAL before any launch: a null pointer that is not optional; l outside 1..STNERF_MAX_LAYERS; S outside 1..256; w_min or
+ *   merge_dz negative or NaN; raw or samples not 16-byte aligned; E outside 0..8; capacity < 0; a workspace that is too small. */
+#define STNERF_DEEP_MAX_ELEMENTS 8
+int64_t stnerf_deep_workspace_bytes(int64_t n);
+int stnerf_deep_count(const float* t, const uint8_t* mask, const float* merged_weights, int64_t n, int l, int S,
+                      const stnerf_composite_params* params_host, float w_min, float merge_dz, int32_t* counts, stnerf_stream_t stream);
+int stnerf_deep_offsets(const int32_t* counts, int64_t n, int64_t max_count, int64_t* offsets, void* workspace, int64_t workspace_bytes,
+                        stnerf_stream_t stream);
+int stnerf_deep_fill(const float* t, const float* raw, const uint8_t* mask, const float* merged_weights, int64_t n, int l, int S,
+                     const stnerf_composite_params* params_host, float w_min, float merge_dz, const int64_t* offsets, float* samples,
+                     int64_t capacity, int64_t* deep_total, stnerf_stream_t stream);
+int stnerf_deep_composite(const int64_t* offsets, const float* samples, int64_t n, int l, const float* elements, int E, float* mixed_out,
+                          float* scene_out, float* shares, stnerf_stream_t stream);
+/* The render call with deep output: stnerf_render_options followed by the deep fields.  stnerf_render_rays_opts and
+ * stnerf_render_workspace_bytes_opts accept a pointer to either record and tell them apart by struct_size, so every caller of the
+ * shorter record -- the named entries among them -- goes on as it was, and an all-zero tail is "no deep output": no new launch, no
+ * changed bit, the same render workspace.
+ *   deep_samples != NULL turns the feature on.  It needs scene_out (as the occluder does: the merged weights exist only with the scene
+ *   passes), deep_offsets, deep_total and deep_workspace, and params->n1 + n2 (n1 with only_coarse) <= 256.  The launches count ->
+ *   offsets -> fill follow the final stage's scene pass (and stnerf_scene_occluder if there is one) on the same stream while t, raw
+ *   and the merged weights are live; the deep frame is of the scene WITHOUT the occluder.  The render workspace is unchanged.
+ *   deep_workspace: stnerf_deep_workspace_bytes(n) + 4 n bytes on the device, 8-byte aligned (the scan's scratch, then the counts). */
+typedef struct stnerf_render_options_deep {
+    stnerf_render_options base;             /* base.struct_size = sizeof(stnerf_render_options_deep)                                */
+    float deep_w_min;                       /* >= 0                                                                                 */
+    float deep_merge_dz;                    /* >= 0; 0: every kept sample is a segment                                              */
+    int64_t* deep_offsets;                  /* device int64 [n + 1]                                                                 */
+    float* deep_samples;                    /* device [deep_capacity][8], 16-byte aligned, or NULL = no deep output                 */
+    int64_t deep_capacity;                  /* records deep_samples holds                                                           */
+    int64_t* deep_total;                    /* device int64: the records the call needs                                             */
+    void* deep_workspace;                   /* device, stnerf_deep_workspace_bytes(n) + 4 n bytes                                   */
+} stnerf_render_options_deep;
+
 /* ---- Progressive multi-sample frames (csrc/accumulate.hip): a frame as the per-pixel mean of several
  * passes -- each with its own sub-pixel offset, shutter time and seed -- in which a pixel stops being sampled once its running
  * mean is known well enough.  Three helpers around the render entries, every fp32 operation below on its own (no contraction).

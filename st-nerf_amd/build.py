@@ -22,6 +22,7 @@ SOURCES = [
     ("sampler.hip", ["-ffp-contract=off"]),
     ("composite.hip", ["-ffp-contract=off"]),
     ("occluder.hip", ["-ffp-contract=off"]),
+    ("deep.hip", ["-ffp-contract=off"]),
     ("resample.hip", ["-ffp-contract=off"]),
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),

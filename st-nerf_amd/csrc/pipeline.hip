@@ -136,11 +136,32 @@ struct Workspace {
 
 const stnerf_render_options kNoOptions = {(int32_t)sizeof(stnerf_render_options)};
 
+// The record is stnerf_render_options or, with the deep fields behind it, stnerf_render_options_deep: struct_size says which.
 int check_options_size(const stnerf_render_options* opts, const char* what) {
-    STNERF_REQUIRE(!opts || opts->struct_size == (int32_t)sizeof(stnerf_render_options),
-                   "%s: stnerf_render_options.struct_size = %d is not a size this library knows (%d): set it to sizeof", what,
-                   opts ? (int)opts->struct_size : 0, (int)sizeof(stnerf_render_options));
+    STNERF_REQUIRE(!opts || opts->struct_size == (int32_t)sizeof(stnerf_render_options) || opts->struct_size == (int32_t)sizeof(stnerf_render_options_deep),
+                   "%s: stnerf_render_options.struct_size = %d is not a size this library knows (%d, or %d with the deep fields): set it to sizeof", what,
+                   opts ? (int)opts->struct_size : 0, (int)sizeof(stnerf_render_options), (int)sizeof(stnerf_render_options_deep));
     return STNERF_OK;
+}
+
+// the deep fields of a record that has them; nullptr: no deep output
+const stnerf_render_options_deep* deep_options(const stnerf_render_options* opts) {
+    if (!opts || opts->struct_size != (int32_t)sizeof(stnerf_render_options_deep)) return nullptr;
+    const stnerf_render_options_deep* d = reinterpret_cast<const stnerf_render_options_deep*>(opts);
+    return d->deep_samples ? d : nullptr;
+}
+
+// Deep output (include/stnerf.h): count -> offsets -> fill on the final stage's buffers, behind its scene pass.
+int launch_deep(const stnerf_render_options_deep& d, const float* t, const float* raw, const uint8_t* mask, const float* merged_weights, int64_t n, int l,
+                int S, const stnerf_composite_params* cp, stnerf_stream_t stream) {
+    const int64_t scan = stnerf_deep_workspace_bytes(n);
+    int32_t* counts = reinterpret_cast<int32_t*>(static_cast<char*>(d.deep_workspace) + scan);
+    int rc = stnerf_deep_count(t, mask, merged_weights, n, l, S, cp, d.deep_w_min, d.deep_merge_dz, counts, stream);
+    if (rc) return rc;
+    rc = stnerf_deep_offsets(counts, n, (int64_t)l * S, d.deep_offsets, d.deep_workspace, scan, stream);
+    if (rc) return rc;
+    return stnerf_deep_fill(t, raw, mask, merged_weights, n, l, S, cp, d.deep_w_min, d.deep_merge_dz, d.deep_offsets, d.deep_samples, d.deep_capacity,
+                            d.deep_total, stream);
 }
 
 }  // namespace
@@ -318,8 +339,19 @@ struct Call {
 };
 
 // Every argument check of the render call, on the host and before anything is launched.
-int check_call(RENDER_PARAMS, const stnerf_render_options& o, Call* call) {
+int check_call(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, Call* call) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
+    if (deep) {
+        STNERF_REQUIRE(o.scene_out, "render_rays: deep output needs scene_out (the merged weights exist only with the scene passes)");
+        STNERF_REQUIRE(deep->deep_offsets && deep->deep_total && deep->deep_workspace, "render_rays: deep output needs deep_offsets, deep_total and deep_workspace");
+        STNERF_REQUIRE(deep->deep_w_min >= 0.f && deep->deep_merge_dz >= 0.f, "render_rays: deep_w_min = %g / deep_merge_dz = %g is negative or NaN",
+                       (double)deep->deep_w_min, (double)deep->deep_merge_dz);
+        STNERF_REQUIRE(deep->deep_capacity >= 0 && ((uintptr_t)deep->deep_samples & 15) == 0 && ((uintptr_t)deep->deep_workspace & 7) == 0,
+                       "render_rays: deep_capacity = %lld, deep_samples 16-byte and deep_workspace 8-byte aligned", (long long)deep->deep_capacity);
+        const int Sd = p->only_coarse ? p->n1 : p->n1 + p->n2;
+        STNERF_REQUIRE(Sd <= 256 && n <= (int64_t)INT32_MAX / ((int64_t)(p->l > 0 ? p->l : 1) * (Sd > 0 ? Sd : 1)),
+                       "render_rays: deep output packs first_k in eight bits and one call's records in 31: samples per layer <= 256, n l S < 2^31");
+    }
     STNERF_REQUIRE(!o.occluder || (o.scene_out && o.occluded_mixed),
                    "render_rays: an occluder needs scene_out and occluded_mixed (the merged weights exist only with the scene passes)");
     STNERF_REQUIRE(o.occluder || (!o.occluder_stops && !o.occluded_mixed && !o.occluded_scene && !o.occluder_share),
@@ -474,7 +506,7 @@ int check_call(RENDER_PARAMS, const stnerf_render_options& o, Call* call) {
 // which lie over that stage's points and stay live until the call returns.  occluder_stops: an opaque row's depth is folded into
 // t_stop right after stnerf_ray_stop, so the flagged layers' row lists leave out the fine samples behind it.
 // An option that is absent (a null table, no flag set, no bits, every mode OFF) adds no launch and changes none.
-int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const Call& c, const Plan& pl, const Workspace& w, stnerf_stream_t stream) {
+int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, const Call& c, const Plan& pl, const Workspace& w, stnerf_stream_t stream) {
     const int l = p->l, n1 = p->n1, n2 = p->n2, S = n1 + n2, rs = p->ray_stride;
     const bool cached = c.cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
     const uint32_t lcap = c.lcap, lreuse = c.lreuse, term = c.term;
@@ -667,6 +699,10 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const Call& c
                                        o.occluder_share, nullptr, nullptr, stream);
             if (rc) return rc;
         }
+        if (deep) {
+            rc = launch_deep(*deep, w.t_c, w.raw_c, mask, w.xyz_c, n, l, n1, &cp, stream);
+            if (rc) return rc;
+        }
         return clear_mask_hints(mask, n * l, as_stream(stream));
     }
     if (term) {   // (before the resampler overwrites the weights with the fine points)
@@ -713,6 +749,10 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const Call& c
                                    o.occluder_share, nullptr, nullptr, stream);
         if (rc) return rc;
     }
+    if (deep) {
+        rc = launch_deep(*deep, w.t_f, w.raw_f, mask, w.xyz_f, n, l, S, &cp, stream);
+        if (rc) return rc;
+    }
     return clear_mask_hints(mask, n * l, as_stream(stream));
 }
 
@@ -722,13 +762,14 @@ extern "C" int stnerf_render_rays_opts(RENDER_PARAMS, const stnerf_render_option
     const int src = check_options_size(opts, "render_rays");
     if (src) return src;
     const stnerf_render_options& o = opts ? *opts : kNoOptions;
+    const stnerf_render_options_deep* deep = deep_options(opts);
     Call call;
-    const int rc = check_call(RENDER_ARGS, o, &call);
+    const int rc = check_call(RENDER_ARGS, o, deep, &call);
     if (rc) return rc;
     if (n == 0) return STNERF_OK;
     const Plan pl = make_plan(n, p->l, p->n1, p->n2, p->only_coarse);
     const Workspace w(workspace, workspace_bytes, pl, call.rows, n, p->l);
-    return launch_sequence(RENDER_ARGS, o, call, pl, w, stream);
+    return launch_sequence(RENDER_ARGS, o, deep, call, pl, w, stream);
 }
 
 // ---- the fixed-argument forms (include/stnerf.h): each names the options up to the one it introduced, in the record's order, and

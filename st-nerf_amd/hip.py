@@ -100,6 +100,23 @@ class RenderOptions(C.Structure):
         super().__init__(struct_size=C.sizeof(RenderOptions), **fields)
 
 
+class RenderOptionsDeep(C.Structure):
+    """stnerf_render_options_deep (include/stnerf.h): ``RenderOptions`` followed by the deep fields; struct_size says which of the two
+    a record is.  ``RenderOptionsDeep()`` is "no feature" too.  ``ref()`` is what the render entries take."""
+    _fields_ = RenderOptions._fields_ + [("deep_w_min", C.c_float), ("deep_merge_dz", C.c_float), ("deep_offsets", C.c_void_p),
+                                         ("deep_samples", c_f32p), ("deep_capacity", c_i64), ("deep_total", C.c_void_p),
+                                         ("deep_workspace", C.c_void_p)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=C.sizeof(RenderOptionsDeep), **fields)
+
+    def ref(self):
+        return C.cast(C.pointer(self), C.POINTER(RenderOptions))
+
+
+DEEP_MAX_ELEMENTS = 8   # STNERF_DEEP_MAX_ELEMENTS
+
+
 class LensRecord(C.Structure):
     """stnerf_lens (include/stnerf.h): the distortion coefficients, the plane in focus, the device table of lens points and the
     pass's place in it.  ``LensRecord()`` is "no lens": all zero, struct_size set."""
@@ -230,6 +247,13 @@ _PROTOS = {
     "stnerf_scene_occluder": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), c_f32p, c_f32p,
                                         c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_occluder_stop": (C.c_int, [c_f32p, c_i64, c_f32p, C.c_void_p]),
+    "stnerf_deep_workspace_bytes": (c_i64, [c_i64]),
+    "stnerf_deep_count": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), C.c_float, C.c_float,
+                                    C.c_void_p, C.c_void_p]),
+    "stnerf_deep_offsets": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "stnerf_deep_fill": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), C.c_float, C.c_float,
+                                   C.c_void_p, c_f32p, c_i64, C.c_void_p, C.c_void_p]),
+    "stnerf_deep_composite": (C.c_int, [C.c_void_p, c_f32p, c_i64, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "stnerf_generate_rays_list": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
                                             C.c_float, C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_generate_rays_lens": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,

@@ -663,7 +663,8 @@ class LayeredRFRender(nn.Module):
                              ray_count=cnt[i:i + 1])
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
-                       scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False, background_rays=None):
+                       scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False, background_rays=None,
+                       deep=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache or the layer cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
@@ -675,7 +676,8 @@ class LayeredRFRender(nn.Module):
         ``render_rays_occluded`` (with scene): three more tensors come back; occluder_stops: its opaque rows lower the stop depth of
         the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached).
         background_rays: the piece's entries (n,) of the per-ray background mask; such a call neither captures into nor reuses the
-        background cache (the cached raw would hold the zeros of one mask); the layer cache is unaffected."""
+        background cache (the cached raw would hold the zeros of one mask); the layer cache is unaffected.  deep: the ``deep=`` dict of
+        ``ops.render_rays`` (with scene): offsets, samples and total come back last."""
         from stnerf_amd import hip
         n, l, dev = rays.shape[0], self.total_layers, rays.device
         p = self._render_params(rays.shape[1], pivot, retiming, only_coarse, thr, bthr, window)
@@ -704,6 +706,8 @@ class LayeredRFRender(nn.Module):
             kw.update(occluder=occluder, occluder_stops=bool(occluder_stops) and "terminate" in kw)
         if background_rays is not None:
             kw.update(background_rays=background_rays)
+        if deep is not None:
+            kw.update(deep=deep)
         table = self._layer_alpha_table()
         if table is not None:
             kw.update(layer_alpha=table)
@@ -895,6 +899,34 @@ class LayeredRFRender(nn.Module):
         occluded = dict(mixed=trip(raw[6]), scene=[trip(raw[7][:, i]) for i in range(l)], share=trip(raw[8]))
         return self.as_reference_tuple(raw[:5]), scene, occluded
 
+    def render_rays_deep(self, rays, spec=None, only_coarse=False, density_threshold=0.0001, bkgd_density_threshold=0.0,
+                         ref_chunk: Optional[int] = None, occluder=None, capacity: Optional[int] = None):
+        """``render_rays_scene`` with deep output -> (the reference 5-tuple, scene, DeepFrame) -- or, with ``occluder`` (n,5),
+        (5-tuple, scene, occluded, DeepFrame) as ``render_rays_occluded`` returns them; the deep frame is of the scene WITHOUT the
+        occluder.  ``spec``: a ``stnerf_amd.DeepSpec`` (None: the default, every sample of nonzero weight its own record).  The
+        frame is a piece of H = 1, W = n pixels: per ray the kept samples of the final stage with their premultiplied colour, alpha
+        and depths (include/stnerf.h states the rules), on which ``DeepFrame.composite`` puts depth-tested elements with no network.
+        The five outputs and ``scene`` are the bits of ``render_rays_scene``.  The call never re-renders and never drops: every launch
+        piece's record buffer has the worst case n l S records, and the piece is shrunk so that the buffer stays under
+        ``stnerf_amd.deep.PIECE_BUFFER_BYTES``; the piece's total is read back (one host sync per piece) and that many records join
+        the frame's list.  ``capacity``: records per launch piece instead of the worst case; a piece that needs more raises
+        RuntimeError with the total it needs.  Inference only, one rank, the fused pipeline only."""
+        from stnerf_amd import deep as D
+        self._refuse_scene_call("render_rays_deep", "deep output has", "render on one rank")
+        spec = D.as_spec(spec) or D.DeepSpec()
+        if occluder is not None and (not torch.is_tensor(occluder) or tuple(occluder.shape) != (rays.shape[0], 5)):
+            raise ValueError(f"render_rays_deep: the occluder must be a ({rays.shape[0]},5) tensor of (r, g, b, a, z) rows")
+        raw, pieces = self._render_rays_raw(rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=True,
+                                            occluder=occluder, deep=spec.options(capacity))
+        l = self.total_layers
+        trip = lambda x: (x[..., 0:3], x[..., 3:4], x[..., 4:5])
+        scene = [trip(raw[5][:, i]) for i in range(l)]
+        frame = D.DeepFrame.from_pieces(pieces, 1, rays.shape[0], l, device=rays.device)
+        if occluder is None:
+            return self.as_reference_tuple(raw[:5]), scene, frame
+        occluded = dict(mixed=trip(raw[6]), scene=[trip(raw[7][:, i]) for i in range(l)], share=trip(raw[8]))
+        return self.as_reference_tuple(raw[:5]), scene, occluded, frame
+
     def as_reference_tuple(self, raw):
         """(mixed_fine (n,5), mixed_coarse (n,5), layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l)) -> the
         reference's 5-tuple of (color (n,3), depth (n,1), acc (n,1)) triples and bool masks (layered_rfrender.py:725-734)."""
@@ -942,10 +974,11 @@ class LayeredRFRender(nn.Module):
                                      background_rays=background_rays)
 
     def _render_rays_raw(self, rays, only_coarse, density_threshold, bkgd_density_threshold, ref_chunk, scene=False, occluder=None,
-                         occluder_stops=False, background_rays=None):
+                         occluder_stops=False, background_rays=None, deep=None):
         """``render_rays_raw``; scene: a sixth tensor, the in-scene layer passes (n,l,5) of ``render_rays_scene``; occluder (with
         scene): the rows (N,5) of ``render_rays_occluded``, three more tensors (occluded mixed, scene, share); background_rays: the
-        (N,) per-ray background mask of ``render_rays_raw``."""
+        (N,) per-ray background mask of ``render_rays_raw``; deep (with scene): the ``deep=`` dict of ``ops.render_rays`` -- the
+        result is then (the tuple, [(offsets, samples) per launch piece])."""
         if not rays.is_cuda:
             raise RuntimeError("rays must live on the GPU: the MI355X render path has no CPU fallback")
         rays = rays.contiguous().float()
@@ -986,6 +1019,8 @@ class LayeredRFRender(nn.Module):
             if self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
                 raise ValueError("a per-ray background mask with mlp_schedule = 'per_net' (one launch per network): the mask walks row "
                                  "lists in the persistent stage kernels; use mlp_schedule = 'stage' or drop background_rays")
+        if deep is not None and torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("deep output in training mode: it has no backward; call model.eval() or wrap the render in torch.no_grad()")
         if scene and per_sample_bkgd_time:
             raise RuntimeError("render_rays_scene on rays that mix background frame ids (BKGD_USE_SPACE_TIME): that call takes the "
                                "op-by-op path, which has no in-scene layer passes; render one background frame id per call")
@@ -1029,8 +1064,11 @@ class LayeredRFRender(nn.Module):
         groups = self._chunk_groups(rays, retiming, ref_chunk)
         occ_ids = self._occupancy_frame_ids(rays, groups, retiming) if culling and self._occupancy.culled_layers(self) else None
         bg_ids = self._background_frame_ids(rays, groups) if bg_culling else None
-        outs = []
+        outs, deep_pieces = [], []
         cap = self.max_rays_per_launch
+        if deep is not None:   # the piece's worst-case record buffer stays under the budget
+            from stnerf_amd import deep as _deep
+            cap = min(cap, _deep.piece_rays(self.total_layers, self.coarse_ray_sample if only_coarse else self.coarse_ray_sample + self.fine_ray_sample))
         first, stripe, period = self.ray_window
         if stripe > 0:                     # launch pieces must start on a stripe boundary
             cap = max(stripe, cap // stripe * stripe)
@@ -1066,11 +1104,21 @@ class LayeredRFRender(nn.Module):
                                                     **(dict(background_id=bg_ids[gi]) if bg_ids is not None else {}),
                                                     **(dict(occluder=occluder[s:e], occluder_stops=occluder_stops)
                                                        if occluder is not None else {}),
-                                                    **(dict(background_rays=background_rays[s:e]) if background_rays is not None else {})))
+                                                    **(dict(background_rays=background_rays[s:e]) if background_rays is not None else {}),
+                                                    **(dict(deep=deep) if deep is not None else {})))
+                    if deep is not None:
+                        offsets, samples, total = outs[-1][-3:]
+                        need = int(total)           # (the one host sync of a deep piece)
+                        if need > samples.shape[0]:
+                            raise RuntimeError(f"render_rays_deep: the launch piece of rays {s}..{e} needs {need} deep records, the "
+                                               f"capacity is {samples.shape[0]}")
+                        deep_pieces.append((offsets, samples[:need].clone()))
+                        del samples, total
+                        outs[-1] = outs[-1][:-3]    # (the worst-case buffer goes back to the allocator: the next piece reuses it)
         cat = (lambda j: outs[0][j]) if len(outs) == 1 else (lambda j: torch.cat([o[j] for o in outs], 0))
         raw = tuple(cat(j) for j in range((9 if occluder is not None else 6) if scene else 5))
         self.advance_seed()
-        return raw
+        return raw if deep is None else (raw, deep_pieces)
 
     def _chunk_groups(self, rays, retiming, ref_chunk):
         """The chunk groups of a call's rays (contiguous float32, on the device): (start, end, edited boxes, pivot[, rotations]) per

@@ -362,7 +362,7 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
                    "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows", "copy_layer_raw_listed",
-                   "scene_occluder", "occluder_stop")
+                   "scene_occluder", "occluder_stop", "deep_count", "deep_offsets", "deep_fill", "deep_composite")
 
 
 def profile_begin() -> None:
@@ -991,7 +991,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
                 visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None,
                 layer_caches=None, layer_mismatch: Optional[Tensor] = None, occluder: Optional[Tensor] = None,
-                occluder_stops: bool = False, background_rays: Optional[Tensor] = None):
+                occluder_stops: bool = False, background_rays: Optional[Tensor] = None, deep: Optional[dict] = None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -1027,8 +1027,17 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     states the rule): layer 0 is evaluated only on the rays whose entry is nonzero, the others get zero outputs for it in both
     stages.  It composes with ``background_grid`` and with termination of layer 0 in the one rows launch layer 0 gets per stage.  The
     workspace is ``render_workspace_bytes(..., background_rays=True)``.  The library refuses precision 2 and a background cache in
-    CAPTURE or REUSE."""
+    CAPTURE or REUSE.
+    ``deep``: None | dict(w_min=0.0, merge_dz=0.0, capacity=None), deep output of the final stage (stnerf_render_options_deep;
+    include/stnerf.h states the rules).  It needs ``scene=True`` and appends offsets (n+1,) int64, samples (capacity,8) and total (1,)
+    int64 to the returned tuple; capacity None = the worst case n l S.  Rays whose records would pass the capacity are not written:
+    compare total with the capacity.  The render workspace is the same with or without it."""
     n, l = rays.shape[0], params.l
+    if deep is not None:
+        if not scene:
+            raise ValueError("render_rays: deep output needs scene=True (the merged weights exist only with the scene passes)")
+        if set(deep) - {"w_min", "merge_dz", "capacity"}:
+            raise ValueError(f"render_rays: deep takes w_min, merge_dz and capacity, got {sorted(deep)}")
     if occluder is not None:
         if not scene:
             raise ValueError("render_rays: an occluder needs scene=True (the merged weights exist only with the scene passes)")
@@ -1050,7 +1059,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
         lo_f = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
     # every optional argument, checked once and named once (stnerf_render_options); what is given but inert -- tau without a flag, count
     # tensors without their feature -- travels as it is: the library ignores it
-    opts = hip.RenderOptions(tau=float(tau), occluder_stops=int(bool(occluder_stops)))
+    opts = (hip.RenderOptions if deep is None else hip.RenderOptionsDeep)(tau=float(tau), occluder_stops=int(bool(occluder_stops)))
     opts.rot = _rotations(rotations, l)
     if cache is not None:
         raw_c, raw_f, mode = cache
@@ -1097,14 +1106,29 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
         occluder = occluder.contiguous()
         opts.occluder = hip.dptr(occluder, name="occluder")
         opts.occluded_mixed, opts.occluded_scene, opts.occluder_share = (hip.dptr(t) for t in occ_out)
+    deep_out = None
+    if deep is not None:
+        S_final = params.n1 if params.only_coarse else params.n1 + params.n2
+        capacity = deep.get("capacity")
+        capacity = n * l * S_final if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"render_rays: deep capacity = {capacity}")
+        scan = deep_workspace_bytes(n)
+        deep_out = (torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(max(capacity, 1), 8, dtype=torch.float32, device=dev)[:capacity],
+                    torch.zeros(1, dtype=torch.int64, device=dev))
+        deep_ws = torch.empty((scan + 4 * n + 7) // 8 + 1, dtype=torch.int64, device=dev)
+        opts.deep_w_min, opts.deep_merge_dz, opts.deep_capacity = float(deep.get("w_min", 0.0)), float(deep.get("merge_dz", 0.0)), capacity
+        opts.deep_offsets, opts.deep_total = hip.dptr(deep_out[0], torch.int64), hip.dptr(deep_out[2], torch.int64)
+        opts.deep_samples, opts.deep_workspace = C.c_void_p(deep_out[1].data_ptr()), hip.dptr(deep_ws, torch.int64)
     hip.check(hip.lib().stnerf_render_rays_opts(hip.dptr(rays, name="rays"), n, bp, bstride, C.byref(nets), C.byref(params),
                                                 hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
                                                 hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
                                                 hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8),
-                                                C.byref(opts), hip.stream_ptr()), "stnerf_render_rays")
+                                                C.byref(opts) if deep is None else opts.ref(), hip.stream_ptr()), "stnerf_render_rays")
     out = (mix_c, mix_c, lo_c, lo_c, mask) if params.only_coarse else (mix_f, mix_c, lo_f, lo_c, mask)
     out = out + (scene_out,) if scene else out
-    return out + occ_out if occ_out is not None else out
+    out = out + occ_out if occ_out is not None else out
+    return out + deep_out if deep_out is not None else out
 
 
 # ---------------------------------------------------------------------------------------- depth-tested occluders
@@ -1152,6 +1176,95 @@ def occluder_stop(occluder: Tensor, t_stop: Tensor) -> Tensor:
     hip.check(hip.lib().stnerf_occluder_stop(hip.dptr(occluder, name="occluder"), occluder.shape[0], hip.dptr(t_stop, name="t_stop"),
                                              hip.stream_ptr()), "stnerf_occluder_stop")
     return t_stop
+
+
+# ---------------------------------------------------------------------------------------- deep frames
+def deep_workspace_bytes(n: int) -> int:
+    """Bytes of scratch ``deep_offsets`` needs for n rays (stnerf_deep_workspace_bytes); not part of the render workspace."""
+    b = hip.lib().stnerf_deep_workspace_bytes(int(n))
+    hip.check(b if b < 0 else hip.OK, "stnerf_deep_workspace_bytes")
+    return int(b)
+
+
+def _deep_ray_args(what, t, mask, merged_weights, params, rgb_activated, evaluated):
+    if t.dim() != 3 or tuple(merged_weights.shape) != tuple(t.shape):
+        raise ValueError(f"{what}: t and merged_weights must be (n,l,S) alike, got {tuple(t.shape)} and {tuple(merged_weights.shape)}")
+    if mask is not None and tuple(mask.shape) != tuple(t.shape[:2]):
+        raise ValueError(f"{what}: mask must be {tuple(t.shape[:2])}, got {tuple(mask.shape)}")
+    return params if params is not None else composite_params(evaluated=evaluated, rgb_activated=rgb_activated)
+
+
+def deep_count(t: Tensor, mask: Optional[Tensor], merged_weights: Tensor, w_min: float = 0.0, merge_dz: float = 0.0,
+               params: Optional["hip.CompositeParams"] = None, rgb_activated: bool = False, evaluated: Optional[Sequence[int]] = None,
+               counts: Optional[Tensor] = None) -> Tensor:
+    """The deep segments of every ray (stnerf_deep_count; include/stnerf.h states the rules): t, merged_weights (n,l,S) and mask
+    (n,l) uint8 | None as ``composite_scene`` took and left them -> counts (n,) int32."""
+    p = _deep_ray_args("deep_count", t, mask, merged_weights, params, rgb_activated, evaluated)
+    n, l, S = t.shape
+    if counts is None:
+        counts = torch.empty(n, dtype=torch.int32, device=t.device)
+    elif tuple(counts.shape) != (n,):
+        raise ValueError(f"deep_count: counts must be ({n},), got {tuple(counts.shape)}")
+    hip.check(hip.lib().stnerf_deep_count(hip.dptr(t, name="t"), hip.dptr(mask, torch.uint8, "mask"), hip.dptr(merged_weights, name="merged_weights"),
+                                          n, l, S, C.byref(p), float(w_min), float(merge_dz), hip.dptr(counts, torch.int32, "counts"),
+                                          hip.stream_ptr()), "stnerf_deep_count")
+    return counts
+
+
+def deep_offsets(counts: Tensor, max_count: int, offsets: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """counts (n,) int32, each at most ``max_count`` (l S) -> offsets (n+1,) int64, their ordered exclusive scan and the total
+    (stnerf_deep_offsets).  workspace: uint8, at least ``deep_workspace_bytes(n)``; None: made here."""
+    n = counts.shape[0]
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=counts.device)
+    elif tuple(offsets.shape) != (n + 1,):
+        raise ValueError(f"deep_offsets: offsets must be ({n + 1},), got {tuple(offsets.shape)}")
+    if workspace is None:
+        workspace = torch.empty(deep_workspace_bytes(n), dtype=torch.uint8, device=counts.device)
+    hip.check(hip.lib().stnerf_deep_offsets(hip.dptr(counts, torch.int32, "counts"), n, int(max_count), hip.dptr(offsets, torch.int64, "offsets"),
+                                            hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(), hip.stream_ptr()),
+              "stnerf_deep_offsets")
+    return offsets
+
+
+def deep_fill(t: Tensor, raw: Tensor, mask: Optional[Tensor], merged_weights: Tensor, offsets: Tensor, samples: Tensor,
+              w_min: float = 0.0, merge_dz: float = 0.0, params: Optional["hip.CompositeParams"] = None, rgb_activated: bool = False,
+              evaluated: Optional[Sequence[int]] = None, total: Optional[Tensor] = None):
+    """The deep records at ``offsets`` (stnerf_deep_fill): raw (n,l,S,4); samples (capacity,8) is written in place, a ray whose range
+    would pass the capacity is left unwritten.  -> (samples, total (1,) int64 = the records needed, whatever the capacity)."""
+    p = _deep_ray_args("deep_fill", t, mask, merged_weights, params, rgb_activated, evaluated)
+    n, l, S = t.shape
+    if tuple(raw.shape) != (n, l, S, 4) or tuple(offsets.shape) != (n + 1,) or samples.dim() != 2 or samples.shape[1] != 8:
+        raise ValueError(f"deep_fill: raw must be ({n},{l},{S},4), offsets ({n + 1},) and samples (capacity,8), got {tuple(raw.shape)}, "
+                         f"{tuple(offsets.shape)}, {tuple(samples.shape)}")
+    if total is None:
+        total = torch.zeros(1, dtype=torch.int64, device=t.device)
+    hip.check(hip.lib().stnerf_deep_fill(hip.dptr(t, name="t"), hip.dptr(raw, name="raw"), hip.dptr(mask, torch.uint8, "mask"),
+                                         hip.dptr(merged_weights, name="merged_weights"), n, l, S, C.byref(p), float(w_min), float(merge_dz),
+                                         hip.dptr(offsets, torch.int64, "offsets"), hip.dptr(samples, name="samples"), samples.shape[0],
+                                         hip.dptr(total, torch.int64, "total"), hip.stream_ptr()), "stnerf_deep_fill")
+    return samples, total
+
+
+def deep_composite(offsets: Tensor, samples: Tensor, l: int, elements: Optional[Tensor] = None, want_scene: bool = True,
+                   want_shares: bool = True):
+    """Depth-tested elements composited on a deep list (stnerf_deep_composite; include/stnerf.h states the rules): offsets (n+1,)
+    int64, samples (total,8), elements (n,E,5) rows {r, g, b, a, z}, 0 <= E <= 8, or None = the flatten.  -> (mixed (n,5), scene
+    (n,l,5) | None, shares (n,E,5) | None)."""
+    n = offsets.shape[0] - 1
+    if offsets.dim() != 1 or n < 0 or samples.dim() != 2 or samples.shape[1] != 8:
+        raise ValueError(f"deep_composite: offsets must be (n+1,) and samples (total,8), got {tuple(offsets.shape)} and {tuple(samples.shape)}")
+    E = 0 if elements is None else elements.shape[1] if elements.dim() == 3 else -1
+    if elements is not None and (E < 0 or tuple(elements.shape) != (n, E, 5)):
+        raise ValueError(f"deep_composite: elements must be ({n},E,5) rows of (r, g, b, a, z), got {tuple(elements.shape)}")
+    dev = offsets.device
+    mixed = torch.empty(n, 5, dtype=torch.float32, device=dev)
+    scene = torch.empty(n, int(l), 5, dtype=torch.float32, device=dev) if want_scene else None
+    shares = torch.empty(n, E, 5, dtype=torch.float32, device=dev) if want_shares and E > 0 else None
+    hip.check(hip.lib().stnerf_deep_composite(hip.dptr(offsets, torch.int64, "offsets"), hip.dptr(samples, name="samples") if samples.numel() else None,
+                                              n, int(l), hip.dptr(elements, name="elements") if E > 0 else None, E, hip.dptr(mixed),
+                                              hip.dptr(scene), hip.dptr(shares), hip.stream_ptr()), "stnerf_deep_composite")
+    return mixed, scene, shares
 
 
 def ray_parameter(rays: Tensor, pose: Tensor, zcam) -> Tensor:

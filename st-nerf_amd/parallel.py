@@ -404,7 +404,7 @@ def _view_frame_ids(model, frame_ids):
 
 def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, bkgd_density_threshold=0.0,
                 chuncks: int = 512 * 7, stripe_rows: int = 1, device="cuda", gather: Optional[str] = None, scene: bool = False,
-                occluder=None, occluder_stops: bool = False, lens=None):
+                occluder=None, occluder_stops: bool = False, lens=None, deep=None):
     """One view from its camera: rays generated on the device (no CPU ray tensor), ``layered_batchify_ray`` semantics, the
     reference's 5-tuple on every rank.  Without a process group: the whole view on this GPU.  With one: interleaved
     stripes of ``stripe_rows`` image rows over the ranks (rank r generates and renders rows r, r + G, ... only), one
@@ -415,9 +415,17 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     ``LayeredRFRender.render_rays_occluded`` (``occluder_stops``: its ``stops``); one rank only, as ``scene``.
     ``lens``: a ``stnerf_amd.lens.Lens`` (or the dict of its arguments) that distorts -- the rays come from
     ``stnerf_generate_rays_lens`` and everything downstream is unchanged, the caches keyed by the lens too; one rank only.  A lens
-    with an aperture needs several passes: ValueError here, ``render_view_accumulated`` renders it."""
+    with an aperture needs several passes: ValueError here, ``render_view_accumulated`` renders it.
+    ``deep``: a ``stnerf_amd.DeepSpec`` -> what ``LayeredRFRender.render_rays_deep`` returns, (5-tuple, scene, DeepFrame) or with an
+    ``occluder`` (5-tuple, scene, occluded, DeepFrame), the frame h x w; one rank only, as ``scene``; not with ``occluder_stops``."""
     from stnerf_amd import ops
     from stnerf_amd.utils.batchify_rays import layered_batchify_ray
+    if deep is not None:
+        from stnerf_amd.deep import as_spec
+        deep = as_spec(deep)
+        if occluder_stops:
+            raise ValueError("render_view(deep=...) with occluder_stops: the deep frame is of the scene without the occluder, and the "
+                             "stop would cut it at the occluder; drop occluder_stops")
     lens = _checked_lens(lens, K, h, w)
     if lens is not None and lens.aperture > 0.0:
         raise ValueError("render_view(lens=...) with aperture > 0: defocus is the mean of several passes through the lens; render it "
@@ -430,6 +438,11 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
         try:
             model.view_key, model.view_frame_ids = _view_key(model, K, T, h, w, frame_ids, lens), _view_frame_ids(model, frame_ids)
             with torch.no_grad():
+                if deep is not None:
+                    out = (model.render_rays_deep(rays, deep, occluder=occluder) if n_total < chuncks else
+                           model.render_rays_deep(rays, deep, False, density_threshold, bkgd_density_threshold, ref_chunk=chuncks, occluder=occluder))
+                    out[-1].H, out[-1].W = h, w
+                    return out
                 if occluder is not None:
                     if n_total < chuncks:
                         return model.render_rays_occluded(rays, occluder, stops=occluder_stops)
@@ -446,6 +459,9 @@ def render_view(model, K, T, h: int, w: int, frame_ids, density_threshold=0.0, b
     if lens is not None:
         raise RuntimeError("render_view(lens=...) on a view sharded over more than one rank: a lens in the windowed ray generator is out "
                            "of scope; render through a lens on one rank (model.shard_views = False)")
+    if deep is not None:
+        raise RuntimeError("render_view(deep=...) on a view sharded over more than one rank: a \"deep\" gather mode is out of scope; "
+                           "render deep frames on one rank (model.shard_views = False)")
     if occluder is not None:
         raise RuntimeError("render_view(occluder=...) on a view sharded over more than one rank: a \"scene\" gather mode is out of scope; "
                            "render with an occluder on one rank (model.shard_views = False)")

@@ -34,7 +34,7 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None, lattice=None):
+                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None, lattice=None, deep=None):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -141,6 +141,21 @@ class LayeredNeuralRenderer:
             if self.scene_passes or self.occluder is not None:
                 raise ValueError("lattice= with scene_passes or occluder=: interpolating those passes is out of scope")
         self.lattice_stats = []
+        # deep: an stnerf_amd.DeepSpec (or True): every frame also keeps its deep frame -- the per-pixel list of the final stage's
+        # weighted samples, on which any number of depth-tested elements are composited after the render (render_pose's `deep`;
+        # DESIGN.md section 7).  The frames are kept in deep_frames (on the device, in the render's own row order: inverse_y_axis does
+        # not reorder a list) and handed to on_frame as the keyword `deep`.  It does not combine with accumulate, lattice, reproject
+        # or occluder_stops.  Not in the reference (keyword-only, off by default)
+        self.deep = None
+        if deep is not None:
+            from stnerf_amd.deep import as_spec as as_deep_spec
+            self.deep = as_deep_spec(deep)
+            for name, value in (("accumulate", self.accumulate), ("lattice", self.lattice), ("reproject", self.reproject)):
+                if value is not None:
+                    raise ValueError(f"deep= with {name}=: such a frame is not one sample list per pixel")
+            if self.occluder_stops:
+                raise ValueError("deep= with occluder_stops: the deep frame is of the scene without the occluder")
+        self.deep_frames = []
         self.layer_num = cfg.DATASETS.LAYER_NUM
         self.frame_num = cfg.DATASETS.FRAME_NUM
         self.display_layers = {i: 1 for i in range(self.total_layers)}
@@ -441,14 +456,14 @@ class LayeredNeuralRenderer:
 
     # ---- rendering -------------------------------------------------------------------------------------------
     def render_pose(self, pose, K, layer_frame_pair, density_threshold=0, bkgd_density_threshold=0, scene_passes=False, occluder=None,
-                    accumulate=None, lens=None, reproject=None, lattice=None):
+                    accumulate=None, lens=None, reproject=None, lattice=None, deep=None):
         """-> color (H,W,3), depth (H,W,1), color_layer, depth_layer on the device (:364-391); with ``scene_passes`` a fifth
         element, the dict of in-scene layer passes (stnerf_amd.render.render_pose); with ``occluder`` = (rgba, depth) that dict
         also holds the occluded results; with ``accumulate`` = a spec the frame is a progressive multi-sample one and the fifth
         element is its ``stats``.  ``lens``: the camera's lens for this frame (default: the renderer's ``lens``).
         ``reproject`` = (spec, plates): the background is warped from those key plates (stnerf_amd.render.render_pose); the fifth
         element is the frame's ``stats``.  ``lattice`` = a spec: the frame is an adaptive lattice one and the fifth element is its
-        ``stats``."""
+        ``stats``.  ``deep`` = a ``DeepSpec``: the fifth element is the passes dict with ``deep``, the frame's ``DeepFrame``."""
         lens = self.lens if lens is None else lens
         return _render_pose(self.model, pose, K, self.height, self.width, layer_frame_pair, self.far, density_threshold,
                             bkgd_density_threshold, **(dict(scene_passes=True) if scene_passes else {}),
@@ -456,7 +471,8 @@ class LayeredNeuralRenderer:
                             **(dict(accumulate=accumulate) if accumulate is not None else {}),
                             **(dict(lens=lens) if lens is not None else {}),
                             **(dict(reproject=reproject) if reproject is not None else {}),
-                            **(dict(lattice=lattice) if lattice is not None else {}))
+                            **(dict(lattice=lattice) if lattice is not None else {}),
+                            **(dict(deep=deep) if deep is not None else {}))
 
     def _key_plates(self, idx, density_threshold, bkgd_density_threshold):
         """The key plates frame ``idx`` uses (``ReprojectSpec.keys_of``) -> (plates, how many were rendered for this frame).  A
@@ -514,11 +530,15 @@ class LayeredNeuralRenderer:
                 stats = dict(stats, status=torch.flip(stats["status"], [0]))
             self._frame_stats = stats
             self.lattice_stats.append({k: v for k, v in stats.items() if k != "status"})
-        elif self.scene_passes or occ is not None:
+        elif self.scene_passes or occ is not None or self.deep is not None:
             color, depth, color_layer, depth_layer, passes = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                              self.layer_frame_pairs[idx], density_threshold,
                                                                              bkgd_density_threshold, scene_passes=True,
-                                                                             **(dict(occluder=occ) if occ is not None else {}))
+                                                                             **(dict(occluder=occ) if occ is not None else {}),
+                                                                             **(dict(deep=self.deep) if self.deep is not None else {}))
+            self._deep_frame = passes.pop("deep", None)
+            if self._deep_frame is not None:
+                self.deep_frames.append(self._deep_frame)
         else:
             color, depth, color_layer, depth_layer = self.render_pose(self.poses[idx], self.Ks[idx],
                                                                      self.layer_frame_pairs[idx], density_threshold,
@@ -542,6 +562,8 @@ class LayeredNeuralRenderer:
             kw["reprojected"] = self._frame_stats
         if self.lattice is not None:
             kw["lattice"] = self._frame_stats
+        if self.deep is not None:
+            kw["deep"] = self._deep_frame
         if self.occluder is not None:
             has = passes is not None and "color_occluded" in passes
             kw["occluded"] = {k: v for k, v in passes.items() if "occlude" in k} if has else None

@@ -15,7 +15,7 @@ from stnerf_amd.parallel import render_view, total_layers
 
 def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Sequence[Tuple[int, float]], far: float,
                 density_threshold: float = 0, bkgd_density_threshold: float = 0, device="cuda", scene_passes: bool = False,
-                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None, reproject=None, lattice=None):
+                occluder=None, occluder_stops: bool = False, accumulate=None, lens=None, reproject=None, lattice=None, deep=None):
     """-> color (H,W,3), depth (H,W,1), color_layer [l x (H,W,3)], depth_layer [l x (H,W,1)].
 
     ``layer_frame_pair``: (layer_id, frame_id) pairs as in data/datasets/ray_dataset.py:276-281.
@@ -71,7 +71,17 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     (``parallel.render_view_lattice``).  The depth post-processing above is applied to the finished state, and
     a fifth element ``stats`` is returned: ``rendered``, ``filled``, ``forced``, ``margin``, ``rays_per_level`` and ``status`` (H,W)
     uint8 (1 rendered, 2 filled).  A distorting ``lens`` passes through; it does not combine with ``accumulate``, ``reproject``,
-    ``scene_passes``, an occluder or a lens with an aperture (ValueError).  Approximate; inference only; one rank only."""
+    ``scene_passes``, an occluder or a lens with an aperture (ValueError).  Approximate; inference only; one rank only.
+    ``deep`` = an ``stnerf_amd.DeepSpec``: the fifth element is returned as with ``scene_passes`` and gains ``deep``, the frame's
+    ``stnerf_amd.DeepFrame`` (H x W pixels, ``far`` set): the per-pixel list of the final stage's weighted samples, on which
+    ``DeepFrame.composite`` puts any number of depth-tested elements after the render.  With an occluder the
+    deep frame is of the scene without it.  It does not combine with ``accumulate``, ``lattice`` or ``reproject`` (ValueError: those
+    frames are not one sample list per pixel) nor with ``occluder_stops``.  Inference only; one rank only."""
+    if deep is not None:
+        for name, value in (("accumulate", accumulate), ("lattice", lattice), ("reproject", reproject)):
+            if value is not None:
+                raise ValueError(f"render_pose(deep=...) with {name}=: such a frame is not one sample list per pixel; render the deep "
+                                 f"frame without {name}=")
     if lattice is not None:
         from stnerf_amd.parallel import render_view_lattice
         frame_ids = [0.0] * total_layers(model)
@@ -140,8 +150,13 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
                       frame_ids, density_threshold, bkgd_density_threshold, device=device, gather="fine",
                       **(dict(scene=True) if scene_passes else {}),
                       **(dict(occluder=occ_rows, occluder_stops=occluder_stops) if occ_rows is not None else {}),
-                      **(dict(lens=lens) if lens is not None else {}))
-    occluded = None
+                      **(dict(lens=lens) if lens is not None else {}), **(dict(deep=deep) if deep is not None else {}))
+    occluded = frame = None
+    if deep is not None:
+        out, frame = out[:-1], out[-1]
+        frame.far = float(far)
+        if occ_rows is None:
+            out = out if scene_passes else out[0]
     if occ_rows is not None:
         (stage2, _, stage2_layer, _, _), scene, occluded = out
     else:
@@ -151,7 +166,7 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
     color_layer = [t[0].reshape(height, width, 3) for t in stage2_layer]
     depth_layer = [t[1].reshape(height, width, 1) / far for t in stage2_layer]
     if not scene_passes and occluded is None:
-        return color, depth, color_layer, depth_layer
+        return (color, depth, color_layer, depth_layer) if frame is None else (color, depth, color_layer, depth_layer, dict(deep=frame))
     passes = dict(color_scene=[t[0].reshape(height, width, 3) for t in scene],
                   alpha_scene=[t[2].reshape(height, width, 1) for t in scene],
                   depth_scene=[t[1].reshape(height, width, 1) / far for t in scene])
@@ -163,6 +178,8 @@ def render_pose(model, pose, K, height: int, width: int, layer_frame_pair: Seque
                       alpha_scene_occluded=[img(t[2], 1) for t in occluded["scene"]],
                       depth_scene_occluded=[img(t[1], 1) / far for t in occluded["scene"]],
                       occluder_share=(img(share[0], 3), img(share[2], 1), img(share[1], 1) / far))
+    if frame is not None:
+        passes["deep"] = frame
     return color, depth, color_layer, depth_layer, passes
 
 

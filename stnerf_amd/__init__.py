@@ -44,4 +44,7 @@ def __getattr__(name):
     if name in ("ReprojectSpec", "BackgroundPlate"):
         from stnerf_amd import reproject
         return getattr(reproject, name)
+    if name in ("DeepSpec", "DeepFrame"):
+        from stnerf_amd import deep
+        return getattr(deep, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
