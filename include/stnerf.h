@@ -714,16 +714,27 @@ int stnerf_occupancy_cull(const float* xyz, int64_t n, int l, int n1, const stne
  *   that is not listed gets raw[ray][i][k] = {0, 0, 0, 0}, four exact zero words, and no network runs on it.  Nothing else changes:
  *   depths, points, masks, the resampler, the compositor and the scene passes see a `raw` buffer and behave as they always did
  *   (sigma = 0 gives alpha = 0: a skipped sample weighs nothing, its depth still takes part in the merge).
- * stnerf_occupancy_rows makes one layer's row list.  ray_list / ray_count: the layer's work list (ray_list NULL: rays 0 .. n-1);
- * xyz / raw: the LAYER's slices (as in stnerf_stage_layer), with their ray strides in floats; grid_host: the layer's entry.  Writes
- *   row_list[capacity] int32: one word (ray << 8) | k per listed sample, the rows of one ray contiguous and ascending in k, the
- *     order of the rays free (it changes from run to run);
- *   row_count int32 (zeroed by the call itself, on the stream);
- *   the zero float4 of every not-listed sample of every tested ray into raw -- and nothing else of raw;
- *   counts_or_null: device, int64 [..][2], row `layer` = (samples tested, samples skipped), ACCUMULATED (the caller zeroes it).
- * STNERF_EINVAL: ns > 256, n > 2^23, capacity < n * ns, layer 0 (the background is never listed), a bad grid.  One launch: a
- * persistent grid of at most 2048 workgroups; a wave takes runs of 16 list slots, keeps their ballots in scalar registers and
- * reserves its range of the list with one atomic add per run. */
+ *
+ *   Row lists (csrc/sample_rows.hip).  Four entries make the row list of ONE layer in ONE network stage of ns samples:
+ *   stnerf_occupancy_rows (here), stnerf_visibility_rows, stnerf_background_rows and stnerf_background_ray_rows (below).  They differ
+ *   in which tests make a sample LISTED -- its ray's flag byte, !(t > t_stop[ray]), its point's cell -- and in where their rays come
+ *   from; this contract is common to all four.
+ *     Arguments.  xyz / t / raw: the LAYER's slices (as in stnerf_stage_layer) of the stage's points, depths and outputs, each with
+ *     its ray stride in floats; raw 16-byte aligned, its stride a multiple of 4 floats.  The tested rays are the first
+ *     min(n, *ray_count) slots of ray_list (ray_count NULL: n of them; ray_list NULL: the slot is the ray), or, for the two
+ *     background entries, the rays 0 .. n-1.  Per-ray arrays (t_stop, ray_flags) are indexed by the ray.
+ *     row_list[capacity] int32: one word (ray << 8) | k per listed sample.  The rows of one ray are contiguous and ascending in k;
+ *     the order of the rays is free (runs of 16 slots land in the order of their atomic adds: it changes from run to run).
+ *     raw: the zero float4 {0, 0, 0, 0} of every sample of every tested ray that is NOT listed -- and nothing else of raw.
+ *     row_count int32: zeroed by the call itself, on the stream, then the number of words.
+ *     counts_or_null: device, int64, 8-byte aligned, two words += (samples tested, samples not listed), ACCUMULATED (the caller
+ *     zeroes them): row `layer` of a [..][2] table for the two entries that take a layer, the array itself for the background's.
+ *     Limits, STNERF_EINVAL for all four: ns outside 1..256 (the sample takes 8 bits of a word), n > 2^23 (the ray takes 23),
+ *     capacity < n * ns, raw or counts misaligned, a null pointer among the required ones, a bad grid.
+ *     One launch: a persistent grid of at most 2048 workgroups of 256; a wave takes runs of 16 slots, keeps their ballots in scalar
+ *     registers, reserves the run's range of the list with one vector atomic add, and adds to each counter once.
+ * stnerf_occupancy_rows: listed = the grid test alone; rays from the layer's work list; grid_host: the layer's entry, with bits.
+ * It also refuses layer 0 (the background is never listed by this entry). */
 int stnerf_occupancy_rows(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz, int64_t xyz_ray_stride,
                           int ns, const stnerf_occupancy* grid_host, float* raw, int64_t raw_ray_stride, int32_t* row_list,
                           int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream);
@@ -757,7 +768,7 @@ int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes,
                                int32_t* counts_or_null, const int32_t* samples_host, int64_t* sample_counts_or_null,
                                stnerf_stream_t stream);
 
-/* ---- early ray termination (csrc/termination.hip) -------------------------------------------------------
+/* ---- early ray termination (csrc/termination.hip, csrc/sample_rows.hip) -------------------------------
  * Opt-in, inference only, the FINE stage only: fine samples that the coarse pass shows to lie behind enough opacity get zero
  * outputs instead of a network evaluation.  Not in the reference.
  *   Stop depth.  One ray after the coarse composite: t[l][n1] its coarse depths, wM[l][n1] its coarse MERGED weights at source
@@ -776,14 +787,12 @@ int stnerf_render_rays_samples(const float* rays, int64_t n, const float* boxes,
  * registers).  STNERF_EINVAL: a null pointer, l outside 1..STNERF_MAX_LAYERS, n1 < 1, tau outside [0, 1) or NaN. */
 int stnerf_ray_stop(const float* t, const float* merged_weights, int64_t n, int l, int n1, float tau, float* t_stop,
                     stnerf_stream_t stream);
-/* stnerf_visibility_rows makes one layer's row list under this rule: stnerf_occupancy_rows' contract (the rows of a ray
- * contiguous and ascending in k, the order of the rays free, row_count zeroed by the call, the zero float4 of every not-listed
- * sample of every tested ray and nothing else of raw, counts_or_null row `layer` += (samples tested, samples not listed)) with
- *   t: the LAYER's slice of the stage's depths, ray stride t_ray_stride floats; t_stop[n] indexed by the ray;
+/* stnerf_visibility_rows makes one layer's row list under this rule (the row-list contract above): listed = not hidden, and with
+ * a grid the grid test; rays from the layer's work list; t and t_stop[n] required.
  *   grid_host_or_null: the layer's grid, or NULL (or bits == NULL) = no grid: every sample that is not hidden is listed, and xyz
  *     is not read (it may be NULL);
  *   layer 0 allowed (without a grid; ray_list NULL = rays 0 .. n-1).
- * STNERF_EINVAL: ns > 256, n > 2^23, capacity < n * ns, a grid on layer 0, a bad grid, a grid without xyz. */
+ * It also refuses a grid on layer 0 and a grid without xyz. */
 int stnerf_visibility_rows(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz,
                            int64_t xyz_ray_stride, const float* t, int64_t t_ray_stride, const float* t_stop, int ns,
                            const stnerf_occupancy* grid_host_or_null, float* raw, int64_t raw_ray_stride, int32_t* row_list,
@@ -813,7 +822,7 @@ int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* box
                                   float tau, const int32_t* terminate_host, int64_t* visibility_counts_or_null,
                                   stnerf_stream_t stream);
 
-/* ---- the background's occupancy grid (csrc/background_rows.hip) ------------------------------------------
+/* ---- the background's occupancy grid (csrc/sample_rows.hip) ---------------------------------------------
  * Opt-in, inference only: the samples of the background that cross empty cells of a grid over its box get zero outputs instead of
  * a network evaluation.  Not in the reference.  The ray cull's rule "layer 0 cannot carry a grid" stands (a whole-ray cull of a
  * layer that runs on every ray saves nothing); this grid is an argument of its own and culls samples only.
@@ -829,18 +838,12 @@ int stnerf_render_rays_terminated(const float* rays, int64_t n, const float* box
  *   cull.  A sample that is not listed gets raw[ray][0][k] = {0, 0, 0, 0}, four exact zero words; no SpaceNet and no MotionNet runs
  *   on it.  Nothing else changes: depths, points, masks, the resampler, the compositor and the scene passes see a `raw` buffer.
  *   With early ray termination on layer 0 a fine sample is listed when it is listed by the grid AND not hidden.
- * stnerf_background_rows makes layer 0's row list of one stage: stnerf_occupancy_rows' output contract -- one word (ray << 8) | k per
- * listed sample, the rows of a ray contiguous and ascending in k, the order of the rays free, row_count zeroed by the call, the zero
- * float4 of every not-listed sample written and nothing else of raw -- with
- *   the slot being the ray: rays 0 .. n-1, no ray list, no device-side count;
- *   xyz / raw (and t): LAYER 0's slices with their ray strides in floats; grid_host: mandatory, with bits;
- *   t_or_null / t_stop_or_null: the stage's depths and stnerf_ray_stop's output [n]; with t_stop a sample with t > t_stop[ray] is
- *     not listed (a NaN depth is not hidden); t_stop NULL: the grid alone, t is not read;
- *   counts_or_null: device, int64 [2] += (samples tested, samples not listed).
- * STNERF_EINVAL: ns outside 1..256, n > 2^23, capacity < n * ns, a bad grid or a grid without bits, t_stop without t, raw not
- * 16-byte aligned (or its stride no multiple of 4 floats), counts not 8-byte aligned.  One launch: a persistent grid of at most
- * 2048 workgroups of 256; a wave takes runs of 16 rays, keeps their ballots in scalar registers and reserves its range of the list
- * with one atomic add per run. */
+ * stnerf_background_rows makes layer 0's row list of one stage (the row-list contract above): listed = the grid test, and with
+ * t_stop not hidden; the rays 0 .. n-1 -- no ray list, no device-side count; xyz / raw (and t) are LAYER 0's slices.
+ *   grid_host: mandatory, with bits;
+ *   t_or_null / t_stop_or_null: the stage's depths and stnerf_ray_stop's output [n]; t_stop NULL: the grid alone, t is not read;
+ *   counts_or_null: device, int64 [2].
+ * It also refuses a grid without bits and t_stop without t. */
 int stnerf_background_rows(int64_t n, const float* xyz, int64_t xyz_ray_stride, int ns, const stnerf_occupancy* grid_host,
                            const float* t_or_null, int64_t t_ray_stride, const float* t_stop_or_null, float* raw, int64_t raw_ray_stride,
                            int32_t* row_list, int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream);
@@ -1034,7 +1037,7 @@ typedef struct stnerf_render_options {
     float* occluder_share;                  /* device [n][5] or NULL                                                                */
     const uint8_t* bkgd_rays;               /* device uint8 [n] or NULL: the per-ray background mask (below); no named entry         */
 } stnerf_render_options;
-/* ---- Per-ray background mask (csrc/background_rays.hip) --------------------------------------------------
+/* ---- Per-ray background mask (csrc/sample_rows.hip) ------------------------------------------------------
  * Opt-in, inference only, not in the reference: the caller says ray by ray whether layer 0 is evaluated -- what a frame needs whose
  * background comes from another source on some of its rays (a reprojected plate) and from the networks on the others.
  * bkgd_rays: device uint8 [n], one byte per ray of the call; nonzero = evaluate layer 0 on this ray.  NULL: the option is absent.
@@ -1048,12 +1051,13 @@ typedef struct stnerf_render_options {
  *   stnerf_render_workspace_bytes_opts: a non-NULL bkgd_rays grows the workspace as a grid with bits does (layer 0's row list).
  *   STNERF_EINVAL before any launch: params->precision == 2; n1 + n2 > 256 or n > 2^23; a background cache (cache->mode) in CAPTURE
  *   or REUSE -- the cached raw would hold the zeros of one mask.  The layer cache is unaffected.
- * stnerf_background_ray_rows makes that row list: stnerf_background_rows' arguments, contract and host checks with two differences.
+ * stnerf_background_ray_rows makes that row list (the row-list contract above): listed = the ray's flag byte nonzero, and with a
+ * grid the grid test, and with t_stop not hidden; the rays 0 .. n-1; stnerf_background_rows' arguments otherwise.
  *   grid_host_or_null may be NULL: no cell test (a grid that is given must have bits);
  *   ray_flags: device uint8 [n], required: a ray whose byte is 0 lists nothing, gets ns zero float4 and loads no point, no depth and
- *   no grid word.  counts: a masked ray's samples are both tested and not listed.
- * One launch of the same shape as the sibling's: runs of 16 rays per wave, the run's 16 flag bytes loaded once and balloted into a
- * wave-uniform mask, ballots in scalar registers, one vector atomic add per run.  With every byte nonzero and a grid the listed set
+ *   no grid word (the run's 16 flag bytes are loaded once and balloted into a wave-uniform mask).  counts: a masked ray's samples
+ *   are both tested and not listed.
+ * It also refuses a missing ray_flags, a grid without bits and t_stop without t.  With every byte nonzero and a grid the listed set
  * and the zeros are stnerf_background_rows'. */
 int stnerf_background_ray_rows(int64_t n, const float* xyz, int64_t xyz_ray_stride, int ns, const stnerf_occupancy* grid_host_or_null,
                                const float* t_or_null, int64_t t_ray_stride, const float* t_stop_or_null, float* raw,

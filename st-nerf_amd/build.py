@@ -26,8 +26,7 @@ SOURCES = [
     ("resample.hip", ["-ffp-contract=off"]),
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),
-    ("background_rows.hip", ["-ffp-contract=off"]),
-    ("background_rays.hip", ["-ffp-contract=off"]),
+    ("sample_rows.hip", ["-ffp-contract=off"]),
     ("accumulate.hip", ["-ffp-contract=off"]),
     ("lens.hip", ["-ffp-contract=off"]),
     ("reproject.hip", ["-ffp-contract=off"]),

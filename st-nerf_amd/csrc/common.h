@@ -32,8 +32,39 @@ struct LaunchTimer {            // RAII: records start on construction, stop + b
 
 // The host checks of a stnerf_occupancy table of l entries (csrc/occupancy.hip), made before any launch.
 int check_occupancy_table(const stnerf_occupancy* table, int l, const char* what);
-// The same checks of the background's grid (csrc/background_rows.hip), the one entry that table refuses; bits are required.
+// The same checks of one entry with bits, named `layer` in the messages; refuses layer 0.
+int check_occupancy_entry(const stnerf_occupancy* grid, int layer, const char* what);
+// The same checks of the background's grid, the one entry the two above refuse; bits are required.
 int check_background_grid(const stnerf_occupancy* grid, const char* what);
+
+// One call of the row-list kernel (csrc/sample_rows.hip), as the four rows entries make it after their own refusals.  The tests of
+// "listed" are the pointers that are set: ray_flags, t_stop (with t), grid (with xyz; checked by the entry).
+struct SampleRowsCall {
+    const char* what;              // the entry's name: the prefix of every message
+    int prof_kernel, prof_kind;    // the profiler's record (LaunchTimer), with the bytes per ray and the launch tag
+    int64_t bytes_per_ray;
+    int tag;
+    bool by_list;                  // slots of ray_list (null: the slot is the ray), at most *ray_count (null: n) of them
+    const int32_t *ray_list, *ray_count;
+    const uint8_t* ray_flags;
+    int64_t n;
+    int ns;
+    const float* xyz;
+    int64_t xyz_ray_stride;
+    const stnerf_occupancy* grid;
+    const float* t;
+    int64_t t_ray_stride;
+    const float* t_stop;
+    float* raw;
+    int64_t raw_ray_stride;
+    int32_t* row_list;
+    int64_t capacity;
+    int32_t* row_count;
+    int64_t* counts;               // the two words this call adds to, or null
+    stnerf_stream_t stream;
+};
+// The shared checks, the row_count memset, the n == 0 return, the choice of kernel and its launch.
+int launch_sample_rows(const SampleRowsCall& call);
 
 #define STNERF_REQUIRE(cond, ...)                \
     do {                                         \

@@ -1,15 +1,16 @@
 // Occupancy grids (include/stnerf.h: stnerf_occupancy): a bit per cell of a performer's box, made from the
 // networks' own densities at the cell corners (occupancy_build_kernel), and the cull that clears the hit bit of a (ray, layer)
 // pair none of whose coarse sample points lies in an occupied cell (occupancy_cull_kernel).  A culled pair is in the state of
-// a ray that grazes the box -- bit 0 clear, bit 1 clear, depths real -- which every later kernel already handles.
+// a ray that grazes the box -- bit 0 clear, bit 1 clear, depths real -- which every later kernel already handles.  Also the host
+// checks of a grid, for every entry that takes one.  The sample cull's row list is stnerf_occupancy_rows (csrc/sample_rows.hip).
 // Compiled with -ffp-contract=off: the point -> cell map is a subtraction and a product, two separate fp32 operations.
 #include <math.h>
-#include <string.h>
+#include <stdio.h>
 
 #include <algorithm>
 
 #include "common.h"
-#include "occupancy_grid.h"   // OccGrid, cell_of, point_occupied: the point -> cell rule, shared with termination.hip
+#include "occupancy_grid.h"   // OccGrid, cell_of, point_occupied: the point -> cell rule, shared with sample_rows.hip
 
 using namespace stnerf;
 
@@ -40,76 +41,6 @@ __global__ void __launch_bounds__(256) occupancy_cull_kernel(const float* __rest
         seen += 1ull | (hit ? 0ull : 1ull << 32);
     }
     if (lane == 0 && counts && seen) atomicAdd(counts + layer, seen);
-}
-
-// The sample cull's row list.  A wave takes runs of ROWS_RUN consecutive slots of the layer's ray list, run
-// after run a whole grid of waves apart.  Pass 1 tests the run's samples -- lane j the samples k = j, j + 64, ... of a ray, one
-// ballot per (ray, 64 samples), all of them kept in scalar registers -- and stores the zero float4 of every sample that is not
-// listed; then ONE atomic add reserves the run's range of the list, and pass 2 writes the words (ray << 8 | k) from the ballots:
-// the rows of a ray contiguous and ascending in k, the runs in the order the adds landed.  NC = ceil(ns / 64) <= 4.
-// counts (or null): (samples tested, samples skipped), summed in the wave's registers and added once per wave.
-constexpr int ROWS_RUN = 16;
-template <int NC>
-__global__ void __launch_bounds__(256) occupancy_rows_kernel(const int32_t* __restrict__ ray_list, const int32_t* __restrict__ ray_count, int64_t n,
-                                                             const float* __restrict__ xyz, int64_t xyz_ray_stride, int ns, OccGrid g,
-                                                             float* __restrict__ raw, int64_t raw_ray_stride, int32_t* __restrict__ row_list,
-                                                             int64_t capacity, int32_t* __restrict__ row_count,
-                                                             unsigned long long* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * 4;
-    int64_t cnt = n;
-    if (ray_count) {
-        const int64_t c = *ray_count;
-        cnt = c < 0 ? 0 : (c < cnt ? c : cnt);
-    }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned long long tested = 0ull, skipped = 0ull;    // the same in every lane
-    for (int64_t slot0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS_RUN; slot0 < cnt; slot0 += waves * ROWS_RUN) {
-        const int64_t left = cnt - slot0;
-        const int m = left < ROWS_RUN ? (int)left : ROWS_RUN;      // rays of this run (uniform)
-        int32_t my_ray = 0;
-        if (lane < m) my_ray = ray_list ? ray_list[slot0 + lane] : (int32_t)(slot0 + lane);
-        unsigned long long bal[ROWS_RUN][NC];
-        int listed = 0;
-#pragma unroll
-        for (int r = 0; r < ROWS_RUN; ++r) {
-            const int64_t ray = __builtin_amdgcn_readlane(my_ray, r);
-            const float* p = xyz + ray * xyz_ray_stride;
-            float4* o = reinterpret_cast<float4*>(raw + ray * raw_ray_stride);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int k = 64 * c + lane;
-                const bool live = r < m && k < ns;
-                bool occ = false;
-                if (live) {
-                    occ = point_occupied(g, p[3 * k], p[3 * k + 1], p[3 * k + 2]);
-                    if (!occ) o[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                bal[r][c] = __ballot(occ);
-                listed += __popcll(bal[r][c]);
-            }
-        }
-        tested += (unsigned long long)m * (unsigned long long)ns;
-        skipped += (unsigned long long)m * (unsigned long long)ns - (unsigned long long)listed;
-        int base = 0;
-        if (lane == 0 && listed) base = atomicAdd(row_count, listed);
-        int64_t at = __builtin_amdgcn_readfirstlane(base);
-#pragma unroll
-        for (int r = 0; r < ROWS_RUN; ++r) {
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(my_ray, r) << 8;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const unsigned long long b = bal[r][c];
-                const int64_t pos = at + __popcll(b & below);
-                if ((b >> lane & 1ull) && pos < capacity) row_list[pos] = (int32_t)(hi | (uint32_t)(64 * c + lane));
-                at += __popcll(b);
-            }
-        }
-    }
-    if (lane == 0 && counts && tested) {
-        atomicAdd(counts, tested);
-        if (skipped) atomicAdd(counts + 1, skipped);
-    }
 }
 
 // dense: !(sigma <= threshold) in either array (a NaN is dense)
@@ -154,22 +85,41 @@ bool res_ok(const int32_t* res) {
 }  // namespace
 
 namespace stnerf {
-int check_occupancy_table(const stnerf_occupancy* table, int l, const char* what) {
-    STNERF_REQUIRE(table, "%s: null occupancy table", what);
-    STNERF_REQUIRE(!table[0].bits, "%s: layer 0 cannot carry an occupancy grid (the background runs on every ray whatever its mask)", what);
-    for (int i = 1; i < l; ++i) {
-        const stnerf_occupancy& g = table[i];
-        if (!g.bits) continue;
-        STNERF_REQUIRE(res_ok(g.res), "%s: occupancy grid of layer %d has res (%d, %d, %d), each must be 1..256", what, i, g.res[0], g.res[1],
-                       g.res[2]);
-        STNERF_REQUIRE(((uintptr_t)g.bits & 3) == 0, "%s: occupancy bits of layer %d must be 4-byte aligned", what, i);
-        for (int a = 0; a < 3; ++a) {
-            STNERF_REQUIRE(isfinite(g.inv_cell[a]) && g.inv_cell[a] > 0.f, "%s: occupancy grid of layer %d: inv_cell[%d] = %g is not finite and positive",
-                           what, i, a, (double)g.inv_cell[a]);
-            STNERF_REQUIRE(isfinite(g.lo[a]), "%s: occupancy grid of layer %d: lo[%d] is not finite", what, i, a);
-        }
+// The checks of one entry with bits, shared by every caller.  layer names the grid in the messages; 0 is the background's.
+static int check_grid(const stnerf_occupancy& g, int layer, const char* what) {
+    char grid[48] = "the background's grid", bits[48] = "the background grid's bits";
+    if (layer) {
+        snprintf(grid, sizeof(grid), "occupancy grid of layer %d", layer);
+        snprintf(bits, sizeof(bits), "occupancy bits of layer %d", layer);
+    }
+    STNERF_REQUIRE(res_ok(g.res), "%s: %s has res (%d, %d, %d), each must be 1..256", what, grid, g.res[0], g.res[1], g.res[2]);
+    STNERF_REQUIRE(((uintptr_t)g.bits & 3) == 0, "%s: %s must be 4-byte aligned", what, bits);
+    for (int a = 0; a < 3; ++a) {
+        STNERF_REQUIRE(isfinite(g.inv_cell[a]) && g.inv_cell[a] > 0.f, "%s: %s: inv_cell[%d] = %g is not finite and positive", what, grid, a,
+                       (double)g.inv_cell[a]);
+        STNERF_REQUIRE(isfinite(g.lo[a]), "%s: %s: lo[%d] is not finite", what, grid, a);
     }
     return STNERF_OK;
+}
+
+int check_occupancy_entry(const stnerf_occupancy* g, int layer, const char* what) {
+    STNERF_REQUIRE(layer != 0, "%s: layer 0 cannot carry an occupancy grid (the background runs on every ray whatever its mask)", what);
+    return check_grid(*g, layer, what);
+}
+
+int check_occupancy_table(const stnerf_occupancy* table, int l, const char* what) {
+    STNERF_REQUIRE(table, "%s: null occupancy table", what);
+    for (int i = 0; i < l; ++i) {
+        if (!table[i].bits) continue;
+        const int rc = check_occupancy_entry(&table[i], i, what);
+        if (rc) return rc;
+    }
+    return STNERF_OK;
+}
+
+int check_background_grid(const stnerf_occupancy* g, const char* what) {
+    STNERF_REQUIRE(g && g->bits, "%s: the background's grid has no bits", what);
+    return check_grid(*g, 0, what);
 }
 }  // namespace stnerf
 
@@ -202,7 +152,7 @@ extern "C" int stnerf_occupancy_cull(const float* xyz, int64_t n, int l, int n1,
     for (int i = 1; i < l; ++i) {
         const stnerf_occupancy& t = table_host[i];
         if (!t.bits) continue;
-        OccGrid g{t.bits, t.res[0], t.res[1], t.res[2], {t.lo[0], t.lo[1], t.lo[2]}, {t.inv_cell[0], t.inv_cell[1], t.inv_cell[2]}};
+        const OccGrid g = make_occ_grid(t);
         set_launch_tag(i);
         {
             LaunchTimer timer(PROF_OCCUPANCY_CULL, 0, n, n1, 12 * (int64_t)n1 + 2, st);
@@ -212,58 +162,5 @@ extern "C" int stnerf_occupancy_cull(const float* xyz, int64_t n, int l, int n1,
         set_launch_tag(-1);
         STNERF_CHECK_LAUNCH("occupancy_cull");
     }
-    return STNERF_OK;
-}
-
-// One layer's row list: see include/stnerf.h.  xyz / raw are the LAYER's slices (as in stnerf_stage_layer); `layer` names it for the
-// layer-0 refusal, the profiler's tag and the counters' row.
-extern "C" int stnerf_occupancy_rows(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz,
-                                     int64_t xyz_ray_stride, int ns, const stnerf_occupancy* grid_host, float* raw, int64_t raw_ray_stride,
-                                     int32_t* row_list, int64_t capacity, int32_t* row_count, int64_t* counts_or_null, stnerf_stream_t stream) {
-    STNERF_REQUIRE(xyz && raw && row_list && row_count && grid_host, "occupancy_rows: null pointer");
-    STNERF_REQUIRE(layer >= 1 && layer < STNERF_MAX_LAYERS,
-                   "occupancy_rows: layer %d: layer 0 cannot carry an occupancy grid (the background is never listed), layers end at %d", layer,
-                   STNERF_MAX_LAYERS - 1);
-    STNERF_REQUIRE(ns >= 1 && ns <= 256, "occupancy_rows: ns = %d, a row packs the sample into 8 bits: 1..256", ns);
-    STNERF_REQUIRE(n >= 0 && n <= ((int64_t)1 << 23), "occupancy_rows: n = %lld, a row packs the ray into 23 bits: at most 2^23", (long long)n);
-    STNERF_REQUIRE(capacity >= n * ns, "occupancy_rows: capacity %lld below n x ns = %lld", (long long)capacity, (long long)(n * ns));
-    STNERF_REQUIRE((raw_ray_stride & 3) == 0 && ((uintptr_t)raw & 15) == 0, "occupancy_rows: raw must be 16-byte aligned, its ray stride a multiple of 4 floats");
-    STNERF_REQUIRE(((uintptr_t)counts_or_null & 7) == 0, "occupancy_rows: counts must be 8-byte aligned");
-    STNERF_REQUIRE(grid_host->bits, "occupancy_rows: layer %d has no grid", layer);
-    {
-        stnerf_occupancy table[STNERF_MAX_LAYERS];
-        memset(table, 0, sizeof(table));
-        table[layer] = *grid_host;
-        const int rc = check_occupancy_table(table, layer + 1, "occupancy_rows");
-        if (rc) return rc;
-    }
-    hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(row_count, 0, sizeof(int32_t), st) != hipSuccess) {
-        set_error("occupancy_rows: hipMemsetAsync failed");
-        return STNERF_ELAUNCH;
-    }
-    if (n == 0) return STNERF_OK;
-    const stnerf_occupancy& t = *grid_host;
-    OccGrid g{t.bits, t.res[0], t.res[1], t.res[2], {t.lo[0], t.lo[1], t.lo[2]}, {t.inv_cell[0], t.inv_cell[1], t.inv_cell[2]}};
-    const int64_t runs = (n + ROWS_RUN - 1) / ROWS_RUN;
-    const dim3 grid((unsigned)std::min<int64_t>((runs + 3) / 4, CULL_MAX_BLOCKS));
-    unsigned long long* counts = counts_or_null ? reinterpret_cast<unsigned long long*>(counts_or_null) + 2 * layer : nullptr;
-    set_launch_tag(layer);
-    {
-        // per ray: the points read, a zero or a row word per sample (at most 16 bytes)
-        LaunchTimer timer(PROF_OCCUPANCY_ROWS, 0, n, ns, 28 * (int64_t)ns + 4, st);
-#define STNERF_ROWS_LAUNCH(NC)                                                                                                                  \
-    hipLaunchKernelGGL(occupancy_rows_kernel<NC>, grid, dim3(256), 0, st, ray_list, ray_count, n, xyz, xyz_ray_stride, ns, g, raw, raw_ray_stride, \
-                       row_list, capacity, row_count, counts)
-        if (ns <= 64)
-            STNERF_ROWS_LAUNCH(1);
-        else if (ns <= 128)
-            STNERF_ROWS_LAUNCH(2);
-        else
-            STNERF_ROWS_LAUNCH(4);
-#undef STNERF_ROWS_LAUNCH
-    }
-    set_launch_tag(-1);
-    STNERF_CHECK_LAUNCH("occupancy_rows");
     return STNERF_OK;
 }

@@ -1,5 +1,5 @@
 // The point -> cell rule of the occupancy grids (include/stnerf.h: stnerf_occupancy), stated once for the kernels of
-// csrc/occupancy.hip and csrc/termination.hip.  Both files are compiled with -ffp-contract=off: the map is a subtraction and a
+// csrc/occupancy.hip and csrc/sample_rows.hip.  Both files are compiled with -ffp-contract=off: the map is a subtraction and a
 // product, two separate fp32 operations.
 #pragma once
 #include <math.h>

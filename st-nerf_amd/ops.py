@@ -838,6 +838,37 @@ def occupancy_cull(xyz: Tensor, mask: Tensor, table, counts: Optional[Tensor] = 
     return mask
 
 
+def _rows_args(what: str, raw: Tensor, xyz: Optional[Tensor], t: Optional[Tensor], t_stop: Optional[Tensor], row_list: Optional[Tensor],
+               row_count: Optional[Tensor], counts: Optional[Tensor], layer: Optional[int] = None) -> dict:
+    """What the four rows calls share: the shape checks of the layer's slices xyz (n,ns,3), raw (n,ns,4), t (n,ns), of t_stop (n,)
+    and of counts -- (2,), or with ``layer`` (> layer, 2) --, the pointer and ray stride of each strided view (an absent xyz or t
+    is a null pointer), and the default ``row_list`` (n x ns words) and ``row_count``.  -> the C arguments by name: "xyz" / "t" /
+    "raw" = (pointer, ray stride), "rows" = (row_list, capacity, row_count, counts), and "out" = (row_list, row_count)."""
+    if xyz is not None and (xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4)):
+        raise ValueError(f"{what}: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
+    n, ns = raw.shape[0], raw.shape[1]
+    if t is not None and tuple(t.shape) != (n, ns):
+        raise ValueError(f"{what}: t must be ({n},{ns}), got {tuple(t.shape)}")
+    if t_stop is not None and tuple(t_stop.shape) != (n,):
+        raise ValueError(f"{what}: t_stop must be ({n},), got {tuple(t_stop.shape)}")
+    null = (C.c_void_p(0), 0)
+    a = {"n": n, "ns": ns, "xyz": _strided_view_ptr(xyz, (ns, 3), "xyz") if xyz is not None else null,
+         "raw": _strided_view_ptr(raw, (ns, 4), "raw"), "t": _strided_view_ptr(t, (ns,), "t") if t is not None else null,
+         "t_stop": hip.dptr(t_stop, name="t_stop")}
+    if row_list is None:
+        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=raw.device)
+    if row_count is None:
+        row_count = torch.zeros(1, dtype=torch.int32, device=raw.device)
+    if counts is not None and layer is None and tuple(counts.shape) != (2,):
+        raise ValueError(f"{what}: counts must be int64 (2,), got {tuple(counts.shape)}")
+    if counts is not None and layer is not None and (counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] <= int(layer)):
+        raise ValueError(f"{what}: counts must be int64 (> {int(layer)}, 2), got {tuple(counts.shape)}")
+    a["out"] = (row_list, row_count)
+    a["rows"] = (hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(), hip.dptr(row_count, torch.int32, "row_count"),
+                 hip.dptr(counts, torch.int64, "counts"))
+    return a
+
+
 def occupancy_rows(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None,
                    row_list: Optional[Tensor] = None, row_count: Optional[Tensor] = None, counts: Optional[Tensor] = None):
     """One layer's row list of the sample cull (stnerf_occupancy_rows; include/stnerf.h states the rule).  xyz (n,ns,3) and raw
@@ -846,25 +877,13 @@ def occupancy_rows(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Opt
     the listed rays into ``row_list`` (at least n x ns words; made here when None), their number into ``row_count`` (1,), and four
     zero words into raw at every sample of those rays that is NOT listed.  counts: int64 (>= layer + 1, 2) | None accumulates
     (samples tested, samples skipped) in row ``layer``.  -> (row_list, row_count)."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
-        raise ValueError(f"occupancy_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
-    n, ns = xyz.shape[0], xyz.shape[1]
     if grid is None:
         raise ValueError("occupancy_rows: the layer's grid (bits, res, lo, inv_cell) is required")
-    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
-    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
-    if row_list is None:
-        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
-    if row_count is None:
-        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
-    if counts is not None and (counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] <= int(layer)):
-        raise ValueError(f"occupancy_rows: counts must be int64 (> {int(layer)}, 2), got {tuple(counts.shape)}")
-    entry = _occupancy_table([grid], 1)
+    a = _rows_args("occupancy_rows", raw, xyz, None, None, row_list, row_count, counts, layer)
     lp, cp = _worklist(ray_list, ray_count)
-    hip.check(hip.lib().stnerf_occupancy_rows(lp, cp, n, int(layer), xp, xs, ns, entry, rp, rs, hip.dptr(row_list, torch.int32, "row_list"),
-                                              row_list.numel(), hip.dptr(row_count, torch.int32, "row_count"),
-                                              hip.dptr(counts, torch.int64, "counts"), hip.stream_ptr()), "stnerf_occupancy_rows")
-    return row_list, row_count
+    hip.check(hip.lib().stnerf_occupancy_rows(lp, cp, a["n"], int(layer), *a["xyz"], a["ns"], _occupancy_table([grid], 1), *a["raw"], *a["rows"],
+                                              hip.stream_ptr()), "stnerf_occupancy_rows")
+    return a["out"]
 
 
 def background_rows(xyz: Tensor, raw: Tensor, grid, t: Optional[Tensor] = None, t_stop: Optional[Tensor] = None,
@@ -874,29 +893,12 @@ def background_rows(xyz: Tensor, raw: Tensor, grid, t: Optional[Tensor] = None, 
     mandatory.  EVERY ray 0..n-1 is tested: sample k is listed when its point lies in an occupied cell (or has a NaN coordinate)
     and -- with t (n,ns) and t_stop (n,), ``ray_stop``'s output -- ``not t[ray, k] > t_stop[ray]``; the others get four zero words
     in raw.  counts: int64 (2,) | None accumulates (samples tested, not listed).  -> (row_list, row_count)."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
-        raise ValueError(f"background_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
-    n, ns = xyz.shape[0], xyz.shape[1]
     if grid is None:
         raise ValueError("background_rows: the background's grid (bits, res, lo, inv_cell) is required")
-    if t is not None and tuple(t.shape) != (n, ns):
-        raise ValueError(f"background_rows: t must be ({n},{ns}), got {tuple(t.shape)}")
-    if t_stop is not None and tuple(t_stop.shape) != (n,):
-        raise ValueError(f"background_rows: t_stop must be ({n},), got {tuple(t_stop.shape)}")
-    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
-    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
-    tp, ts = _strided_view_ptr(t, (ns,), "t") if t is not None else (C.c_void_p(0), 0)
-    if row_list is None:
-        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
-    if row_count is None:
-        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
-    if counts is not None and tuple(counts.shape) != (2,):
-        raise ValueError(f"background_rows: counts must be int64 (2,), got {tuple(counts.shape)}")
-    hip.check(hip.lib().stnerf_background_rows(n, xp, xs, ns, _occupancy_table([grid], 1), tp, ts, hip.dptr(t_stop, name="t_stop"), rp, rs,
-                                               hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
-                                               hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+    a = _rows_args("background_rows", raw, xyz, t, t_stop, row_list, row_count, counts)
+    hip.check(hip.lib().stnerf_background_rows(a["n"], *a["xyz"], a["ns"], _occupancy_table([grid], 1), *a["t"], a["t_stop"], *a["raw"], *a["rows"],
                                                hip.stream_ptr()), "stnerf_background_rows")
-    return row_list, row_count
+    return a["out"]
 
 
 def background_ray_rows(xyz: Tensor, raw: Tensor, ray_flags: Tensor, grid=None, t: Optional[Tensor] = None, t_stop: Optional[Tensor] = None,
@@ -907,29 +909,12 @@ def background_ray_rows(xyz: Tensor, raw: Tensor, ray_flags: Tensor, grid=None, 
     has a NaN coordinate) and -- with t (n,ns) and t_stop (n,) -- ``not t[r, k] > t_stop[r]``; the others get four zero words in
     raw.  A ray whose flag is zero lists nothing and loads nothing.  counts: int64 (2,) | None accumulates (samples tested, not
     listed).  -> (row_list, row_count)."""
-    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
-        raise ValueError(f"background_ray_rows: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
-    n, ns = xyz.shape[0], xyz.shape[1]
-    flags = _ray_flags(ray_flags, n, "background_ray_rows")
-    if t is not None and tuple(t.shape) != (n, ns):
-        raise ValueError(f"background_ray_rows: t must be ({n},{ns}), got {tuple(t.shape)}")
-    if t_stop is not None and tuple(t_stop.shape) != (n,):
-        raise ValueError(f"background_ray_rows: t_stop must be ({n},), got {tuple(t_stop.shape)}")
-    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz")
-    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
-    tp, ts = _strided_view_ptr(t, (ns,), "t") if t is not None else (C.c_void_p(0), 0)
-    if row_list is None:
-        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=xyz.device)
-    if row_count is None:
-        row_count = torch.zeros(1, dtype=torch.int32, device=xyz.device)
-    if counts is not None and tuple(counts.shape) != (2,):
-        raise ValueError(f"background_ray_rows: counts must be int64 (2,), got {tuple(counts.shape)}")
+    a = _rows_args("background_ray_rows", raw, xyz, t, t_stop, row_list, row_count, counts)
+    flags = _ray_flags(ray_flags, a["n"], "background_ray_rows")
     entry = None if grid is None else _occupancy_table([grid], 1)
-    hip.check(hip.lib().stnerf_background_ray_rows(n, xp, xs, ns, entry, tp, ts, hip.dptr(t_stop, name="t_stop"), rp, rs,
-                                                   hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
-                                                   hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+    hip.check(hip.lib().stnerf_background_ray_rows(a["n"], *a["xyz"], a["ns"], entry, *a["t"], a["t_stop"], *a["raw"], *a["rows"],
                                                    hip.dptr(flags, torch.uint8, "ray_flags"), hip.stream_ptr()), "stnerf_background_ray_rows")
-    return row_list, row_count
+    return a["out"]
 
 
 def _ray_flags(flags: Tensor, n: int, what: str) -> Tensor:
@@ -967,22 +952,12 @@ def visibility_rows(t: Tensor, t_stop: Tensor, raw: Tensor, xyz: Optional[Tensor
     n, ns = t.shape
     if grid is not None and (xyz is None or tuple(xyz.shape) != (n, ns, 3)):
         raise ValueError(f"visibility_rows: a grid needs the layer's points xyz ({n},{ns},3)")
-    tp, ts = _strided_view_ptr(t, (ns,), "t")
-    rp, rs = _strided_view_ptr(raw, (ns, 4), "raw")
-    xp, xs = _strided_view_ptr(xyz, (ns, 3), "xyz") if grid is not None else (C.c_void_p(0), 0)
-    if row_list is None:
-        row_list = torch.empty(max(n * ns, 1), dtype=torch.int32, device=t.device)
-    if row_count is None:
-        row_count = torch.zeros(1, dtype=torch.int32, device=t.device)
-    if counts is not None and (counts.dim() != 2 or counts.shape[1] != 2 or counts.shape[0] <= int(layer)):
-        raise ValueError(f"visibility_rows: counts must be int64 (> {int(layer)}, 2), got {tuple(counts.shape)}")
+    a = _rows_args("visibility_rows", raw, xyz if grid is not None else None, t, t_stop, row_list, row_count, counts, layer)
     entry = None if grid is None else _occupancy_table([grid], 1)
     lp, cp = _worklist(ray_list, ray_count)
-    hip.check(hip.lib().stnerf_visibility_rows(lp, cp, n, int(layer), xp, xs, tp, ts, hip.dptr(t_stop, name="t_stop"), ns, entry, rp, rs,
-                                               hip.dptr(row_list, torch.int32, "row_list"), row_list.numel(),
-                                               hip.dptr(row_count, torch.int32, "row_count"), hip.dptr(counts, torch.int64, "counts"),
+    hip.check(hip.lib().stnerf_visibility_rows(lp, cp, n, int(layer), *a["xyz"], *a["t"], a["t_stop"], ns, entry, *a["raw"], *a["rows"],
                                                hip.stream_ptr()), "stnerf_visibility_rows")
-    return row_list, row_count
+    return a["out"]
 
 
 def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.RenderParams", workspace: Tensor,

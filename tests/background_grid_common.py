@@ -13,6 +13,7 @@ from oracle import stnerf_oracle as O
 
 import occupancy_common as OC
 import sample_cull_common as SC
+import sample_rows_common as SR
 import scene_edits_common as S
 
 EPS = 5.5e-5      # the project's fp32 / fp64 point spread (tests/termination_common.py, tests/test_sample_cull_cpu.py: "full edits")
@@ -22,12 +23,8 @@ EPS = 5.5e-5      # the project's fp32 / fp64 point spread (tests/termination_co
 def np_background_rows(xyz, grid, t=None, t_stop=None):
     """Layer 0's expected row list of one stage.  xyz (n, ns, 3) fp32, grid = (occupied [Rz][Ry][Rx], lo, inv_cell); t (n, ns) and
     t_stop (n,) or None -> (the sorted words ``ray << 8 | k`` of the listed samples of every ray, listed (n, ns) bool)."""
-    listed = OC.np_points_occupied(np.asarray(xyz, np.float32), *grid)
-    if t_stop is not None:
-        with np.errstate(invalid="ignore"):
-            listed = listed & ~(np.asarray(t) > np.asarray(t_stop)[:, None])      # (a NaN depth is not hidden)
-    r, k = np.nonzero(listed)
-    return np.sort((r.astype(np.int64) << 8) | k.astype(np.int64)), listed
+    occupied = OC.np_points_occupied(np.asarray(xyz, np.float32), *grid)
+    return SR.np_sample_rows(xyz.shape[0], xyz.shape[1], t=t, t_stop=t_stop, occupied=occupied)
 
 
 def bkgd_bounds(case):

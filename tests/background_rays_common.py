@@ -9,6 +9,7 @@ a sample that is not listed gets four zero words; counts += (n ns, samples not l
 import numpy as np
 
 import occupancy_common as OC
+import sample_rows_common as SR
 
 BLOCK_CAP = 2048         # the rows kernels' persistent grid: at most this many workgroups of 4 waves, 16 rays per wave and run
 RUN = 16
@@ -17,16 +18,8 @@ RUN = 16
 def np_background_ray_rows(flags, ns, xyz=None, grid=None, t=None, t_stop=None):
     """flags (n,) uint8; xyz (n, ns, 3) fp32 and grid = (occupied [Rz][Ry][Rx], lo, inv_cell) or None; t (n, ns) and t_stop (n,) or
     None -> (the sorted words ``ray << 8 | k`` of the listed samples, listed (n, ns) bool)."""
-    flags = np.asarray(flags)
-    n = flags.shape[0]
-    listed = np.broadcast_to((flags != 0)[:, None], (n, ns)).copy()
-    if grid is not None:
-        listed &= OC.np_points_occupied(np.asarray(xyz, np.float32), *grid)
-    if t_stop is not None:
-        with np.errstate(invalid="ignore"):
-            listed &= ~(np.asarray(t) > np.asarray(t_stop)[:, None])
-    r, k = np.nonzero(listed)
-    return np.sort((r.astype(np.int64) << 8) | k.astype(np.int64)), listed
+    occupied = None if grid is None else OC.np_points_occupied(np.asarray(xyz, np.float32), *grid)
+    return SR.np_sample_rows(np.asarray(flags).shape[0], ns, flags=flags, t=t, t_stop=t_stop, occupied=occupied)
 
 
 def flag_pattern(name, n, seed=0):

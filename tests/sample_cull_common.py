@@ -9,6 +9,7 @@ import torch
 from oracle import stnerf_oracle as O
 
 import occupancy_common as OC
+import sample_rows_common as SR
 import scene_edits_common as S
 
 
@@ -56,11 +57,10 @@ def np_listed(xyz, grid):
 def np_rows(xyz, rays, grid):
     """One layer's expected row list.  xyz (n, ns, 3); rays: the listed ray indices (any order) -> (the sorted words
     ``ray << 8 | k`` of the listed samples of those rays, listed (n, ns) bool with False on rays not tested)."""
-    listed = np.zeros(xyz.shape[:2], bool)
     rays = np.asarray(rays, np.int64)
-    listed[rays] = np_listed(xyz[rays], grid)
-    r, k = np.nonzero(listed)
-    return np.sort((r.astype(np.int64) << 8) | k.astype(np.int64)), listed
+    occupied = np.zeros(xyz.shape[:2], bool)
+    occupied[rays] = np_listed(xyz[rays], grid)
+    return SR.np_sample_rows(xyz.shape[0], xyz.shape[1], rays=rays, occupied=occupied)
 
 
 def rows_are_contiguous_and_ascending(words):

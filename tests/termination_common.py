@@ -8,6 +8,7 @@ import torch
 
 from oracle import stnerf_oracle as O
 
+import sample_rows_common as SR
 import scene_edits_common as S
 
 EPS = 5.5e-5      # the fp32 / fp64 resampling spread the sample cull measured (tests/test_sample_cull_cpu.py: "full edits")
@@ -73,14 +74,7 @@ def np_hidden(t_f, t_stop):
 def np_visibility_rows(t, t_stop, rays, occupied=None):
     """One layer's expected row list.  t (n, ns); rays: the listed ray indices; occupied (n, ns) bool | None: the grid rule's
     verdict -> (sorted words ray << 8 | k, listed (n, ns) bool with False on rays not tested)."""
-    listed = np.zeros(t.shape, bool)
-    rays = np.asarray(rays, np.int64)
-    keep = ~np_hidden(t[rays], t_stop[rays])
-    if occupied is not None:
-        keep &= occupied[rays]
-    listed[rays] = keep
-    r, k = np.nonzero(listed)
-    return np.sort((r.astype(np.int64) << 8) | k.astype(np.int64)), listed
+    return SR.np_sample_rows(t.shape[0], t.shape[1], rays=rays, t=t, t_stop=t_stop, occupied=occupied)
 
 
 # ---------------------------------------------------------------------------------------- the oracle's expectation

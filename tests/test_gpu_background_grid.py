@@ -1,4 +1,4 @@
-"""The background's occupancy grid on the GPU (csrc/background_rows.hip: background_rows_kernel;
+"""The background's occupancy grid on the GPU (csrc/sample_rows.hip: sample_rows_kernel;
 stnerf_render_rays_background; OccupancyGrids(background=True) / set_background_manual):
   1. the rows kernel against the numpy restatement of the rule, bit for bit, with every byte around it and every EINVAL;
   2. the row-list stage kernels with layer 0 listed at ns = n1 (the coarse shape) against the unlisted launch, both arithmetics;

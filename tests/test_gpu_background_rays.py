@@ -1,5 +1,5 @@
-"""The per-ray background mask on the GPU (include/stnerf.h: "Per-ray background mask"; csrc/background_rays.hip:
-background_ray_rows_kernel; stnerf_render_options.bkgd_rays; ``ReprojectSpec(exclusive=True)``):
+"""The per-ray background mask on the GPU (include/stnerf.h: "Per-ray background mask"; csrc/sample_rows.hip:
+sample_rows_kernel; stnerf_render_options.bkgd_rays; ``ReprojectSpec(exclusive=True)``):
   1. the rows kernel against the numpy restatement (tests/background_rays_common.py), bit for bit, with every zero, every byte
      around the outputs and the counters;
   2. the pipeline: all flags on changes no bit; a mixed mask is, row by row, ``where(flag, the plain call, the call under an

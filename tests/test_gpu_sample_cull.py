@@ -1,4 +1,4 @@
-"""The sample cull on the GPU (csrc/occupancy.hip: occupancy_rows_kernel; the row-list flavours of the stage
+"""The sample cull on the GPU (csrc/sample_rows.hip: sample_rows_kernel; the row-list flavours of the stage
 kernels, csrc/mlp_wave_rows.hip and csrc/mlp_bf16x3_rows.hip; stnerf_render_rays_samples; OccupancyGrids(samples=True)):
   1. the rows kernel against the numpy restatement of the rule, bit for bit, with every byte around it;
   2. the row-list stage kernels against the unlisted launch, bit for bit at the listed samples, nothing written elsewhere;

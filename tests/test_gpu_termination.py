@@ -1,4 +1,4 @@
-"""Early ray termination on the GPU (csrc/termination.hip: ray_stop_kernel, visibility_rows_kernel;
+"""Early ray termination on the GPU (csrc/termination.hip: ray_stop_kernel; csrc/sample_rows.hip: sample_rows_kernel;
 stnerf_render_rays_terminated; model.set_termination):
   1. stnerf_ray_stop against the numpy restatement of the rule, bit for bit, with canaries around t_stop;
   2. stnerf_visibility_rows against the numpy restatement, bit for bit, with every byte around it;

@@ -1,5 +1,5 @@
 """Build-quality gate for the listed copy (csrc/layer_cache.hip: copy_layer_raw_listed_kernel), CPU only, in the manner of
-tests/test_background_grid_kernel_resources.py: hipcc cross-compiles the file to gfx950 assembly with the flags the build gives it,
+tests/test_termination_kernel_resources.py: hipcc cross-compiles the file to gfx950 assembly with the flags the build gives it,
 and the code objects' own metadata is read.
 
 The kernel is a copy: one wave per slot, four slots in flight per wave, launched with __launch_bounds__(256).  It is HBM-bound and

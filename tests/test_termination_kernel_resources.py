@@ -1,13 +1,13 @@
-"""Build-quality gate for the two kernels of early ray termination (csrc/termination.hip: ray_stop_kernel, visibility_rows_kernel),
-CPU only, in the manner of tests/test_sample_cull_kernel_resources.py: hipcc cross-compiles the file to gfx950 assembly with the
-flags the build gives it, and the code objects' own metadata is read.
+"""Build-quality gate for the kernel of early ray termination (csrc/termination.hip: ray_stop_kernel; the rows kernel of
+stnerf_visibility_rows is gated by tests/test_sample_rows_kernel_resources.py), CPU only, in the manner of
+tests/test_sample_cull_kernel_resources.py: hipcc cross-compiles the file to gfx950 assembly with the flags the build gives it, and
+the code objects' own metadata is read.
 
-Both kernels are launched with __launch_bounds__(256): four waves, one per SIMD of a CU.  They are latency-bound walks over HBM
-(the merge's dependent loads; the rows kernel's depth, point and grid-word loads), so they must leave room for at least FOUR
-workgroups per CU -- occupancy >= 4 waves per SIMD, i.e. at most 128 VGPRs -- and use no scratch: every per-layer array of the
-merge (cursors, head depths) and every ballot of the rows kernel is indexed by compile-time constants and lives in registers.
-Measured with hipcc --offload-arch=gfx950 (ROCm 7.2): ray_stop_kernel<4 | 8 | 16>: 34 / 58 / 106 VGPRs, occupancy 8 / 8 / 4;
-visibility_rows_kernel<1 | 2 | 4, grid | no grid>: 33 .. 41 VGPRs, occupancy 7 or 8 (the ballots of a run sit in scalar registers)."""
+The kernel is launched with __launch_bounds__(256): four waves, one per SIMD of a CU.  It is a latency-bound walk over HBM (the
+merge's dependent loads), so it must leave room for at least FOUR workgroups per CU -- occupancy >= 4 waves per SIMD, i.e. at most
+128 VGPRs -- and use no scratch: every per-layer array of the merge (cursors, head depths) is indexed by compile-time constants and
+lives in registers.
+Measured with hipcc --offload-arch=gfx950 (ROCm 7.2): ray_stop_kernel<4 | 8 | 16>: 34 / 58 / 106 VGPRs, occupancy 8 / 8 / 4."""
 import os
 import re
 import shutil
@@ -42,9 +42,7 @@ def test_the_termination_kernels_use_no_scratch_and_fit_four_workgroups_per_cu(t
            "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "termination.hip")]
     assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
     kernels = _kernels(open(asm).read())
-    stop = {k: v for k, v in kernels.items() if "ray_stop_kernel" in k}
-    rows = {k: v for k, v in kernels.items() if "visibility_rows_kernel" in k}
-    assert len(stop) == 3 and len(rows) == 6 and len(kernels) == 9, sorted(kernels)       # LCAP 4 / 8 / 16; NC 1 / 2 / 4 x grid or none
+    assert len(kernels) == 3 and all("ray_stop_kernel" in k for k in kernels), sorted(kernels)       # LCAP 4 / 8 / 16
     for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0 and lds == 0, (name, scratch, lds)
