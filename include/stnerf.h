@@ -50,7 +50,8 @@ int stnerf_device_info(int* cu_count, int* lds_bytes_per_cu, int* clock_khz, cha
  * HIP event pair recorded on the launch stream.  _end synchronises those events only and returns one record per
  * launch, in launch order (n_records = number of launches, even if larger than max_records).
  * kernel: 0 spacenet, 1 motionnet, 2 composite, 3 resample, 4 sample_coarse, 5 mlp_stage, 6 copy_layer_raw, 7 occupancy_cull,
- * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop | 2 the per-ray flavour), 13 copy_layer_raw_listed;
+ * 8 occupancy_build, 9 occupancy_rows, 10 ray_stop, 11 visibility_rows, 12 background_rows (kind: 1 with t_stop | 2 the per-ray flavour), 13 copy_layer_raw_listed,
+ * 20 proposal_density (tag: the layer);
  * kind: the net kind for 0/1, to_dense for 6 and 13, dilate for 8, for 5 the bits deep_rgb | 2 bf16x3 |
  * 4 the row-list flavour (stnerf_mlp_stage_rows with at least one listed layer);
  * n_rays x ns = the launch's upper bound on rows (masked launches process ray_count x ns of them);
@@ -1333,6 +1334,65 @@ int stnerf_lattice_select(const uint8_t* status, int64_t n_pixels, int32_t* pixe
                           int64_t workspace_bytes, stnerf_stream_t stream);
 int stnerf_lattice_scatter(const float* rows, int64_t n, int C, int64_t row_stride, const int32_t* pixels, int64_t n_pixels,
                            float* values, uint8_t* status, stnerf_stream_t stream);
+
+/* ---- Grid proposals (csrc/proposal.hip): a layer's COARSE densities from a grid of vertex densities, no coarse
+ * network.  Opt-in, approximate, inference only, not in the reference.  The only thing the final frame takes from the coarse pass is
+ * the weights the resampler turns into n2 new depths; a flagged layer's coarse raw slice is a trilinear lookup in its grid, and
+ * everything downstream -- the coarse composite, stnerf_ray_stop, the resampler, the fine stage -- is fed with those densities.
+ *   Grid.  res = (Rx, Ry, Rz) cells spanning the bounds lo, hi of the layer's UNEDITED box at the layer's frame id, as
+ *   stnerf_occupancy states them (inv_a = (float)R_a / (hi_a - lo_a), computed once on the host in fp32).  sigma[Rz+1][Ry+1][Rx+1]
+ *   fp32: the density at the vertices, vertex (x, y, z) at (z (Ry + 1) + y) (Rx + 1) + x.
+ *   Lookup of point p -- the point the networks would be given: after the ray's rotation and the scale / shift un-edit, before the
+ *   MotionNet.  Every line is one fp32 operation (no fused multiply-add).  Per axis a:
+ *     d  = p_a - lo_a
+ *     g  = d * inv_a
+ *     gc = fminf(fmaxf(g, 0), (float)R_a)
+ *     i  = (int)fminf(floorf(gc), (float)(R_a - 1))
+ *     f  = gc - (float)i
+ *     u  = 1 - f
+ *   then along x, along y, along z, each lerp as (v0 * u) + (v1 * f): two products and a sum,
+ *     c_jk  = (s[z+k][y+j][x] * ux) + (s[z+k][y+j][x+1] * fx)        j, k = 0, 1
+ *     c_k   = (c_0k * uy) + (c_1k * fy)
+ *     sigma = (c_0 * uz) + (c_1 * fz)
+ *   With finite vertex values this form returns the vertex value itself at f = 0 and at f = 1 (v0 + f (v1 - v0) does not).  A point
+ *   outside the box clamps to its faces (+-inf included); a NaN coordinate makes fmaxf(g, 0) = 0, so it is carried in by hand: the
+ *   sample's sigma is NaN, which is what the network would give it.
+ * stnerf_proposal_density: xyz / raw are the LAYER's slices (as in stnerf_stage_layer) with their ray strides in floats.  The rays are
+ * the first min(n, *ray_count) slots of ray_list; ray_list == NULL: every ray 0 .. n-1 (layer 0's convention in
+ * stnerf_background_rows; ray_count is then not read).  Every sample k < ns of a listed ray gets raw = {0, 0, 0, sigma}, one float4
+ * store; a ray that is not listed keeps its bytes.  `layer` names the launch in the profiler record (kernel 20, tag = layer).
+ * One launch: one wave per listed ray over a persistent grid, lane (k mod 64) takes samples k, k + 64, ..; the grid record travels
+ * by value; eight plain vector loads per sample; no LDS, no scratch.
+ * STNERF_EINVAL before any launch: a null pointer (ray_list with ray_count, or neither); sigma not 4-byte, raw not 16-byte aligned or
+ * its stride no multiple of 4 floats; res < 1 or (Rx+1)(Ry+1)(Rz+1) >= 2^31; a non-finite lo or inv_cell; ns outside 1..256; layer
+ * outside 0..STNERF_MAX_LAYERS-1; n < 0. */
+typedef struct stnerf_density_grid {
+    const float* sigma;   /* device, [rz+1][ry+1][rx+1] vertex densities, or NULL = this layer has no proposal */
+    int32_t res[3];       /* rx, ry, rz >= 1, (rx+1)(ry+1)(rz+1) < 2^31 */
+    float lo[3], inv_cell[3];   /* as stnerf_occupancy states them */
+} stnerf_density_grid;
+int stnerf_proposal_density(const int32_t* ray_list, const int32_t* ray_count, int64_t n, int layer, const float* xyz,
+                            int64_t xyz_ray_stride, int ns, const stnerf_density_grid* grid_host, float* raw, int64_t raw_ray_stride,
+                            stnerf_stream_t stream);
+/* The render call with grid proposals: stnerf_render_options_deep followed by the table.  stnerf_render_rays_opts and
+ * stnerf_render_workspace_bytes_opts accept this third record by struct_size exactly as they accept the deep one; the two shorter
+ * records and every named entry stay as they are.  proposal: a host table of params->l entries; NULL, or every sigma NULL, is "no
+ * feature": no new launch, no changed bit, the same workspace (there is no new workspace with the feature either).
+ *   A flagged layer i (proposal[i].sigma != NULL) is in NO coarse network stage, as a layer-cache REUSE layer is in none: no stage
+ *   item, no coarse rows launch, no coarse ray-bias, no stand-alone coarse MotionNet.  Its MotionNet-reuse bit is cleared (there are no
+ *   moved coarse points to reuse): the fine MotionNet runs fused on all n1 + n2 rows.  Right after the coarse stage and the caches'
+ *   copies, one stnerf_proposal_density launch per flagged layer fills its slice of the coarse raw buffer, on the layer's list of hit
+ *   rays (layer 0: every ray).  The fine stage, both composites, termination, the scene passes, the occluder and deep output are
+ *   untouched; the sample cull of a flagged layer acts on its fine stage only.
+ *   Coarse outputs: layer_coarse / mixed_coarse of a flagged layer carry ZERO colour and the grid's depth and alpha.
+ *   STNERF_EINVAL: params->precision == 2 (the per-net schedule does not store activated colours); a flagged layer that is hidden or
+ *   whose layer cache entry is in CAPTURE / REUSE; layer 0 flagged while the background cache is in CAPTURE / REUSE; layer 0 flagged
+ *   together with bkgd_rays or a background grid with bits (the coarse rows launch that stores those zeros is gone: out of scope);
+ *   whatever stnerf_proposal_density refuses of a grid; n1 > 256. */
+typedef struct stnerf_render_options_proposal {
+    stnerf_render_options_deep deep;        /* deep.base.struct_size = sizeof(stnerf_render_options_proposal)                       */
+    const stnerf_density_grid* proposal;    /* host, params->l entries, or NULL                                                     */
+} stnerf_render_options_proposal;
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ SOURCES = [
     ("occupancy.hip", ["-ffp-contract=off"]),
     ("termination.hip", ["-ffp-contract=off"]),
     ("sample_rows.hip", ["-ffp-contract=off"]),
+    ("proposal.hip", ["-ffp-contract=off"]),
     ("accumulate.hip", ["-ffp-contract=off"]),
     ("lens.hip", ["-ffp-contract=off"]),
     ("reproject.hip", ["-ffp-contract=off"]),

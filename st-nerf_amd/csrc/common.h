@@ -20,7 +20,8 @@ int reserve_dynamic_lds(const void* kernel, int bytes, const char* what);
 enum ProfKernel { PROF_SPACENET = 0, PROF_MOTIONNET = 1, PROF_COMPOSITE = 2, PROF_RESAMPLE = 3, PROF_SAMPLE_COARSE = 4, PROF_MLP_STAGE = 5,
                   PROF_COPY_LAYER_RAW = 6, PROF_OCCUPANCY_CULL = 7, PROF_OCCUPANCY_BUILD = 8, PROF_OCCUPANCY_ROWS = 9, PROF_RAY_STOP = 10,
                   PROF_VISIBILITY_ROWS = 11, PROF_BACKGROUND_ROWS = 12, PROF_COPY_LAYER_RAW_LISTED = 13, PROF_SCENE_OCCLUDER = 14,
-                  PROF_OCCLUDER_STOP = 15, PROF_DEEP_COUNT = 16, PROF_DEEP_OFFSETS = 17, PROF_DEEP_FILL = 18, PROF_DEEP_COMPOSITE = 19 };
+                  PROF_OCCLUDER_STOP = 15, PROF_DEEP_COUNT = 16, PROF_DEEP_OFFSETS = 17, PROF_DEEP_FILL = 18, PROF_DEEP_COMPOSITE = 19,
+                  PROF_PROPOSAL_DENSITY = 20 };
 bool profiling_enabled();
 void set_launch_tag(int tag);  // e.g. the layer a pipeline launch works on; -1 = none
 struct LaunchTimer {            // RAII: records start on construction, stop + bookkeeping on destruction
@@ -36,6 +37,8 @@ int check_occupancy_table(const stnerf_occupancy* table, int l, const char* what
 int check_occupancy_entry(const stnerf_occupancy* grid, int layer, const char* what);
 // The same checks of the background's grid, the one entry the two above refuse; bits are required.
 int check_background_grid(const stnerf_occupancy* grid, const char* what);
+// The host checks of one density grid with sigma (csrc/proposal.hip), named `layer` in the messages.
+int check_density_grid(const stnerf_density_grid* grid, int layer, const char* what);
 
 // One call of the row-list kernel (csrc/sample_rows.hip), as the four rows entries make it after their own refusals.  The tests of
 // "listed" are the pointers that are set: ray_flags, t_stop (with t), grid (with xyz; checked by the entry).

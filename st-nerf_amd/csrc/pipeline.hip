@@ -136,19 +136,32 @@ struct Workspace {
 
 const stnerf_render_options kNoOptions = {(int32_t)sizeof(stnerf_render_options)};
 
-// The record is stnerf_render_options or, with the deep fields behind it, stnerf_render_options_deep: struct_size says which.
+// The record is stnerf_render_options or, with the deep fields behind it, stnerf_render_options_deep or, with the proposal table behind
+// those, stnerf_render_options_proposal: struct_size says which.
 int check_options_size(const stnerf_render_options* opts, const char* what) {
-    STNERF_REQUIRE(!opts || opts->struct_size == (int32_t)sizeof(stnerf_render_options) || opts->struct_size == (int32_t)sizeof(stnerf_render_options_deep),
-                   "%s: stnerf_render_options.struct_size = %d is not a size this library knows (%d, or %d with the deep fields): set it to sizeof", what,
-                   opts ? (int)opts->struct_size : 0, (int)sizeof(stnerf_render_options), (int)sizeof(stnerf_render_options_deep));
+    STNERF_REQUIRE(!opts || opts->struct_size == (int32_t)sizeof(stnerf_render_options) || opts->struct_size == (int32_t)sizeof(stnerf_render_options_deep) ||
+                       opts->struct_size == (int32_t)sizeof(stnerf_render_options_proposal),
+                   "%s: stnerf_render_options.struct_size = %d is not a size this library knows (%d, %d with the deep fields, or %d with the proposal table): set it to sizeof",
+                   what, opts ? (int)opts->struct_size : 0, (int)sizeof(stnerf_render_options), (int)sizeof(stnerf_render_options_deep),
+                   (int)sizeof(stnerf_render_options_proposal));
     return STNERF_OK;
 }
 
 // the deep fields of a record that has them; nullptr: no deep output
 const stnerf_render_options_deep* deep_options(const stnerf_render_options* opts) {
-    if (!opts || opts->struct_size != (int32_t)sizeof(stnerf_render_options_deep)) return nullptr;
+    if (!opts || (opts->struct_size != (int32_t)sizeof(stnerf_render_options_deep) && opts->struct_size != (int32_t)sizeof(stnerf_render_options_proposal)))
+        return nullptr;
     const stnerf_render_options_deep* d = reinterpret_cast<const stnerf_render_options_deep*>(opts);
     return d->deep_samples ? d : nullptr;
+}
+
+// the proposal table of a record that has one with a grid among its first l entries; nullptr: no grid proposal
+const stnerf_density_grid* proposal_options(const stnerf_render_options* opts, int l) {
+    if (!opts || opts->struct_size != (int32_t)sizeof(stnerf_render_options_proposal)) return nullptr;
+    const stnerf_density_grid* t = reinterpret_cast<const stnerf_render_options_proposal*>(opts)->proposal;
+    for (int i = 0; t && i < l && i < STNERF_MAX_LAYERS; ++i)
+        if (t[i].sigma) return t;
+    return nullptr;
 }
 
 // Deep output (include/stnerf.h): count -> offsets -> fill on the final stage's buffers, behind its scene pass.
@@ -335,11 +348,12 @@ struct Call {
     int cache_mode;           // the background cache's
     uint32_t lcap, lreuse;    // bit i: performer i's slices go to / come from its layer cache entry (a hidden layer's entry is ignored)
     uint32_t term;            // bit i: layer i's fine stage is terminated
+    uint32_t prop;            // bit i: layer i's coarse densities come from its density grid (a grid proposal)
     RowPlan rows;
 };
 
 // Every argument check of the render call, on the host and before anything is launched.
-int check_call(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, Call* call) {
+int check_call(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, const stnerf_density_grid* proposal, Call* call) {
     STNERF_REQUIRE(rays && boxes && nets && p && workspace && mask, "render_rays: null pointer");
     if (deep) {
         STNERF_REQUIRE(o.scene_out, "render_rays: deep output needs scene_out (the merged weights exist only with the scene passes)");
@@ -461,6 +475,26 @@ int check_call(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_rende
         if (orc) return orc;
         STNERF_REQUIRE(((uintptr_t)o.counts & 7) == 0, "render_rays: occupancy counts must be 8-byte aligned");
     }
+    call->prop = 0;
+    if (proposal) {
+        STNERF_REQUIRE(p->precision != 2, "render_rays: grid proposals are not built for precision 2 (the per-net schedule does not store activated colours)");
+        STNERF_REQUIRE(n1 <= 256, "render_rays: grid proposals take n1 <= 256 coarse samples");
+        for (int i = 0; i < l; ++i) {
+            if (!proposal[i].sigma) continue;
+            const int prc = check_density_grid(&proposal[i], i, "render_rays");
+            if (prc) return prc;
+            if (i == 0) {
+                STNERF_REQUIRE(cache_mode == STNERF_BKGD_CACHE_OFF,
+                               "render_rays: a grid proposal on layer 0 with the background cache in CAPTURE or REUSE (the cached coarse raw would be the grid's)");
+                STNERF_REQUIRE(!bg_rows, "render_rays: a grid proposal on layer 0 with a background grid or a per-ray background mask (the coarse rows launch that "
+                                         "stores their zeros is gone: out of scope)");
+            } else {
+                STNERF_REQUIRE(p->shown[i], "render_rays: a grid proposal on layer %d, which is hidden", i);
+                STNERF_REQUIRE(!((lcap | lreuse) >> i & 1), "render_rays: a grid proposal on layer %d, whose layer cache entry is in CAPTURE or REUSE", i);
+            }
+            call->prop |= 1u << i;
+        }
+    }
     return STNERF_OK;
 }
 
@@ -505,11 +539,17 @@ int check_call(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_rende
 // occluder: the final stage's scene pass is followed by stnerf_scene_occluder on the same buffers -- t, raw and the merged weights,
 // which lie over that stage's points and stay live until the call returns.  occluder_stops: an opaque row's depth is folded into
 // t_stop right after stnerf_ray_stop, so the flagged layers' row lists leave out the fine samples behind it.
+// proposal: a flagged layer is in no COARSE network stage, as a layer in REUSE is in none: no stage item, no rows launch, no ray-bias,
+// no stand-alone MotionNet (its `reuse` bit is cleared: there are no moved coarse points, the fine MotionNet runs fused on all n1 + n2
+// rows).  Its slice of raw_c is filled by stnerf_proposal_density right after the coarse stage and the caches' copies, on the
+// layer's hit rays (layer 0: every ray) and on the points the coarse stage would have been given.  From the coarse composite on the
+// call is what it is without the option; a sample-culled flagged layer is culled in the fine stage only.
 // An option that is absent (a null table, no flag set, no bits, every mode OFF) adds no launch and changes none.
-int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, const Call& c, const Plan& pl, const Workspace& w, stnerf_stream_t stream) {
+int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_render_options_deep* deep, const stnerf_density_grid* proposal, const Call& c,
+                    const Plan& pl, const Workspace& w, stnerf_stream_t stream) {
     const int l = p->l, n1 = p->n1, n2 = p->n2, S = n1 + n2, rs = p->ray_stride;
     const bool cached = c.cache_mode == STNERF_BKGD_CACHE_REUSE;   // layer 0's network outputs come from the cache
-    const uint32_t lcap = c.lcap, lreuse = c.lreuse, term = c.term;
+    const uint32_t lcap = c.lcap, lreuse = c.lreuse, term = c.term, prop = c.prop;
     const int64_t row_cap = c.rows.row_cap;
     hipStream_t st = as_stream(stream);
     int rc;
@@ -537,7 +577,7 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_
         const char* sw = getenv("STNERF_MOTION_REUSE");
         if (!(sw && sw[0] == '0'))
             for (int i = 1; i < l; ++i)
-                if (p->shown[i] && !w.row_list[i] && !(lreuse >> i & 1) && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
+                if (p->shown[i] && !w.row_list[i] && !((lreuse | prop) >> i & 1) && (!p->has_edits || memcmp(&p->edits_coarse[i], &p->edits_fine[i], sizeof(stnerf_layer_edit)) == 0))
                     reuse |= 1u << i;
     }
     uint32_t* motion_queue = reinterpret_cast<uint32_t*>(w.ray_count + STNERF_MAX_LAYERS + 2);   // [layer][coarse, fine]
@@ -556,6 +596,7 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_
             for (int pass = 0; pass < 2; ++pass) {
                 for (int i = cached ? 1 : 0; i < l; ++i) {
                     if (i > 0 && (!p->shown[i] || (lreuse >> i & 1))) continue;   // (hidden, or from the layer cache)
+                    if (!fine && (prop >> i & 1)) continue;                          // (a grid proposal: in no coarse stage)
                     const bool deform = i == 0 ? p->bkgd_use_deform_time != 0 : p->use_deform_time != 0;
                     if ((pass == 0) != deform) continue;
                     const bool timed = (i > 0 ? 1 : p->bkgd_use_space_time) && p->use_space_time;
@@ -673,6 +714,12 @@ int launch_sequence(RENDER_PARAMS, const stnerf_render_options& o, const stnerf_
     // (raw_f lies over the whole coarse block: the coarse slice is copied here, before the compositor reads raw_c)
     rc = stage_and_cache(w.xyz_c, w.raw_c, n1, false, o.cache ? o.cache->raw_coarse : nullptr);
     if (rc) return rc;
+    for (int i = 0; i < l; ++i) {   // grid proposals: the flagged layers' coarse densities
+        if (!(prop >> i & 1)) continue;
+        rc = stnerf_proposal_density(i == 0 ? nullptr : w.ray_list + (int64_t)i * n, i == 0 ? nullptr : w.ray_count + i, n, i, w.xyz_c + (int64_t)i * n1 * 3,
+                                     (int64_t)l * n1 * 3, n1, proposal + i, w.raw_c + (int64_t)i * n1 * 4, (int64_t)l * n1 * 4, stream);
+        if (rc) return rc;
+    }
 
     // ---- coarse: density edits, per-layer + merged composite (:414-448)
     stnerf_composite_params cp;
@@ -763,13 +810,14 @@ extern "C" int stnerf_render_rays_opts(RENDER_PARAMS, const stnerf_render_option
     if (src) return src;
     const stnerf_render_options& o = opts ? *opts : kNoOptions;
     const stnerf_render_options_deep* deep = deep_options(opts);
+    const stnerf_density_grid* proposal = p ? proposal_options(opts, p->l) : nullptr;
     Call call;
-    const int rc = check_call(RENDER_ARGS, o, deep, &call);
+    const int rc = check_call(RENDER_ARGS, o, deep, proposal, &call);
     if (rc) return rc;
     if (n == 0) return STNERF_OK;
     const Plan pl = make_plan(n, p->l, p->n1, p->n2, p->only_coarse);
     const Workspace w(workspace, workspace_bytes, pl, call.rows, n, p->l);
-    return launch_sequence(RENDER_ARGS, o, deep, call, pl, w, stream);
+    return launch_sequence(RENDER_ARGS, o, deep, proposal, call, pl, w, stream);
 }
 
 // ---- the fixed-argument forms (include/stnerf.h): each names the options up to the one it introduced, in the record's order, and

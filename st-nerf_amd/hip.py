@@ -114,6 +114,24 @@ class RenderOptionsDeep(C.Structure):
         return C.cast(C.pointer(self), C.POINTER(RenderOptions))
 
 
+class DensityGrid(C.Structure):
+    """stnerf_density_grid (include/stnerf.h): one layer's vertex densities (device, (Rz+1, Ry+1, Rx+1) fp32), its cell counts
+    (Rx, Ry, Rz), lo and R / (hi - lo).  sigma NULL: the layer has no proposal."""
+    _fields_ = [("sigma", c_f32p), ("res", C.c_int32 * 3), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
+
+
+class RenderOptionsProposal(C.Structure):
+    """stnerf_render_options_proposal (include/stnerf.h): ``RenderOptionsDeep`` followed by the table of density grids; struct_size
+    says which of the three a record is.  ``RenderOptionsProposal()`` is "no feature" too.  ``ref()`` is what the render entries take."""
+    _fields_ = RenderOptionsDeep._fields_ + [("proposal", C.POINTER(DensityGrid))]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=C.sizeof(RenderOptionsProposal), **fields)
+
+    def ref(self):
+        return C.cast(C.pointer(self), C.POINTER(RenderOptions))
+
+
 DEEP_MAX_ELEMENTS = 8   # STNERF_DEEP_MAX_ELEMENTS
 
 
@@ -254,6 +272,8 @@ _PROTOS = {
     "stnerf_deep_fill": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_i64, C.c_int, C.c_int, C.POINTER(CompositeParams), C.c_float, C.c_float,
                                    C.c_void_p, c_f32p, c_i64, C.c_void_p, C.c_void_p]),
     "stnerf_deep_composite": (C.c_int, [C.c_void_p, c_f32p, c_i64, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "stnerf_proposal_density": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, c_f32p, c_i64, C.c_int, C.POINTER(DensityGrid), c_f32p, c_i64,
+                                          C.c_void_p]),
     "stnerf_generate_rays_list": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,
                                             C.c_float, C.POINTER(C.c_float), C.c_int, c_f32p, C.c_int, C.c_void_p]),
     "stnerf_generate_rays_lens": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, c_i64, C.c_float,

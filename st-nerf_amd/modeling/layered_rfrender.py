@@ -117,6 +117,7 @@ class LayeredRFRender(nn.Module):
         self._layer_cache = None           # stnerf_amd.LayerCache or None (set_layer_cache)
         self._occupancy = None             # stnerf_amd.OccupancyGrids or None (set_occupancy)
         self._termination = None           # stnerf_amd.termination.Termination or None (set_termination)
+        self._proposal = None              # stnerf_amd.ProposalGrids or None (set_proposal)
         self.view_key = None               # (view identity, background frame id) of the rays in flight (stnerf_amd.bkgd_cache.view_key),
                                            # set and restored around a call by whoever generated the rays from a camera
                                            # (stnerf_amd.parallel.render_view / render_view_share); None: rays of unknown origin,
@@ -207,6 +208,8 @@ class LayeredRFRender(nn.Module):
             return "occupancy grids (set_occupancy)"
         if getattr(self, "_termination", None) is not None:
             return "early ray termination (set_termination)"
+        if getattr(self, "_proposal", None) is not None:
+            return "grid proposals (set_proposal)"
         return None
 
     def set_precision(self, precision: str):
@@ -342,6 +345,73 @@ class LayeredRFRender(nn.Module):
         culled background needs ONE background frame id per chunk group."""
         self._occupancy = grids
         return self
+
+    # ---- grid proposals (not in the reference) ------------------------------------------------------------------
+    def set_proposal(self, grids):
+        """Attach a ``stnerf_amd.ProposalGrids`` (None: detach).  While one is attached a flagged layer's COARSE densities are a
+        trilinear lookup in a grid of the layer's own fine densities (include/stnerf.h states the rule): its
+        coarse SpaceNet and MotionNet do not run, and everything downstream -- the coarse composite, termination, the resampler,
+        the fine stage -- is fed with those densities.  The grids are built on first use (``density_grid(..., fine=True)``) or given
+        by the caller (``ProposalGrids.set_manual``).  A flagged layer needs ONE frame id per chunk group.  An approximation: the
+        fine depths are drawn from other weights, so the frame differs from the exact one as a frame of another seed does;
+        ``layer_coarse`` / ``mixed_coarse`` of a flagged layer carry zero colour and the grid's depth and alpha.  Inference only, one
+        rank, the "stage" schedule; not beside a layer cache (performers flagged) or a background cache (the background flagged),
+        and the background is not flagged beside a background grid or a per-ray background mask."""
+        self._proposal = grids
+        return self
+
+    @property
+    def proposal(self):
+        """The attached ``stnerf_amd.ProposalGrids`` or None."""
+        return getattr(self, "_proposal", None)
+
+    def _check_proposal(self, flagged, background_rays):
+        """The refusals of a render with grid proposals on the layers ``flagged``, before anything is launched."""
+        from stnerf_amd import parallel
+        window, self.ray_window = self.ray_window, (0, 0, 0)   # (inside a sharded call the rank's window is set: ask without it)
+        try:
+            sharded = parallel.active_group(self) is not None
+        finally:
+            self.ray_window = window
+        if sharded:
+            raise RuntimeError("grid proposals under shard_views with more than one rank: the cross-rank check does not cover the grids; "
+                               "render on one rank (model.shard_views = False) or set_proposal(None)")
+        if self.mlp_schedule != "stage" and self.bkgd_spacenet.precision != "bf16x3":
+            raise ValueError("grid proposals with mlp_schedule = 'per_net' (one launch per network): that schedule does not store activated "
+                             "colours; use mlp_schedule = 'stage' or set_proposal(None)")
+        if any(i > 0 for i in flagged) and getattr(self, "_layer_cache", None) is not None:
+            raise ValueError("grid proposals on a performer beside a layer cache: a cached layer's coarse slice would be the grid's; "
+                             "set_layer_cache(None) or set_proposal(None)")
+        if 0 in flagged:
+            if getattr(self, "_bkgd_cache", None) is not None:
+                raise ValueError("a grid proposal on the background beside a background cache: the cached coarse slice would be the grid's; "
+                                 "set_background_cache(None) or ProposalGrids(background=False)")
+            occ = getattr(self, "_occupancy", None)
+            if occ is not None and occ.has_background():
+                raise ValueError("a grid proposal on the background beside a background occupancy grid: the coarse rows launch that stores "
+                                 "the grid's zeros is gone (out of scope); drop one of the two")
+            if background_rays is not None:
+                raise ValueError("a grid proposal on the background beside a per-ray background mask: the coarse rows launch that stores "
+                                 "the mask's zeros is gone (out of scope); drop one of the two")
+
+    def _proposal_frame_ids(self, rays, groups, retiming, flagged):
+        """Per chunk group the frame id of every layer (l floats), after checking that each FLAGGED layer's frame-id column is constant
+        within the group (the background's only where its flags make the id an input of its density): the rule of
+        ``_occupancy_frame_ids``.  A grid made at row 0's id applied to rays of another id would propose wrongly and silently."""
+        l = self.total_layers
+        cols = (lambda a, b: rays[a:b, 6:6 + l]) if retiming else (lambda a, b: rays[a:b, 6:7].expand(b - a, l))
+        mm, mixed = self._frame_id_ranges(groups, cols)
+        out = []
+        for k, g in enumerate(groups):
+            for i in flagged:
+                if i == 0 and not self._proposal.background_timed(self):
+                    continue
+                if mixed(mm[k, 0, i], mm[k, 1, i]):
+                    raise ValueError(f"proposal: layer {i} has frame ids {float(mm[k, 0, i])} .. {float(mm[k, 1, i])} among rays {g[0]}..{g[1]} of "
+                                     "one chunk group; a flagged layer needs one frame id per group (its grid is made at that id) -- "
+                                     "render one frame id per chunk group, or detach the grids (set_proposal(None))")
+            out.append([float(x) for x in mm[k, 0]])
+        return out
 
     # ---- early ray termination (not in the reference) ---------------------------------------------------------
     def set_termination(self, tau=1e-4, layers=None, background=True):
@@ -664,7 +734,7 @@ class LayeredRFRender(nn.Module):
 
     def _render_launch(self, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None,
                        scene=False, occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False, background_rays=None,
-                       deep=None):
+                       deep=None, proposal_ids=None):
         """One kernel sequence over `rays` (n <= max_rays_per_launch) = ONE call into the C ABI
         (stnerf_render_rays, csrc/pipeline.hip).  boxes: (l,8,3) shared or (n,l,8,3).  piece: the (start, end) of `rays` in
         the call's ray tensor when the background cache or the layer cache may serve it (a view key is set), else None.  rotations: ``layer_ray_transforms`` of the
@@ -677,7 +747,9 @@ class LayeredRFRender(nn.Module):
         the piece's terminated layers (dropped where the piece terminates nothing: only_coarse, every flagged layer cached).
         background_rays: the piece's entries (n,) of the per-ray background mask; such a call neither captures into nor reuses the
         background cache (the cached raw would hold the zeros of one mask); the layer cache is unaffected.  deep: the ``deep=`` dict of
-        ``ops.render_rays`` (with scene): offsets, samples and total come back last."""
+        ``ops.render_rays`` (with scene): offsets, samples and total come back last.  proposal_ids: the chunk group's frame id per
+        layer, passed only while grid proposals flag a layer: one density grid per flagged layer is looked up or built and the table
+        travels with the call."""
         from stnerf_amd import hip
         n, l, dev = rays.shape[0], self.total_layers, rays.device
         p = self._render_params(rays.shape[1], pivot, retiming, only_coarse, thr, bthr, window)
@@ -708,6 +780,10 @@ class LayeredRFRender(nn.Module):
             kw.update(background_rays=background_rays)
         if deep is not None:
             kw.update(deep=deep)
+        if proposal_ids is not None:
+            prop_table, held = self._proposal.table(self, proposal_ids, dev, retiming)
+            keep.append(held)
+            kw.update(proposal=prop_table)
         table = self._layer_alpha_table()
         if table is not None:
             kw.update(layer_alpha=table)
@@ -1056,6 +1132,9 @@ class LayeredRFRender(nn.Module):
                 raise ValueError(f"early ray termination with alpha = {self.alpha} / layer_alpha = {self.layer_alpha}: the coarse composite "
                                  "ignores both opacities, so its stop depth would be wrong for a layer made transparent in the fine "
                                  "composite; leave them at 1 or set_termination(None)")
+        flagged = self._proposal.flagged_layers(self) if getattr(self, "_proposal", None) is not None else []
+        if flagged:
+            self._check_proposal(flagged, background_rays)
         self._warn_if_eval_with_grad()
         if occluder is not None:
             occluder = occluder.to(rays.device, torch.float32).contiguous()
@@ -1064,6 +1143,7 @@ class LayeredRFRender(nn.Module):
         groups = self._chunk_groups(rays, retiming, ref_chunk)
         occ_ids = self._occupancy_frame_ids(rays, groups, retiming) if culling and self._occupancy.culled_layers(self) else None
         bg_ids = self._background_frame_ids(rays, groups) if bg_culling else None
+        prop_ids = self._proposal_frame_ids(rays, groups, retiming, flagged) if flagged else None
         outs, deep_pieces = [], []
         cap = self.max_rays_per_launch
         if deep is not None:   # the piece's worst-case record buffer stays under the budget
@@ -1105,7 +1185,8 @@ class LayeredRFRender(nn.Module):
                                                     **(dict(occluder=occluder[s:e], occluder_stops=occluder_stops)
                                                        if occluder is not None else {}),
                                                     **(dict(background_rays=background_rays[s:e]) if background_rays is not None else {}),
-                                                    **(dict(deep=deep) if deep is not None else {})))
+                                                    **(dict(deep=deep) if deep is not None else {}),
+                                                    **(dict(proposal_ids=prop_ids[gi]) if prop_ids is not None else {})))
                     if deep is not None:
                         offsets, samples, total = outs[-1][-3:]
                         need = int(total)           # (the one host sync of a deep piece)

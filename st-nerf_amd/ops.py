@@ -362,7 +362,8 @@ def pack_motionnet(state: dict, prefix: str, device="cuda", precision: str = "fp
 
 PROFILE_KERNELS = ("spacenet", "motionnet", "composite", "resample", "sample_coarse", "mlp_stage", "copy_layer_raw", "occupancy_cull",
                    "occupancy_build", "occupancy_rows", "ray_stop", "visibility_rows", "background_rows", "copy_layer_raw_listed",
-                   "scene_occluder", "occluder_stop", "deep_count", "deep_offsets", "deep_fill", "deep_composite")
+                   "scene_occluder", "occluder_stop", "deep_count", "deep_offsets", "deep_fill", "deep_composite",
+                   "proposal_density")
 
 
 def profile_begin() -> None:
@@ -917,6 +918,51 @@ def background_ray_rows(xyz: Tensor, raw: Tensor, ray_flags: Tensor, grid=None, 
     return a["out"]
 
 
+def _density_grid_table(table, l):
+    """-> hip.DensityGrid array of l entries | None.  table: per layer None | (sigma fp32 device tensor (Rz+1, Ry+1, Rx+1), lo (3 floats),
+    inv_cell (3 floats)) -- the numbers as they are (``stnerf_amd.proposal`` computes inv_cell in fp32).  A table without a grid is None."""
+    if table is None:
+        return None
+    if len(table) != l:
+        raise ValueError(f"proposal table must have one entry per layer ({l}), got {len(table)}")
+    if all(e is None for e in table):
+        return None
+    arr = (hip.DensityGrid * l)()
+    for i, e in enumerate(table):
+        if e is None:
+            continue
+        sigma, lo, inv = e
+        if not torch.is_tensor(sigma) or sigma.dim() != 3 or min(sigma.shape) < 2:
+            raise ValueError(f"density grid of layer {i}: sigma must be a (Rz+1, Ry+1, Rx+1) tensor with a cell per axis, got "
+                             f"{tuple(sigma.shape) if torch.is_tensor(sigma) else type(sigma).__name__}")
+        arr[i].sigma = hip.dptr(sigma, name=f"density grid of layer {i}").value
+        for a in range(3):
+            arr[i].res[a], arr[i].lo[a], arr[i].inv_cell[a] = int(sigma.shape[2 - a]) - 1, float(lo[a]), float(inv[a])
+    return arr
+
+
+def proposal_density(xyz: Tensor, raw: Tensor, grid, layer: int = 1, ray_list: Optional[Tensor] = None, ray_count: Optional[Tensor] = None) -> Tensor:
+    """One layer's coarse densities from its density grid (stnerf_proposal_density; include/stnerf.h states the rule).  xyz (n,ns,3)
+    and raw (n,ns,4) are the layer's slices (strided views whose dim 0 is the ray); grid = (sigma (Rz+1, Ry+1, Rx+1), lo, inv_cell);
+    ray_list / ray_count: its work list, or None = every ray.  Every sample of a listed ray gets raw = (0, 0, 0, sigma), the trilinear
+    lookup at its point; the rows of the other rays keep their bytes.  -> raw."""
+    if grid is None:
+        raise ValueError("proposal_density: the layer's grid (sigma, lo, inv_cell) is required")
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or raw.dim() != 3 or tuple(raw.shape) != (xyz.shape[0], xyz.shape[1], 4):
+        raise ValueError(f"proposal_density: xyz must be (n,ns,3) and raw (n,ns,4), got {tuple(xyz.shape)} and {tuple(raw.shape)}")
+    n, ns = raw.shape[0], raw.shape[1]
+    if (ray_list is None) != (ray_count is None):
+        raise ValueError("proposal_density: ray_list and ray_count come together (both None: every ray)")
+    if ray_list is not None and (ray_list.numel() < n or ray_count.numel() < 1):
+        raise ValueError(f"proposal_density: ray_list must hold {n} entries and ray_count one, got {ray_list.numel()} and {ray_count.numel()}")
+    if n == 0:
+        return raw
+    lp, cp = _worklist(ray_list, ray_count)
+    hip.check(hip.lib().stnerf_proposal_density(lp, cp, n, int(layer), *_strided_view_ptr(xyz, (ns, 3), "xyz"), ns, _density_grid_table([grid], 1),
+                                                *_strided_view_ptr(raw, (ns, 4), "raw"), hip.stream_ptr()), "stnerf_proposal_density")
+    return raw
+
+
 def _ray_flags(flags: Tensor, n: int, what: str) -> Tensor:
     """A per-ray mask as the library takes it: (n,) uint8, contiguous, on the device (bool is reinterpreted, not copied)."""
     if not torch.is_tensor(flags) or tuple(flags.shape) != (n,) or flags.dtype not in (torch.uint8, torch.bool):
@@ -966,7 +1012,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                 occupancy_samples=None, sample_counts: Optional[Tensor] = None, terminate=None, tau: float = 1e-4,
                 visibility_counts: Optional[Tensor] = None, background_grid=None, background_counts: Optional[Tensor] = None,
                 layer_caches=None, layer_mismatch: Optional[Tensor] = None, occluder: Optional[Tensor] = None,
-                occluder_stops: bool = False, background_rays: Optional[Tensor] = None, deep: Optional[dict] = None):
+                occluder_stops: bool = False, background_rays: Optional[Tensor] = None, deep: Optional[dict] = None, proposal=None):
     """One call = the whole chunk pipeline (stnerf_render_rays).  Returns mixed_fine (n,5), mixed_coarse (n,5),
     layer_fine (n,l,5), layer_coarse (n,l,5), mask (n,l) uint8 (fine outputs alias the coarse ones if only_coarse).
     ``cache`` = (raw_coarse (n,n1,4), raw_fine (n,n1+n2,4) | None, mode): the background cache of this launch piece
@@ -1006,8 +1052,14 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
     ``deep``: None | dict(w_min=0.0, merge_dz=0.0, capacity=None), deep output of the final stage (stnerf_render_options_deep;
     include/stnerf.h states the rules).  It needs ``scene=True`` and appends offsets (n+1,) int64, samples (capacity,8) and total (1,)
     int64 to the returned tuple; capacity None = the worst case n l S.  Rays whose records would pass the capacity are not written:
-    compare total with the capacity.  The render workspace is the same with or without it."""
+    compare total with the capacity.  The render workspace is the same with or without it.
+    ``proposal``: per layer None | (sigma (Rz+1, Ry+1, Rx+1), lo, inv_cell), the table of grid proposals
+    (stnerf_render_options_proposal; include/stnerf.h states the rules): a layer with an entry is in no coarse network stage, its coarse
+    densities are ``proposal_density``'s.  Its layer_coarse / mixed_coarse carry zero colour and the grid's depth and alpha.  The render
+    workspace is the same with or without it.  The library refuses precision 2, a hidden or cached flagged layer, and layer 0 flagged
+    beside a background cache, grid or per-ray mask."""
     n, l = rays.shape[0], params.l
+    proposal = _density_grid_table(proposal, l)
     if deep is not None:
         if not scene:
             raise ValueError("render_rays: deep output needs scene=True (the merged weights exist only with the scene passes)")
@@ -1034,7 +1086,10 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
         lo_f = torch.empty(n, l, 5, dtype=torch.float32, device=dev)
     # every optional argument, checked once and named once (stnerf_render_options); what is given but inert -- tau without a flag, count
     # tensors without their feature -- travels as it is: the library ignores it
-    opts = (hip.RenderOptions if deep is None else hip.RenderOptionsDeep)(tau=float(tau), occluder_stops=int(bool(occluder_stops)))
+    record = hip.RenderOptionsProposal if proposal is not None else hip.RenderOptions if deep is None else hip.RenderOptionsDeep
+    opts = record(tau=float(tau), occluder_stops=int(bool(occluder_stops)))
+    if proposal is not None:
+        opts.proposal = proposal
     opts.rot = _rotations(rotations, l)
     if cache is not None:
         raw_c, raw_f, mode = cache
@@ -1099,7 +1154,7 @@ def render_rays(rays: Tensor, boxes: Tensor, nets: "hip.Nets", params: "hip.Rend
                                                 hip.dptr(jitter, name="jitter"), hip.dptr(u, name="u"),
                                                 hip.dptr(workspace, torch.uint8, "workspace"), workspace.numel(),
                                                 hip.dptr(mix_f), hip.dptr(mix_c), hip.dptr(lo_f), hip.dptr(lo_c), hip.dptr(mask, torch.uint8),
-                                                C.byref(opts) if deep is None else opts.ref(), hip.stream_ptr()), "stnerf_render_rays")
+                                                C.byref(opts) if record is hip.RenderOptions else opts.ref(), hip.stream_ptr()), "stnerf_render_rays")
     out = (mix_c, mix_c, lo_c, lo_c, mask) if params.only_coarse else (mix_f, mix_c, lo_f, lo_c, mask)
     out = out + (scene_out,) if scene else out
     out = out + occ_out if occ_out is not None else out

@@ -34,7 +34,8 @@ class LayeredNeuralRenderer:
     def __init__(self, cfg, scale=None, shift=None, rotation=None, s_shift=None, s_scale=None, s_alpha=None, *,
                  model=None, gt_poses=None, gt_Ks=None, cache_background=False, s_rotation=None, scene_passes=False,
                  layer_alpha=None, s_layer_alpha=None, occupancy=False, terminate=False, cache_layers=False,
-                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None, lattice=None, deep=None):
+                 occluder=None, occluder_stops=False, accumulate=None, lens=None, reproject=None, lattice=None, deep=None,
+                 proposal=False):
         if model is None or gt_poses is None or gt_Ks is None:
             raise NotImplementedError(
                 "dataset / checkpoint discovery from cfg.OUTPUT_DIR (render/layered_neural_renderer.py:96-121) is "
@@ -75,6 +76,7 @@ class LayeredNeuralRenderer:
         self.cache_layers = cache_layers
         self.occupancy = occupancy
         self.terminate = terminate
+        self.proposal = proposal
         # scene_passes: render_path / render_path_walking also keep every layer's share of the mixed image (its premultiplied
         # colour and alpha with the other layers' occlusion: render_pose's `scene_passes`) in images_scene / alphas_scene and
         # hand the frame's dict to on_frame as the keyword `scene`; not in the reference (keyword-only, off by default)
@@ -273,6 +275,25 @@ class LayeredNeuralRenderer:
         else:
             raise TypeError("occupancy is False, True, \"samples\", \"background\", \"samples+background\" or an OccupancyGrids, "
                             f"got {value!r}")
+
+    @property
+    def proposal(self):
+        """The ``stnerf_amd.ProposalGrids`` attached to the model, or None: while one is attached the flagged layers' coarse densities
+        come from a grid of their own fine densities and their coarse networks do not run (``LayeredRFRender.set_proposal``).
+        Setting True attaches fresh grids with the defaults (every shown performer, 128 cells a side), a ``ProposalGrids`` attaches
+        that one, False / None detaches; not in the reference (keyword-only, off by default)."""
+        return getattr(self.model, "_proposal", None)
+
+    @proposal.setter
+    def proposal(self, value):
+        from stnerf_amd.proposal import ProposalGrids
+        if isinstance(value, ProposalGrids):
+            self.model.set_proposal(value)
+        elif value is None or isinstance(value, bool):
+            if bool(value) != (self.proposal is not None):
+                self.model.set_proposal(ProposalGrids() if value else None)
+        else:
+            raise TypeError(f"proposal is False, True or a ProposalGrids, got {type(value).__name__}")
 
     @property
     def terminate(self):

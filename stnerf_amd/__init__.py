@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "OccupancyGrids":
         from stnerf_amd.occupancy import OccupancyGrids
         return OccupancyGrids
+    if name == "ProposalGrids":
+        from stnerf_amd.proposal import ProposalGrids
+        return ProposalGrids
     if name == "Termination":
         from stnerf_amd.termination import Termination
         return Termination
