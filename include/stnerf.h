@@ -213,8 +213,8 @@ int stnerf_spacenet_fwd_rot(int kind, const void* packed, int64_t n_rays, int ns
 /* The per-ray part of rgb_net.1 (modeling/spacenet.py:80-86,141-151): the layer reads the 256 backbone features of a
  * sample and the encodings of the ray's direction and frame id -- the same 27 (+ 21) numbers for every sample of the ray
  * (:115,118 repeat them).  out[j][0..127] = bias + W[:, 256:] * relu([PE_4(dir_j), PE_10(time_j)]) for the listed rays j
- * (rows of other rays are left untouched); the exact-f32 MLP kernels take row j as the C operand of the layer's first
- * MFMA.  stnerf_spacenet_fwd and stnerf_mlp_stage call this themselves into their `ray_bias` workspaces
+ * (rows of other rays are left untouched); the exact-f32 MLP kernels add row j behind the layer's product
+ * (the split-bf16 ones likewise).  stnerf_spacenet_fwd and stnerf_mlp_stage call this themselves into their `ray_bias` workspaces
  * ([n_rays][128] floats per layer, 16-byte aligned); exported for tests and for callers that want the table. */
 int stnerf_rgb_ray_bias(int kind, const void* packed, int64_t n_rays, const int32_t* ray_list, const int32_t* ray_count,
                         const float* dirs, int64_t dirs_ray_stride, const float* times, int64_t times_ray_stride,
@@ -476,6 +476,9 @@ typedef struct stnerf_dw_problem {
     int32_t n, k;
 } stnerf_dw_problem;
 int64_t stnerf_train_dw_batch_workspace_bytes(const stnerf_dw_problem* problems, int32_t count, int64_t m);
+/* How stnerf_train_dw_batch runs these problems (host arithmetic only, the same plan): bundles_out[0] = 2 x 2 bundles in split bf16,
+ * [1] = 2 x 2 bundles in f32, [2] = shared-input bundles (two 256-output layers whose 64-column tiles read the same columns of one matrix). */
+int stnerf_train_dw_batch_plan(const stnerf_dw_problem* problems, int32_t count, int64_t m, int32_t* bundles_out);
 int stnerf_train_dw_batch(const stnerf_dw_problem* problems, int32_t count, int64_t m, int32_t accumulate, void* workspace,
                           int64_t workspace_bytes, stnerf_stream_t stream);
 /* Positional encoding (utils/dimension_kernel.py:54-73) of x[src][0..dim) into columns [col0, col0 + dim (include_input + 2

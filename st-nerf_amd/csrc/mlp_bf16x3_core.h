@@ -26,7 +26,7 @@
 //     first MFMAs of a unit; one raw s_barrier per slot (= 48 MFMAs) orders "slot landed" and "slot free" at once.
 //   * Bias vectors and head weights: one copy per workgroup in LDS (LDS-DMA at the start of a work item).
 //   * PE, bias, ReLU, heads, outputs: fp32, as in the exact-f32 kernels; rgb_net.1's direction / time columns come per
-//     ray from mlp_raybias.hip (exact f32) as the layer's C operand.
+//     ray from mlp_raybias.hip (exact f32), added behind the layer's K loop.
 //
 // Four kernels are built from this machinery.  mlp_bf16x3.hip: the stage kernel of the render path (mlp_bf16x3_stage_kernel<DEEP,
 // NoTapArgs>); the same kernel with the training tap (<false, StoreTapArgs>: every layer's post-ReLU output and its mask bits written
@@ -838,8 +838,8 @@ __device__ __forceinline__ float4 space_bx(Ctx& cx, const float* net, const bool
     }
 #undef BX_INLINED
     // ---- rgb_net: relu -> Linear(283|304, 128) -> relu -> Linear(128, 3) (:80-86); the 256 backbone columns here, the
-    // bias + direction / time columns = this sample's row of the ray-bias table (mlp_raybias.hip).  The exact-f32 kernels take
-    // that row as the C operand; here it is added BEHIND the K loop: it is an order of magnitude larger than the backbone
+    // bias + direction / time columns = this sample's row of the ray-bias table (mlp_raybias.hip).  It is added BEHIND the K loop
+    // (in the exact-f32 kernels likewise: relu_add_rebias, mlp_wave_core.h): it is an order of magnitude larger than the backbone
     // part, and as the C operand it would put every rounding of the a0 b0 chain at its scale (measured: the colour output at
     // 1.3 x the fp32 CPU chain's error instead of 0.5 x).  Its 16 loads go out in front of the pass's last slot (14 of the 16
     // K steps' activation registers are dead by then).

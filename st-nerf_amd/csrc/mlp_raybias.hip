@@ -3,12 +3,12 @@
 // direction and frame id -- the same 27 (+ 21) numbers for every sample of the ray (:115,118 repeat them).  Their part
 // of the layer,
 //     c[f] = bias[f] + sum_k W[f][256 + k] * relu(enc(dir, time))[k],
-// is therefore evaluated here, once per (layer, hit ray), and the MLP kernels take row c[ray] as the C operand of the
-// layer's first MFMA instead of the bias: 16 % of the layer's multiply-adds (1.3 % of the network's) and the 22 sin/cos
+// is therefore evaluated here, once per (layer, hit ray), and the MLP kernels add row c[ray] behind the layer's
+// backbone product instead of the bias: 16 % of the layer's multiply-adds (1.3 % of the network's) and the 22 sin/cos
 // pairs per SAMPLE of the fused kernels go away.
 // This kernel defines the arithmetic for every exact-f32 MLP kernel (mlp_wave.hip): c starts from
-// the bias and takes the encoded features in index order with one fmaf each; the layer then adds the 256 backbone
-// features in the kernels' usual k order.
+// the bias and takes the encoded features in index order with one fmaf each; the layer sums its 256 backbone features
+// from 0 in the kernels' usual k order and adds c to that sum, one rounding, in front of the ReLU.
 #include "mlp_common.h"
 
 namespace stnerf {

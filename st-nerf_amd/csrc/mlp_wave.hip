@@ -19,7 +19,7 @@
 //   * Weights: the A operand of a K step is 8 x 16 B per lane straight from the packed blob (buffer loads, SGPR
 //     offsets, one step ahead); the four waves of a CU run the same network in step, so each line comes out of L2
 //     once per CU and the other three waves hit the vector L1.
-//   * rgb_net.1's direction / time columns come per RAY from mlp_raybias.hip as the layer's C operand.
+//   * rgb_net.1's direction / time columns come per RAY from mlp_raybias.hip, added behind the layer's product.
 //   * Encodings are staged through a wave-private 11 KiB LDS window (the two lanes of a sample split the frequencies,
 //     then each lane reads its half of the feature quads back) -- ordering inside a wave only, no barrier.
 //   * Heads: a lane holds every second feature quad of its sample; the partial sums are grouped as 4 parts x 4

@@ -111,7 +111,8 @@ __device__ __forceinline__ void load_bias(f32x16 (&acc)[8], __amdgpu_buffer_rsrc
 // the step they were written in (left alone, the machine scheduler sinks each load to just before its first use and
 // exposes the L2 latency), and sched_group_barrier interleaves them ONE per MFMA (issued as a clump they take more issue
 // cycles than one MFMA's shadow and the matrix pipe idles).
-// Summation order of an output feature n: the bias is the C operand of the layer's first MFMA; then K step s = 0, 1, ...
+// Summation order of an output feature n: the bias is the C operand of the layer's first MFMA (rgb_net.1: the chain starts from 0 and
+// its ray-bias row is added behind it, see relu_add_rebias); then K step s = 0, 1, ...
 // (k = 8 s .. 8 s + 7), inside a step kk = 0..3 with lane half h supplying k = 8 s + 4 h + kk -- one v_mfma_f32_32x32x2_f32
 // adds the products of k = 8 s + kk and 8 s + 4 + kk.  stage2.0's PE(pos) segment continues the same chain after its 256
 // backbone inputs.
@@ -177,8 +178,9 @@ __device__ __forceinline__ LaneOfs lane_offsets_paired(uint32_t wlane, uint32_t 
     }
     return o;
 }
-template <int NL, bool BOTH>
+template <int NL, bool BOTH, bool ZERO = false>
 __device__ __forceinline__ void pair_r(f32x16 (&acc)[8], const float4 (&wc)[8], const f32x16& b0, int r0, const f32x16& b1, int r1) {
+    const f32x16 zero = {};     // (ZERO: the C operand of each accumulator's first MFMA is the constant 0 -- no instruction clears them)
 #pragma unroll
     for (int half = 0; half < (BOTH ? 2 : 1); ++half) {
 #pragma unroll
@@ -188,7 +190,7 @@ __device__ __forceinline__ void pair_r(f32x16 (&acc)[8], const float4 (&wc)[8], 
             for (int fb = 0; fb < 4; ++fb) {
                 const float4& w4 = wc[4 * half + fb];
                 const float wv = kk == 0 ? w4.x : kk == 1 ? w4.y : kk == 2 ? w4.z : w4.w;
-                acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, bv, acc[fb], 0, 0, 0);
+                acc[fb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, bv, (ZERO && half == 0 && kk == 0) ? zero : acc[fb], 0, 0, 0);
             }
         }
     }
@@ -203,11 +205,12 @@ __device__ __forceinline__ void pair_r(f32x16 (&acc)[8], const float4 (&wc)[8], 
 }
 // STEPS K steps (an odd count ends on a half pair); pair m reads buffer (m + PAR) & 1; on entry that buffer holds pair 0;
 // the last pair fetches NFB_NEXT blocks at (next_wlane, next_soff) into the other buffer.
-template <int NBLK, int STEPS, int PAR, int NFB_NEXT>
+template <int NBLK, int STEPS, int PAR, int NFB_NEXT, bool ZERO = false>
 __device__ __forceinline__ void segment_p(f32x16 (&acc)[8], const f32x16 (&blk)[NBLK], float4 (&wa)[8], float4 (&wb)[8],
                                           __amdgpu_buffer_rsrc_t rsrc, const LaneOfs& wlp, uint32_t soff, uint32_t wstep,
                                           const NextOfs& next_wlane, uint32_t next_soff) {
     static_assert(STEPS >= 1 && STEPS <= 4 * NBLK, "segment_p: not enough input blocks");
+    static_assert(!ZERO || STEPS > 2, "segment_p: ZERO is written for segments of more than one pair");
     constexpr int PAIRS = (STEPS + 1) / 2;
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -215,7 +218,8 @@ __device__ __forceinline__ void segment_p(f32x16 (&acc)[8], const f32x16 (&blk)[
         float4 (&wc)[8] = ((m + PAR) & 1) ? wb : wa;
         float4 (&wn)[8] = ((m + PAR) & 1) ? wa : wb;
         load_w<8>(wn, rsrc, wlp, soff + (uint32_t)(m + 1) * 2u * wstep);
-        pair_r<8, true>(acc, wc, blk[(2 * m) >> 2], 4 * ((2 * m) & 3), blk[(2 * m + 1) >> 2], 4 * ((2 * m + 1) & 3));
+        if (ZERO && m == 0) pair_r<8, true, true>(acc, wc, blk[0], 0, blk[0], 4);
+        else pair_r<8, true>(acc, wc, blk[(2 * m) >> 2], 4 * ((2 * m) & 3), blk[(2 * m + 1) >> 2], 4 * ((2 * m + 1) & 3));
     }
     {
         constexpr int m = PAIRS - 1;
@@ -270,6 +274,41 @@ __device__ __forceinline__ void relu_rebias(f32x16 (&acc)[8], f32x16 (&in)[8], c
         if (fb < NFB) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) in[fb][i] = relu_bits(acc[fb][i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (the bias goes into the registers just read: no earlier)
+        if (fb < NFB_NEXT) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 b = nb4[fb * 8 + 2 * q];
+                acc[fb][4 * q + 0] = b.x;
+                acc[fb][4 * q + 1] = b.y;
+                acc[fb][4 * q + 2] = b.z;
+                acc[fb][4 * q + 3] = b.w;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The same boundary behind rgb_net.1: in = relu(acc + row), row = this sample's row of the ray-bias table (quad 4 fb + q <-> registers
+// 4 q .. 4 q + 3 of block fb).  The row is ADDED BEHIND the product: as the product's C operand (up to round 6) it was ~10 x the
+// backbone product, and each of the layer's 128 K = 2 steps rounded the running sum at its size -- 8e-7 .. 1.1e-6 of the layer's
+// largest output where the fp32 CPU chain has 1.7e-7 .. 3.5e-7 (tests/test_gpu_train_accuracy.py).
+template <int NFB_NEXT>
+__device__ __forceinline__ void relu_add_rebias(f32x16 (&acc)[8], f32x16 (&in)[8], const float4 (&row)[16], const float* next_bias, int lane) {
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    const float4* nb4 = reinterpret_cast<const float4*>(next_bias) + (lane >> 5);
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 r = row[4 * fb + q];
+            const f32x2_ lo = f32x2_{acc[fb][4 * q + 0], acc[fb][4 * q + 1]} + f32x2_{r.x, r.y};
+            const f32x2_ hi = f32x2_{acc[fb][4 * q + 2], acc[fb][4 * q + 3]} + f32x2_{r.z, r.w};
+            in[fb][4 * q + 0] = relu_bits(lo.x);
+            in[fb][4 * q + 1] = relu_bits(lo.y);
+            in[fb][4 * q + 2] = relu_bits(hi.x);
+            in[fb][4 * q + 3] = relu_bits(hi.y);
         }
         __builtin_amdgcn_sched_barrier(0);  // (the bias goes into the registers just read: no earlier)
         if (fb < NFB_NEXT) {
@@ -415,7 +454,7 @@ __device__ __forceinline__ float4 space_wave(const float* net, const bool use_ti
     const NextOfs nx256{(uint32_t)(h * 256 + c) * 16u, false, 0u}, nx128p{(uint32_t)(h * 128 + c) * 16u, true, WSTEP128};
     const uint32_t blane = (uint32_t)h * 16u;
     // ---- every later bias vector on its way into the wave's LDS window: slots 0..5 = stage1.2 .. stage2.4, 6 / 7 = the
-    // deep_rgb layers (rgb_net.1 has none: its C operand is the ray's row of `raybias`); then stage1.0's bias + first
+    // deep_rgb layers (rgb_net.1 has none: the ray's row of `raybias` is added behind its product); then stage1.0's bias + first
     // weights, all in flight behind the encoding arithmetic
     float* biasw = encw + WV_ENC_FLOATS;
     constexpr int NBS = DEEP ? 8 : 6;
@@ -478,25 +517,10 @@ __device__ __forceinline__ float4 space_wave(const float* net, const bool use_ti
     WV_DBG(6, in, 8);
     tap.template blocks<8>(6, in, 8, lane);
     WP(WP_L_EPI);
-    // ---- rgb_net.1's C operands: this sample's row of the ray-bias table straight into the accumulators.  (Fetching them
-    // inside the preceding ReLU pass, block by block, would cover their latency, but keeps the row pointer live through
-    // the layer loop -- the loop's lane offsets then go to scratch and every phase slows down.)
-    {
-        const float* row = raybias + (int64_t)ray * 128 + 4 * h;
-#pragma unroll
-        for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(row + fb * 32 + 8 * q);
-                acc[fb][4 * q + 0] = v.x;
-                acc[fb][4 * q + 1] = v.y;
-                acc[fb][4 * q + 2] = v.z;
-                acc[fb][4 * q + 3] = v.w;
-            }
-    }
     // ---- sigma = density_net(h) (:139), raw, then rgb_net: relu -> Linear(283|304, 128) -> relu -> Linear(128, 3)
     // (:80-86); h is already >= 0, and only the 256 backbone columns are left of the first layer.  The next item's HBM
-    // loads go out first (`mid`); the sigma chains (weights from the LDS window) cover them and the C-operand fetch above.
+    // loads go out first (`mid`); the sigma chains (weights from the LDS window) cover them.  (The ray-bias row is
+    // fetched between rgb_net.1's two segments, below.)
     const float b_sigma = net[L.b_sigma];
     const uint32_t wr = (uint32_t)L.w_rgb1 * 4u;
     const LaneOfs wl128p = lane_offsets_paired(nx128p.base, WSTEP128);  // (not live through the layer loop)
@@ -504,19 +528,31 @@ __device__ __forceinline__ float4 space_wave(const float* net, const bool use_ti
     float sigma = head_sigma<0>(in, biasw + WV_HEAD_SLOT * 256, b_sigma, lane);
     sigma = head_sigma<1>(in, biasw + WV_HEAD_SLOT * 256, sigma, lane);
     WP(WP_S_MID);
-    segment_p<4, 16, 0, 8>(acc, reinterpret_cast<const f32x16 (&)[4]>(in[0]), wa, wb, rsrc, wl128p, wr, WSTEP128, nx128p,
-                           wr + 16u * WSTEP128);
+    segment_p<4, 16, 0, 8, true>(acc, reinterpret_cast<const f32x16 (&)[4]>(in[0]), wa, wb, rsrc, wl128p, wr, WSTEP128, nx128p,
+                                 wr + 16u * WSTEP128);
+    // ---- rgb_net.1's bias: this sample's row of the ray-bias table, added BEHIND the layer's product (relu_add_rebias).  Fetched
+    // between the layer's two segments: the second one's 1024 MFMA cycles x 8 pairs cover the fetch, and the row is live in registers
+    // for one segment only.  (Fetched in front of the layer it is parked in accumulator registers and read back: +38 v_accvgpr_read.)
+    float4 rb[16];
+    {
+        const float* row = raybias + (int64_t)ray * 128 + 4 * h;
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rb[4 * fb + q] = *reinterpret_cast<const float4*>(row + fb * 32 + 8 * q);
+    }
     const uint32_t w_after = DEEP ? (uint32_t)L.w_deep[0] * 4u : wr;  // (not deep: nothing follows; the fetch is discarded)
     segment_p<4, 16, 0, 8>(acc, reinterpret_cast<const f32x16 (&)[4]>(in[4]), wa, wb, rsrc, wl128p, wr + 16u * WSTEP128, WSTEP128,
                            nx128p, w_after);
     if constexpr (DEEP) {  // deep_rgb (:68-79): two more 128-wide hidden layers
-        relu_rebias<4, 4>(acc, in, biasw + 6 * 256, lane);
+        relu_add_rebias<4>(acc, in, rb, biasw + 6 * 256, lane);
         segment_p<8, 16, 0, 8>(acc, in, wa, wb, rsrc, wl128p, (uint32_t)L.w_deep[0] * 4u, WSTEP128, nx128p, (uint32_t)L.w_deep[1] * 4u);
         relu_rebias<4, 4>(acc, in, biasw + 7 * 256, lane);
         segment_p<8, 16, 0, 8>(acc, in, wa, wb, rsrc, wl128p, (uint32_t)L.w_deep[1] * 4u, WSTEP128, nx128p, (uint32_t)L.w_deep[1] * 4u);
     }
     WP(WP_S_RGB1);
-    relu_rebias<4, 0>(acc, in, biasw, lane);
+    if constexpr (DEEP) relu_rebias<4, 0>(acc, in, biasw, lane);
+    else relu_add_rebias<0>(acc, in, rb, biasw, lane);
     WV_DBG(7, in, 4);
     tap.template blocks<8>(7, in, 4, lane);
     float rgb[3];

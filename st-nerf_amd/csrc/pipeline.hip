@@ -60,7 +60,7 @@ Plan make_plan(int64_t n, int l, int n1, int n2, int only_coarse) {
     p.flags = n;                      // one byte per ray: the compositor's scratch
     // hit-ray counts + the work-queue heads of the two network stages + those of the MotionNet launches (coarse, fine per layer)
     p.count = STNERF_MAX_LAYERS + 2 + 2 * STNERF_MAX_LAYERS;
-    p.raybias = (int64_t)l * n * 128;  // per (layer, ray): the C operands of rgb_net.1 (mlp_raybias.hip), reused by both stages
+    p.raybias = (int64_t)l * n * 128;  // per (layer, ray): rgb_net.1's bias rows (mlp_raybias.hip), reused by both stages
     return p;
 }
 

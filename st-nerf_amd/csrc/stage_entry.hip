@@ -168,7 +168,7 @@ extern "C" int stnerf_spacenet_fwd_rot(int kind, const void* packed, int64_t n_r
     STNERF_REQUIRE((raw_ray_stride & 3) == 0 && ((uintptr_t)raw & 15) == 0, "spacenet_fwd: raw must be 16-byte aligned");
     STNERF_REQUIRE(((uintptr_t)packed & 15) == 0, "spacenet_fwd: packed weights must be 16-byte aligned");
     if (n_rays == 0) return STNERF_OK;
-    // rgb_net.1's direction / time columns once per ray (mlp_raybias.hip) -> the C operands of that layer
+    // rgb_net.1's direction / time columns once per ray (mlp_raybias.hip) -> the rows added behind that layer's product
     if (const int rc = launch_ray_bias(kind, static_cast<const float*>(packed), n_rays, ray_list, ray_count, dirs, dirs_ray_stride,
                                        times, times_ray_stride, ray_bias, as_stream(stream), rotation_host))
         return rc;

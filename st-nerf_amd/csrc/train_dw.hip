@@ -826,6 +826,16 @@ extern "C" int64_t stnerf_train_dw_batch_workspace_bytes(const stnerf_dw_problem
     return 4 * P.floats + 512;
 }
 
+extern "C" int stnerf_train_dw_batch_plan(const stnerf_dw_problem* problems, int32_t count, int64_t m, int32_t* bundles_out) {
+    if (const int rc = dww_check(problems, count, m)) return rc;
+    STNERF_REQUIRE(bundles_out, "train_dw_batch_plan: null pointer");
+    DwwPlan P;
+    dww_plan(problems, count, m, P);
+    bundles_out[0] = bundles_out[1] = bundles_out[2] = 0;
+    for (int b = 0; b < P.k.n_bundles; ++b) ++bundles_out[P.k.bundle[b].n_pieces == 3 ? 2 : P.k.bundle[b].bx ? 0 : 1];
+    return STNERF_OK;
+}
+
 extern "C" int stnerf_train_dw_batch(const stnerf_dw_problem* problems, int32_t count, int64_t m, int32_t accumulate, void* workspace,
                                      int64_t workspace_bytes, stnerf_stream_t stream) {
     if (const int rc = dww_check(problems, count, m)) return rc;

@@ -123,7 +123,15 @@ __global__ __launch_bounds__(WV_THREADS, 1) void train_space_dx_kernel(DxArgs a)
                 }
         }
         mask_boundary<4>(acc, in, bw[7], yrow(7), valid);
-        // ---- d act6 = d y7 W_rgb1[:, :256] + d sigma w_sigma: the density head's rank-1 term is the product's C operand
+        // ---- d act6 = d y7 W_rgb1[:, :256] + d sigma w_sigma.  The density head's rank-1 term is added BEHIND the product: as the
+        // product's C operand (up to round 6) it was ~12 x the product itself, and each of an accumulator's 64 MFMAs (16 K steps of
+        // four K = 2 instructions: 128 deep) rounded the running sum at that size -- 6e-7 of the matrix's largest entry where the
+        // fp32 CPU chain has 8e-8 (tests/test_gpu_train_accuracy.py).  (mask_boundary<4> has just cleared blocks 0 .. 3.)
+#pragma unroll
+        for (int fb = 4; fb < 8; ++fb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[fb][i] = 0.f;
+        segment_r<8, 4, 16, 0, 8>(acc, reinterpret_cast<const f32x16 (&)[4]>(in[0]), wa, wb, rsrc, wl256, a.o_rgb1 * 4u, WSTEP256, nx256, a.o_l[6] * 4u);
         {
             const float4* w4 = reinterpret_cast<const float4*>(heads) + h;
 #pragma unroll
@@ -131,13 +139,12 @@ __global__ __launch_bounds__(WV_THREADS, 1) void train_space_dx_kernel(DxArgs a)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float4 w = w4[2 * (fb * 4 + q)];
-                    acc[fb][4 * q + 0] = g.w * w.x;
-                    acc[fb][4 * q + 1] = g.w * w.y;
-                    acc[fb][4 * q + 2] = g.w * w.z;
-                    acc[fb][4 * q + 3] = g.w * w.w;
+                    acc[fb][4 * q + 0] = fmaf(g.w, w.x, acc[fb][4 * q + 0]);
+                    acc[fb][4 * q + 1] = fmaf(g.w, w.y, acc[fb][4 * q + 1]);
+                    acc[fb][4 * q + 2] = fmaf(g.w, w.z, acc[fb][4 * q + 2]);
+                    acc[fb][4 * q + 3] = fmaf(g.w, w.w, acc[fb][4 * q + 3]);
                 }
         }
-        segment_r<8, 4, 16, 0, 8>(acc, reinterpret_cast<const f32x16 (&)[4]>(in[0]), wa, wb, rsrc, wl256, a.o_rgb1 * 4u, WSTEP256, nx256, a.o_l[6] * 4u);
         mask_boundary<8>(acc, in, bw[6], yrow(6), valid);
         segment_r<8, 8, 32, 0, 8>(acc, in, wa, wb, rsrc, wl256, a.o_l[6] * 4u, WSTEP256, nx256, a.o_l[5] * 4u);     // stage2.4
         mask_boundary<8>(acc, in, bw[5], yrow(5), valid);

@@ -217,6 +217,7 @@ _PROTOS = {
     "stnerf_train_linear_dw": (C.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_i64, C.c_int, C.c_int, c_f32p, c_i64, c_f32p, C.c_int, C.c_void_p,
                                          c_i64, C.c_void_p]),
     "stnerf_train_dw_batch_workspace_bytes": (c_i64, [C.POINTER(DwProblem), C.c_int32, c_i64]),
+    "stnerf_train_dw_batch_plan": (C.c_int, [C.POINTER(DwProblem), C.c_int32, c_i64, C.POINTER(C.c_int32)]),
     "stnerf_train_dw_batch": (C.c_int, [C.POINTER(DwProblem), C.c_int32, c_i64, C.c_int32, C.c_void_p, c_i64, C.c_void_p]),
     "stnerf_train_encode": (C.c_int, [c_f32p, c_i64, C.c_int, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, C.c_int,
                                       C.c_void_p]),

@@ -1627,11 +1627,8 @@ def _dw_workspace(need: int, device) -> Tensor:
 DW_BATCH_MAX = 16
 
 
-def train_dw_batch(layers: Sequence[Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]], accumulate: bool) -> None:
-    """For every (dy (m,n), x (m,k), dw (n,k), db (n,) | None) of `layers` (the same m): dw (+)= dy.T @ x, db (+)= dy.sum(0) --
-    stnerf_train_dw_batch: all weight and bias gradients of a network in one launch and one deterministic reduction."""
-    if not layers:
-        return
+def _dw_problems(layers):
+    """-> (the stnerf_dw_problem array of `layers`, m)"""
     if len(layers) > DW_BATCH_MAX:
         raise ValueError(f"train_dw_batch: {len(layers)} layers, at most {DW_BATCH_MAX}")
     m = layers[0][0].shape[0]
@@ -1645,6 +1642,24 @@ def train_dw_batch(layers: Sequence[Tuple[Tensor, Tensor, Tensor, Optional[Tenso
             raise ValueError(f"train_dw_batch: layer {i}: dy {tuple(dy.shape)}, x {tuple(x.shape)}, dw {tuple(dw.shape)}, m = {m}")
         bp = hip.dptr(db, name=f"db[{i}]")
         arr[i] = hip.DwProblem(dp.value, lddy, xp.value, ldx, wp.value, lddw, bp.value if bp is not None else None, n, k)
+    return arr, m
+
+
+def train_dw_batch_bundles(layers: Sequence[Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]]) -> Tuple[int, int, int]:
+    """How ``train_dw_batch`` would run `layers` (stnerf_train_dw_batch_plan, host arithmetic): the number of (split-bf16 2 x 2,
+    f32 2 x 2, shared-input) LDS bundles of the plan."""
+    arr, m = _dw_problems(layers)
+    out = (C.c_int32 * 3)()
+    hip.check(hip.lib().stnerf_train_dw_batch_plan(arr, len(layers), m, out), "stnerf_train_dw_batch_plan")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def train_dw_batch(layers: Sequence[Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]], accumulate: bool) -> None:
+    """For every (dy (m,n), x (m,k), dw (n,k), db (n,) | None) of `layers` (the same m): dw (+)= dy.T @ x, db (+)= dy.sum(0) --
+    stnerf_train_dw_batch: all weight and bias gradients of a network in one launch and one deterministic reduction."""
+    if not layers:
+        return
+    arr, m = _dw_problems(layers)
     need = int(hip.lib().stnerf_train_dw_batch_workspace_bytes(arr, len(layers), m))
     if need < 0:
         hip.check(need, "stnerf_train_dw_batch_workspace_bytes")

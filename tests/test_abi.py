@@ -191,6 +191,27 @@ def test_render_workspace_query_and_argument_errors(lib):
     assert lib.stnerf_render_rays(null, 4, null, 0, None, None, null, null, null, 0, null, null, null, null, null, null) == hip.EINVAL
 
 
+def test_dw_batch_plan_reports_its_bundles(lib):
+    """stnerf_train_dw_batch_plan (host arithmetic): a 256 x >= 256 layer's 2 x 2 full tiles are a split-bf16 bundle from 64 samples on;
+    two 256-output layers whose 64-column tiles read the same columns of one matrix (x pointers that meet, equal ldx) share one."""
+    import ctypes as C
+    base = 1 << 20                                     # (never dereferenced)
+    def plan(entries, m):
+        arr = (hip.DwProblem * len(entries))()
+        for i, (n, k, x, ldx) in enumerate(entries):
+            arr[i] = hip.DwProblem(base, (n + 3) // 4 * 4, x, ldx, base, k, None, n, k)
+        out = (C.c_int32 * 3)()
+        assert lib.stnerf_train_dw_batch_plan(arr, len(entries), m, out) == 0
+        return tuple(out)
+    X = base + (1 << 16)
+    shared = [(256, 63, X + 256 * 4, 320), (256, 319, X, 320), (256, 256, base, 256)]
+    assert plan(shared, 64) == (2, 0, 1) and plan(shared, 1000) == (2, 0, 1) and plan(shared, 63) == (0, 0, 0)
+    assert plan([(256, 63, base, 64)] + shared[1:], 64) == (2, 0, 0)                  # an x of its own: nothing to share
+    assert plan([(256, 63, X + 256 * 4, 324)] + shared[1:], 64) == (2, 0, 0)          # another row stride
+    assert plan([(128, 84, base, 84), (3, 128, base, 128), (300, 300, base, 300)], 256) == (0, 0, 0)
+    assert lib.stnerf_train_dw_batch_plan((hip.DwProblem * 1)(), 1, 64, (C.c_int32 * 3)()) == hip.EINVAL
+
+
 def test_training_batch_entries_check_their_arguments_on_the_host(lib):
     """stnerf_train_dw_batch_workspace_bytes / stnerf_train_dw_batch / stnerf_pack_transposed: host arithmetic and argument errors
     before any launch (no GPU here): the workspace of a SpaceNet's ten layers, the limits (16 layers, 64 tiles, 16-byte aligned rows),

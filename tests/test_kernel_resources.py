@@ -70,7 +70,7 @@ def test_bf16x3_stage_kernel_resources(tmp_path):
     scratch traffic between the first and the last MFMA of a work
     item -- a reload there waits behind vmcnt(0), i.e. behind the weight ring's DMA queue, inside the K passes.  Tolerated:
     a few loop-invariant values reloaded in front of the first MFMA (the 1 / ns reciprocal of the row lookup ...), ONE
-    reload in front of rgb_net.1's last slot (the ray index of the C-operand row, which waits for memory there anyway) and
+    reload in front of rgb_net.1's last slot (the ray index of the ray-bias row, which waits for memory there anyway) and
     the output address behind the last MFMA.  The LDS-DMA / barrier / MFMA structure is what the design says: 48 MFMAs and
     24 operand reads per ring slot."""
     text = open(_compile("mlp_bf16x3.hip", tmp_path)).read()
