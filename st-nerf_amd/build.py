@@ -1,6 +1,7 @@
 """Build libstnerf_hip.so (in-tree) with hipcc for gfx950.  No GPU needed (cross-compile).
 
     python st-nerf_amd/build.py [--force] [--verbose]
+    python st-nerf_amd/build.py --asm SOURCE OUT [flags...]     gfx950 assembly of one source (e.g. train_dw.hip), as the library compiles it
 """
 import os
 import subprocess
@@ -67,6 +68,18 @@ def _hipcc():
     return "hipcc"
 
 
+def device_asm(source, out, extra=(), path=None, quiet=False, timeout=None):
+    """Write to `out` the gfx950 assembly of `source`, one of SOURCES, compiled as build() compiles it: the one recipe behind the
+    kernel gates (tools/asm_listing.py) and the ISA tools.  `extra`: flags on top; `path`: another file (a gate's probe kernel)
+    compiled with the flags of `source`.  A source the library does not hold is an error, and so is a failed compile."""
+    flags = [f for s, f in SOURCES if s == source]
+    if len(flags) != 1:
+        raise ValueError("%s is not a source of the library (see SOURCES)" % source)
+    cmd = [_hipcc()] + COMMON + flags[0] + list(extra) + ["-S", "--cuda-device-only", path or os.path.join(CSRC, source), "-o", out]
+    subprocess.run(cmd, check=True, timeout=timeout, stderr=subprocess.DEVNULL if quiet else None)
+    return out
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -100,4 +113,9 @@ def build(force=False, verbose=False):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--asm"]:
+        if len(sys.argv) < 4:
+            sys.exit(__doc__)
+        print(device_asm(sys.argv[2], sys.argv[3], extra=sys.argv[4:]))
+        sys.exit(0)
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv or True))

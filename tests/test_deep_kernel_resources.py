@@ -7,45 +7,19 @@ use, ballots for the segment starts; deep_composite_kernel keeps eight sorted ro
 registers.  All must use no scratch and at most 128 VGPRs -- room for four workgroups per CU, the bar of the other helper kernels --
 and no LDS beyond the few words the offset scan's workgroups exchange.  Measured with hipcc --offload-arch=gfx950 (ROCm 7.2): count 19
 VGPRs, fill 83, composite 103, the three scan kernels 6 / 26 / 26 with 16 / 68 / 16 bytes of LDS."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import tools.asm_listing as asm
 
 
-def _kernels(text):
-    """{symbol: (VGPRs, scratch bytes, occupancy, LDS bytes)} of every kernel of an assembly listing."""
-    out = {}
-    for name in re.findall(r"^(_Z\w+):", text, re.M):
-        tail = text[text.index(name + ":"):]
-        if "s_endpgm" not in tail:
-            continue
-        body = tail[:tail.index("s_endpgm")]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", tail).group(1))
-        assert "scratch_" not in body and "s_swappc" not in body, name
-        out[name] = (get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), get("LDSByteSize"))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_the_deep_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    asm = str(tmp_path / "deep.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "deep.hip")]
-    assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    kernels = _kernels(open(asm).read())
+@asm.needs_hipcc
+def test_the_deep_kernels_use_no_scratch_and_at_most_128_vgprs():
+    kernels = asm.kernels(asm.listing("deep.hip"))
     ray = sorted(k for k in kernels if "deep_ray_kernel" in k)
     composite = [k for k in kernels if "deep_composite_kernel" in k]
     scan = [k for k in kernels if "deep_block_sum_kernel" in k or "select_scan_kernel" in k or "deep_offsets_kernel" in k]
     assert len(ray) == 2 and len(composite) == 1 and len(scan) == 3 and len(kernels) == 6, sorted(kernels)
-    for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
+    for name, k in sorted(kernels.items()):
+        asm.assert_no_scratch_no_call(k, name)
+        vgprs, scratch, occupancy, lds = k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["LDSByteSize"]
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0, (name, scratch)
         assert vgprs <= 128 and occupancy >= 4, (name, vgprs, occupancy)

@@ -6,29 +6,26 @@ operand loads of the K loop: -3 % measured).  So the resource usage is asserted 
 """
 import os
 import re
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import tools.asm_listing as asm
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_wave_stage_kernel_uses_no_scratch_and_one_wave_per_simd(tmp_path):
-    src = os.path.join(ROOT, "st-nerf_amd", "csrc", "mlp_wave.hip")
-    asm = tmp_path / "mlp_wave.s"
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(asm), src]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-    text = asm.read_text()
-    kernels = re.findall(r"^(_ZN6stnerf21mlp_wave_stage_kernelILb[01]E\S*):", text, re.M)
+def _named(kernels, pattern):
+    """The symbols of a listing's kernels that match a pattern, in the listing's order."""
+    return [name for name in kernels if re.fullmatch(pattern, name)]
+
+
+@asm.needs_hipcc
+def test_wave_stage_kernel_uses_no_scratch_and_one_wave_per_simd():
+    text = asm.listing("mlp_wave.hip")
+    every = asm.kernels(text)
+    kernels = _named(every, r"_ZN6stnerf21mlp_wave_stage_kernelILb[01]E\S*")
     # the plain and the deep_rgb variant, and (round 5) the training instantiation of the plain one that writes every layer's input out
     assert len(kernels) == 3 and sum("StoreTapArgs" in k for k in kernels) == 1, kernels
-    scratch = [int(v) for v in re.findall(r"; ScratchSize: (\d+)", text)]
-    vgprs = [int(v) for v in re.findall(r"; TotalNumVgprs: (\d+)", text)]
-    occupancy = [int(v) for v in re.findall(r"; Occupancy: (\d+)", text)]
+    scratch = [k["ScratchSize"] for k in every.values()]
+    vgprs = [k["TotalNumVgprs"] for k in every.values()]
+    occupancy = [k["Occupancy"] for k in every.values()]
     assert scratch == [0, 0, 0], f"the wave stage kernel spills to scratch: {scratch} bytes"
     assert all(v <= 512 for v in vgprs) and len(vgprs) == 3, vgprs
     assert occupancy == [1, 1, 1], occupancy
@@ -37,22 +34,14 @@ def test_wave_stage_kernel_uses_no_scratch_and_one_wave_per_simd(tmp_path):
     assert "scratch_load" not in text and "scratch_store" not in text
 
 
-def _compile(src_name, tmp_path, extra=()):
-    src = os.path.join(ROOT, "st-nerf_amd", "csrc", src_name)
-    asm = tmp_path / (src_name + ".s")
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function", *extra,
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(asm), src]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-    return str(asm)
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
+@asm.needs_hipcc
 def test_wave_stage_kernel_vector_instruction_ceiling(tmp_path):
     """The exact-f32 kernel's distance from the MFMA pipe's own rate IS its vector-instruction count (every VALU /
     v_accvgpr instruction takes 5 - 6 cycles out of the f32 MFMA stream): a ceiling per region of
     the work-item loop, from tools/isa_vector_count.py's static count (measured: 1027 / 129 / 779 / 265 / 926), so that a
     change of compiler or source that adds vector work shows up here and not as a lost percent on the GPU."""
-    out = subprocess.run(["python3", os.path.join(ROOT, "tools", "isa_vector_count.py"), "--asm", _compile("mlp_wave.hip", tmp_path)],
+    (tmp_path / "mlp_wave.s").write_text(asm.listing("mlp_wave.hip"))
+    out = subprocess.run(["python3", os.path.join(asm.ROOT, "tools", "isa_vector_count.py"), "--asm", str(tmp_path / "mlp_wave.s")],
                          check=True, capture_output=True, text=True, timeout=600).stdout
     got = {m.group(1).strip(): int(m.group(2)) for m in re.finditer(r"^(.+?)\s+vec\s+(\d+)\s", out, re.M)}
     ceilings = {"item head .. MotionNet loop": 1080, "MotionNet layer loop body (x 4)": 136, "MotionNet tail + encoding + stage1.0": 820,
@@ -64,8 +53,8 @@ def test_wave_stage_kernel_vector_instruction_ceiling(tmp_path):
     assert total <= 4500, out
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_bf16x3_stage_kernel_resources(tmp_path):
+@asm.needs_hipcc
+def test_bf16x3_stage_kernel_resources():
     """csrc/mlp_bf16x3.hip (the stage kernel) and csrc/train_bf16x3.hip (the backward chain): one wave per SIMD; (almost) no
     scratch traffic between the first and the last MFMA of a work
     item -- a reload there waits behind vmcnt(0), i.e. behind the weight ring's DMA queue, inside the K passes.  Tolerated:
@@ -73,13 +62,12 @@ def test_bf16x3_stage_kernel_resources(tmp_path):
     reload in front of rgb_net.1's last slot (the ray index of the ray-bias row, which waits for memory there anyway) and
     the output address behind the last MFMA.  The LDS-DMA / barrier / MFMA structure is what the design says: 48 MFMAs and
     24 operand reads per ring slot."""
-    text = open(_compile("mlp_bf16x3.hip", tmp_path)).read()
-    kernels = re.findall(r"^(_ZN6stnerf23mlp_bf16x3_stage_kernelILb[01]E\S*):", text, re.M)
+    stage = asm.kernels(asm.listing("mlp_bf16x3.hip"))
+    kernels = _named(stage, r"_ZN6stnerf23mlp_bf16x3_stage_kernelILb[01]E\S*")
     # the two inference kernels (deep_rgb or not) and the training tap's variant (round 6)
     assert len(kernels) == 3 and sum("StoreTapArgs" in k for k in kernels) == 1, kernels
     for name in kernels:
-        body = text[text.index(name + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = stage[name]["body"]
         lines = body.split("\n")
         loop = next(i for i, l in enumerate(lines) if "This Loop Header: Depth=1" in l)      # the work-item loop
         in_loop = "\n".join(lines[loop:])
@@ -103,41 +91,34 @@ def test_bf16x3_stage_kernel_resources(tmp_path):
             assert in_loop.count("global_store_dwordx4") == 9 * 16 + 8 + 1 and "buffer_store" not in in_loop, in_loop.count("global_store_dwordx4")
             assert "s_waitcnt vmcnt(24)" in in_loop      # the slot turns behind a boundary count its 18 stores in
     # ---- the backward chain (train_space_dx_bx_kernel<DPOS>): no scratch, no call, the ring structure, the masks' reads as asm
-    dx_text = open(_compile("train_bf16x3.hip", tmp_path)).read()
-    dx = re.findall(r"^(_ZN6stnerf24train_space_dx_bx_kernelILb[01]E\S*):", dx_text, re.M)
+    chain = asm.kernels(asm.listing("train_bf16x3.hip"))
+    dx = _named(chain, r"_ZN6stnerf24train_space_dx_bx_kernelILb[01]E\S*")
     assert len(dx) == 2, dx
     for name in dx:
-        body = dx_text[dx_text.index(name + ":"):]
-        body = body[:body.index("s_endpgm")]
-        assert "scratch_" not in body and "s_swappc" not in body, name
+        body = chain[name]["body"]
+        asm.assert_no_scratch_no_call(chain[name], name)
         dpos = "ILb1E" in name
         # rgb_net.1 2 x 4, the two loop bodies and stage2.0's layer 16 each; with d pos: two half passes of 4
         slots = 8 + 3 * 16 + (8 if dpos else 0)
         assert body.count("v_mfma_f32_32x32x16_bf16") == 48 * slots, (name, body.count("v_mfma_f32_32x32x16_bf16"))
         # what drains the weight ring's DMA queue: the item's mask fetch (top of the item) and the kernel's end -- not the boundaries
         assert body.count("s_waitcnt vmcnt(0)") <= 3, body.count("s_waitcnt vmcnt(0)")
-    for name, source in [(k, text) for k in kernels] + [(k, dx_text) for k in dx]:
-        tail = source[source.index(name + ":"):]
-        occ = int(re.search(r"; Occupancy: (\d+)", tail).group(1))
-        scr = int(re.search(r"; ScratchSize: (\d+)", tail).group(1))
+    for name, source in [(k, stage) for k in kernels] + [(k, chain) for k in dx]:
+        occ, scr = source[name]["Occupancy"], source[name]["ScratchSize"]
         assert occ == 1 and scr <= (0 if ("StoreTapArgs" in name or "dx_bx" in name) else 128), (name, occ, scr)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_compositor_and_resampler_production_kernels_resources(tmp_path):
+@asm.needs_hipcc
+def test_compositor_and_resampler_production_kernels_resources():
     """csrc/composite.hip, csrc/resample.hip: the compositor's merge kernel and the resampler are bound by vector-instruction issue and by how many
     waves hide their LDS / HBM round trips (DESIGN.md sections 4.2 / 4.3), so the flavours the BASELINE shapes run (S a multiple
     of 64; device draws) must keep their occupancy targets without scratch, use the one-instruction in-place DPP scan steps,
     and the resampler's sort must not go through ds_bpermute except for its single distance-32 stage."""
-    text = open(_compile("composite.hip", tmp_path)).read() + open(_compile("resample.hip", tmp_path)).read()
+    kernels = {**asm.kernels(asm.listing("composite.hip")), **asm.kernels(asm.listing("resample.hip"))}
 
     def kernel(mangled_part):
-        name = next(n for n in re.findall(r"^(_ZN6stnerf\w+):", text, re.M) if mangled_part in n)
-        body = text[text.index(name + ":"):]
-        end = body.index("s_endpgm")
-        meta = body[end:end + 6000]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", meta).group(1))
-        return body[:end], get("NumVgprs"), get("ScratchSize"), get("Occupancy")
+        k = next(k for n, k in kernels.items() if re.fullmatch(r"_ZN6stnerf\w+", n) and mangled_part in n)
+        return k["body"], k["NumVgprs"], k["ScratchSize"], k["Occupancy"]
 
     for part, occupancy in (("composite_merge_kernelILi1ELb1", 7), ("composite_merge_kernelILi2ELb1", 7), ("composite_merge_kernelILi3ELb1", 6),
                             ("resample_kernelILi1ELb1ELb1", 8), ("resample_kernelILi2ELb1ELb1", 7), ("resample_kernelILi2ELb1ELb0", 7)):
@@ -166,8 +147,8 @@ def test_compositor_and_resampler_production_kernels_resources(tmp_path):
                 assert parked <= 80, (part, parked)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_no_valu_exec_write_within_five_wait_states_of_a_dpp_instruction(tmp_path):
+@asm.needs_hipcc
+def test_no_valu_exec_write_within_five_wait_states_of_a_dpp_instruction():
     """csrc/composite.hip and csrc/resample.hip carry hand-written DPP blocks (csrc/wave_prims.h's in-place wave scans, the bitonic stages).  LLVM's hazard
     recognizer does not look inside inline asm: a VALU write of EXEC (v_cmpx*) needs 5 wait states before a DPP
     instruction reads under it, and a block placed directly behind predicated code would get none from the compiler.  The
@@ -178,8 +159,7 @@ def test_no_valu_exec_write_within_five_wait_states_of_a_dpp_instruction(tmp_pat
     n_dpp, offenders = 0, []
     for src in ("composite.hip", "resample.hip"):
         n_dpp_before = n_dpp
-        text = open(_compile(src, tmp_path, extra=("-ffp-contract=off",))).read()
-        lines = [ln.split(";")[0].strip() for ln in text.split("\n")]
+        lines = [ln.split(";")[0].strip() for ln in asm.listing(src).split("\n")]
         lines = [ln for ln in lines if ln and not ln.startswith(".")]
         for i, ln in enumerate(lines):
             op = ln.split()[0]
@@ -202,57 +182,56 @@ def test_no_valu_exec_write_within_five_wait_states_of_a_dpp_instruction(tmp_pat
     assert not offenders, offenders[:5]
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_fused_backward_kernel_resources(tmp_path):
+@asm.needs_hipcc
+def test_fused_backward_kernel_resources():
     """csrc/train_wave.hip (round 5): the dX chain keeps a wave's gradient in registers from the heads to stage1.2 -- one wave per
     SIMD, no scratch, exactly the MFMAs of the chain (16 + 6 x 32 K steps of 32, + the two 2-block products of the PE columns when
     the points need a gradient); the ReLU masks arrive as bit planes (8 loads of 16 bytes per item, one v_bfe_i32 + one v_and per
     value: no activation is read back), every gradient write is a 16-byte vector store."""
-    text = open(_compile("train_wave.hip", tmp_path)).read()
-    kernels = re.findall(r"^(_ZN6stnerf21train_space_dx_kernelILb[01]EEE\S*):", text, re.M)
+    text = asm.listing("train_wave.hip")
+    every = asm.kernels(text)
+    kernels = _named(every, r"_ZN6stnerf21train_space_dx_kernelILb[01]EEE\S*")
     assert len(kernels) == 2, kernels
     # (five kernels in the file: the MotionNet's training forward, the two SpaceNet chains, the two MotionNet chains)
-    assert [int(v) for v in re.findall(r"; ScratchSize: (\d+)", text)] == [0] * 5
-    assert all(int(v) <= 512 for v in re.findall(r"; TotalNumVgprs: (\d+)", text))
+    assert [k["ScratchSize"] for k in every.values()] == [0] * 5
+    assert all(k["TotalNumVgprs"] <= 512 for k in every.values())
     assert "scratch_" not in text
-    motion = re.findall(r"^(_ZN6stnerf22train_motion_dx_kernelILb[01]EEE\S*):", text, re.M)
+    motion = _named(every, r"_ZN6stnerf22train_motion_dx_kernelILb[01]EEE\S*")
     assert len(motion) == 2, motion
     for k in motion:
         # four 128 x 128 products (16 K steps x 16 MFMAs), + the one into the encoding whose fourth block nobody stores; five masks of
         # 8 bytes per lane; 5 x 16 gradient stores (+ 12 for d enc)
-        body = text[text.index(k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = every[k]["body"]
         dx = "Lb1" in k
         assert body.count("v_mfma_f32_32x32x2_f32") == 4 * 256 + (192 if dx else 0), (k, body.count("v_mfma_f32_32x32x2_f32"))
         assert body.count("global_load_dwordx2") == 5 and body.count("global_load_dwordx4") == 0
         assert body.count("global_store_dwordx4") == 5 * 16 + (12 if dx else 0)
         assert body.count("v_bfe_i32") == 5 * 64 and body.count("v_cmp_") < 16
-    fwd = text[text.index("_ZN6stnerf23train_motion_fwd_kernel"):]
-    fwd = fwd[fwd.index(":"):fwd.index("s_endpgm")]
+    fwd = every[_named(every, r"_ZN6stnerf23train_motion_fwd_kernel\S*")[0]]["body"]
     # the tap: 22 quads of the encoding + 16 stores and 2 x 64 (min, shift-or) pairs per layer (rolled layer loop + the last layer)
     assert fwd.count("global_store_dwordx4") >= 11 + 2 * 16 and fwd.count("global_store_dwordx2") == 2 and fwd.count("v_lshl_or_b32") >= 128
     for k in kernels:
-        body = text[text.index(k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = every[k]["body"]
         want = (16 + 6 * 32) * 32 + (2 * 32 * 8 if "Lb1" in k else 0)
         assert body.count("v_mfma_f32_32x32x2_f32") == want, (k, body.count("v_mfma_f32_32x32x2_f32"), want)
         assert body.count("global_load_dwordx4") <= 16 and body.count("global_store_dwordx4") >= 7 * 32 + 16
         assert body.count("v_bfe_i32") == (4 + 7 * 8) * 16 and body.count("v_cmp_") < 16
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_weight_gradient_kernel_loops_are_what_the_design_says(tmp_path):
+@asm.needs_hipcc
+def test_weight_gradient_kernel_loops_are_what_the_design_says():
     """csrc/train_dw.hip (round 6): one wave per SIMD, no scratch, and the three inner loops as DESIGN 4.4 describes them --
     the direct f32 tile: 128 MFMAs + 16 buffer loads per 16 samples and NO vector instruction besides (on gfx950 every VALU instruction
     takes its cycles out of the f32 MFMA stream); the f32 bundle: 128 MFMAs, 16 LDS reads, 8 LDS-DMA instructions, one barrier per block;
     the split-bf16 bundle: 192 bf16 MFMAs per two 16-sample steps beside <= 5 vector instructions per MFMA (the two operands' splits),
     32 LDS reads, 16 LDS-DMA instructions, two barriers."""
     from collections import Counter
-    text = open(_compile("train_dw.hip", tmp_path)).read()
-    assert [int(v) for v in re.findall(r"; ScratchSize: (\d+)", text)] == [0, 0]          # the tile kernel and the reduction
+    text = asm.listing("train_dw.hip")
+    kernels = list(asm.kernels(text).values())
+    assert [k["ScratchSize"] for k in kernels] == [0, 0]          # the tile kernel and the reduction
     assert "scratch_" not in text
-    assert max(int(v) for v in re.findall(r"; TotalNumVgprs: (\d+)", text)) <= 512
-    assert int(re.findall(r"; Occupancy: (\d+)", text)[0]) == 1
+    assert max(k["TotalNumVgprs"] for k in kernels) <= 512
+    assert kernels[0]["Occupancy"] == 1
     lines = text.split("\n")
     labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
     loops = []
@@ -275,22 +254,21 @@ def test_weight_gradient_kernel_loops_are_what_the_design_says(tmp_path):
         assert c.get("v_cvt_pk_bf16_f32") == 192 and valu(c) <= 5 * 192, (valu(c), dict(c))
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_motionnet_forward_instantiations_use_no_scratch_and_make_no_call(tmp_path):
+@asm.needs_hipcc
+def test_motionnet_forward_instantiations_use_no_scratch_and_make_no_call():
     """train_motion_fwd_kernel<Rows> (csrc/mlp_wave_core.h) runs the MotionNet of the stage kernel over the rows of a launch, one wave per
     SIMD (as launched): its training instantiation (csrc/train_wave.hip, the taps) and the op-level one behind stnerf_motionnet_fwd
     (csrc/stage_entry.hip, the work list).  Every instantiation: no scratch, no call, and the MFMAs of the network -- motion_net.0's 11 K
     steps and the rolled body of the four 128 x 128 layers, 16 MFMAs per K step."""
     found = []
     for src, rows in (("train_wave.hip", "MotionFwdArgs"), ("stage_entry.hip", "MotionOpArgs")):
-        text = open(_compile(src, tmp_path)).read()
-        names = re.findall(r"^(_ZN6stnerf23train_motion_fwd_kernelI\S*):", text, re.M)
+        kernels = asm.kernels(asm.listing(src))
+        names = _named(kernels, r"_ZN6stnerf23train_motion_fwd_kernelI\S*")
         assert len(names) == 1 and rows in names[0], (src, names)
         for k in names:
-            tail = text[text.index(k + ":"):]
-            body = tail[:tail.index("s_endpgm")]
-            assert int(re.search(r"; ScratchSize: (\d+)", tail).group(1)) == 0, k
-            assert "scratch_" not in body and "s_swappc" not in body, k
+            body = kernels[k]["body"]
+            assert kernels[k]["ScratchSize"] == 0, k
+            asm.assert_no_scratch_no_call(kernels[k], k)
             assert body.count("v_mfma_f32_32x32x2_f32") == 11 * 16 + 16 * 16, (k, body.count("v_mfma_f32_32x32x2_f32"))
             found.append(k)
     assert len(found) == 2, found

@@ -9,41 +9,19 @@ select_scan_kernel / select_write_kernel.  Every one must use no scratch and at 
 the bar of the other helper kernels; the five lattice kernels use no LDS, the three select kernels a few words of it (the waves'
 popcounts; the scan's 16 wave sums and its carry).  Measured with hipcc --offload-arch=gfx950 (ROCm 7.2): the figures are
 printed."""
-import os
-import re
-import shutil
-import subprocess
+import tools.asm_listing as asm
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNELS = ("lattice_begin_kernel", "lattice_flat_kernel", "lattice_fill_kernel", "lattice_mark_kernel", "lattice_scatter_kernel",
            "select_count_kernel", "select_scan_kernel", "select_write_kernel")
 FLAGS = ["-ffp-contract=off"]
 
 
-def _kernels(text):
-    """{symbol: (VGPRs, scratch bytes, occupancy, LDS bytes)} from the summary that follows every kernel descriptor."""
-    out = {}
-    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M):
-        tail = text[m.end():]
-        get = lambda k: int(re.search(r"^; " + k + r": (\d+)", tail, re.M).group(1))
-        out[m.group(1)] = (get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), get("LDSByteSize"))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_the_lattice_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    asm = str(tmp_path / "lattice.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17"] + FLAGS + ["-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "lattice.hip")]
-    assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    kernels = _kernels(open(asm).read())
+@asm.needs_hipcc
+def test_the_lattice_kernels_use_no_scratch_and_at_most_128_vgprs():
+    kernels = asm.kernels(asm.listing("lattice.hip"))
     assert len(kernels) == len(KERNELS) and all(sum(k in name for name in kernels) == 1 for k in KERNELS), sorted(kernels)
-    for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
+    for name, k in sorted(kernels.items()):
+        vgprs, scratch, occupancy, lds = k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["LDSByteSize"]
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0, (name, scratch)
         assert vgprs <= 128 and occupancy >= 4, (name, vgprs, occupancy)

@@ -5,44 +5,20 @@ the code object's own metadata is read.
 One helper kernel, generate_rays_lens_kernel (one lane per row, HBM-bound on the row it writes).  It must use no scratch, at most
 128 VGPRs with an occupancy of at least 4 -- the bar of the other helper kernels -- and no LDS.  Measured with hipcc
 --offload-arch=gfx950 (ROCm 7.2): the figures are printed."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
+import tools.asm_listing as asm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNELS = ("generate_rays_lens_kernel",)
 
 
-def _kernels(text):
-    """{symbol: (VGPRs, scratch bytes, occupancy, LDS bytes)} of every kernel of an assembly listing."""
-    out = {}
-    for name in re.findall(r"^(_Z\w+):", text, re.M):
-        tail = text[text.index(name + ":"):]
-        if "s_endpgm" not in tail:
-            continue
-        body = tail[:tail.index("s_endpgm")]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", tail).group(1))
-        assert "scratch_" not in body and "s_swappc" not in body, name
-        out[name] = (get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), get("LDSByteSize"))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_the_lens_kernel_uses_no_scratch_no_lds_and_at_most_128_vgprs(tmp_path):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    asm = str(tmp_path / "lens.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "lens.hip")]
-    assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    text = open(asm).read()
-    kernels = _kernels(text)
+@asm.needs_hipcc
+def test_the_lens_kernel_uses_no_scratch_no_lds_and_at_most_128_vgprs():
+    kernels = asm.kernels(asm.listing("lens.hip"))
     assert len(kernels) == len(KERNELS) and all(sum(k in name for name in kernels) == 1 for k in KERNELS), sorted(kernels)
-    for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
+    for name, k in sorted(kernels.items()):
+        asm.assert_no_scratch_no_call(k, name)
+        vgprs, scratch, occupancy, lds = k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["LDSByteSize"]
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0, (name, scratch)
         assert vgprs <= 128 and occupancy >= 4, (name, vgprs, occupancy)
@@ -52,25 +28,20 @@ def test_the_lens_kernel_uses_no_scratch_no_lds_and_at_most_128_vgprs(tmp_path):
     # quotient and one of one root are compiled with the same flags, and the kernel must hold exactly the fused operations of its
     # quotients and roots plus the two fmaf it WRITES (the squared norm in torch.norm's order) -- one more would be a contracted
     # product of ours.  Quotients in the listing: xd, yd, the round's two (the loop is not unrolled), focus / cz, the norm's three.
-    probe = tmp_path / "probe.hip"
-    probe.write_text("#include <hip/hip_runtime.h>\n"
-                     "__global__ void probe_div(const float* a, const float* b, float* o) { o[threadIdx.x] = a[threadIdx.x] / b[threadIdx.x]; }\n"
-                     "__global__ void probe_sqrt(const float* a, float* o) { o[threadIdx.x] = sqrtf(a[threadIdx.x]); }\n")
-    probe_asm = str(tmp_path / "probe.s")
-    assert subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", probe_asm,
-                           str(probe)], stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    probe_text = open(probe_asm).read()
+    probes = asm.kernels(asm.listing_of(
+        "#include <hip/hip_runtime.h>\n"
+        "__global__ void probe_div(const float* a, const float* b, float* o) { o[threadIdx.x] = a[threadIdx.x] / b[threadIdx.x]; }\n"
+        "__global__ void probe_sqrt(const float* a, float* o) { o[threadIdx.x] = sqrtf(a[threadIdx.x]); }\n", like="lens.hip"))
 
-    def fused(listing, name):
-        body = listing[listing.index(name + ":"):]
-        body = body[:body.index("s_endpgm")]
+    def fused(kernel):
+        body = kernel["body"]
         return (len(re.findall(r"\bv_(?:pk_)?(?:fma|mac|fmac)\w*_f32", body)), len(re.findall(r"\bv_div_fixup_f32", body)),
                 len(re.findall(r"\bv_sqrt_f32", body)))
-    per_div, one, _ = fused(probe_text, [n for n in re.findall(r"^(_Z\w+):", probe_text, re.M) if "probe_div" in n][0])
-    per_sqrt, _, one_root = fused(probe_text, [n for n in re.findall(r"^(_Z\w+):", probe_text, re.M) if "probe_sqrt" in n][0])
+    per_div, one, _ = fused([k for n, k in probes.items() if "probe_div" in n][0])
+    per_sqrt, _, one_root = fused([k for n, k in probes.items() if "probe_sqrt" in n][0])
     assert one == 1 and one_root == 1
     for name in sorted(kernels):
-        n_fused, n_div, n_sqrt = fused(text, name)
+        n_fused, n_div, n_sqrt = fused(kernels[name])
         print(f"{name}: {n_fused} fused operations, {n_div} quotients, {n_sqrt} roots")
         assert (n_div, n_sqrt) == (8, 1), (name, n_div, n_sqrt)
         assert n_fused == per_div * n_div + per_sqrt * n_sqrt + 2, (name, n_fused, per_div, per_sqrt)

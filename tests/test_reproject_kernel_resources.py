@@ -8,44 +8,20 @@ select_count_kernel / select_scan_kernel / select_write_kernel.  Every one must 
 occupancy of at least 4 -- the bar of the other helper kernels; splat and resolve declare no LDS and use none, the three select
 kernels a few words of it (the waves' popcounts; the scan's 16 wave sums and its carry).  Measured with hipcc
 --offload-arch=gfx950 (ROCm 7.2): the figures are printed."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
+import tools.asm_listing as asm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNELS = ("reproject_splat_kernel", "reproject_resolve_kernel", "select_count_kernel", "select_scan_kernel", "select_write_kernel")
 
 
-def _kernels(text):
-    """{symbol: (VGPRs, scratch bytes, occupancy, LDS bytes)} of every kernel of an assembly listing."""
-    out = {}
-    for name in re.findall(r"^(_Z\w+):", text, re.M):
-        tail = text[text.index(name + ":"):]
-        if "s_endpgm" not in tail:
-            continue
-        body = tail[:tail.index("s_endpgm")]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", tail).group(1))
-        assert "scratch_" not in body and "s_swappc" not in body, name
-        out[name] = (get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), get("LDSByteSize"))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_the_reproject_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    asm = str(tmp_path / "reproject.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "reproject.hip")]
-    assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    text = open(asm).read()
-    kernels = _kernels(text)
+@asm.needs_hipcc
+def test_the_reproject_kernels_use_no_scratch_and_at_most_128_vgprs():
+    kernels = asm.kernels(asm.listing("reproject.hip"))
     assert len(kernels) == len(KERNELS) and all(sum(k in name for name in kernels) == 1 for k in KERNELS), sorted(kernels)
-    for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
+    for name, k in sorted(kernels.items()):
+        asm.assert_no_scratch_no_call(k, name)
+        vgprs, scratch, occupancy, lds = k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["LDSByteSize"]
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0, (name, scratch)
         assert vgprs <= 128 and occupancy >= 4, (name, vgprs, occupancy)
@@ -54,7 +30,7 @@ def test_the_reproject_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
         else:
             assert lds == 0, (name, lds)
     # the depth test is ONE 64-bit vector atomic minimum, and only the splat holds it
-    body = lambda k: (lambda t: t[:t.index("s_endpgm")])(text[text.index([n for n in kernels if k in n][0] + ":"):])
+    body = lambda k: [v["body"] for n, v in kernels.items() if k in n][0]
     assert len(re.findall(r"\bglobal_atomic_umin_x2\b", body("reproject_splat_kernel"))) == 1
     assert all("atomic" not in body(k) for k in KERNELS[1:])
     # the definitions' products, quotients and sums stay separate fp32 operations: the file is built without contraction.  A
@@ -63,26 +39,21 @@ def test_the_reproject_kernels_use_no_scratch_and_at_most_128_vgprs(tmp_path):
     # its quotients and roots plus the fmaf it WRITES -- one more would be a contracted product of ours.  The splat divides five
     # times (the ray's three, u and v), takes two roots (the ray's norm, t') and writes four fmaf (the two squared norms, in the
     # ray generator's order); the resolve and the compaction hold none.
-    probe = tmp_path / "probe.hip"
-    probe.write_text("#include <hip/hip_runtime.h>\n"
-                     "__global__ void probe_div(const float* a, const float* b, float* o) { o[threadIdx.x] = a[threadIdx.x] / b[threadIdx.x]; }\n"
-                     "__global__ void probe_sqrt(const float* a, float* o) { o[threadIdx.x] = sqrtf(a[threadIdx.x]); }\n")
-    probe_asm = str(tmp_path / "probe.s")
-    assert subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-o", probe_asm,
-                           str(probe)], stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    probe_text = open(probe_asm).read()
+    probes = asm.kernels(asm.listing_of(
+        "#include <hip/hip_runtime.h>\n"
+        "__global__ void probe_div(const float* a, const float* b, float* o) { o[threadIdx.x] = a[threadIdx.x] / b[threadIdx.x]; }\n"
+        "__global__ void probe_sqrt(const float* a, float* o) { o[threadIdx.x] = sqrtf(a[threadIdx.x]); }\n", like="reproject.hip"))
 
-    def fused(listing, name):
-        b = listing[listing.index(name + ":"):]
-        b = b[:b.index("s_endpgm")]
+    def fused(kernel):
+        b = kernel["body"]
         return (len(re.findall(r"\bv_(?:pk_)?(?:fma|mac|fmac)\w*_f32", b)), len(re.findall(r"\bv_div_fixup_f32", b)),
                 len(re.findall(r"\bv_sqrt_f32", b)))
-    per_div, one, _ = fused(probe_text, [n for n in re.findall(r"^(_Z\w+):", probe_text, re.M) if "probe_div" in n][0])
-    per_sqrt, _, one_root = fused(probe_text, [n for n in re.findall(r"^(_Z\w+):", probe_text, re.M) if "probe_sqrt" in n][0])
+    per_div, one, _ = fused([k for n, k in probes.items() if "probe_div" in n][0])
+    per_sqrt, _, one_root = fused([k for n, k in probes.items() if "probe_sqrt" in n][0])
     assert one == 1 and one_root == 1
     expected = {"reproject_splat_kernel": (5, 2, 4)}
     for name in sorted(kernels):
-        n_fused, n_div, n_sqrt = fused(text, name)
+        n_fused, n_div, n_sqrt = fused(kernels[name])
         n_want_div, n_want_sqrt, written = next((v for k, v in expected.items() if k in name), (0, 0, 0))
         print(f"{name}: {n_fused} fused operations, {n_div} quotients, {n_sqrt} roots")
         assert (n_div, n_sqrt) == (n_want_div, n_want_sqrt), (name, n_div, n_sqrt)

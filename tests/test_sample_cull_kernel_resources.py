@@ -10,15 +10,11 @@ listed in the work-item loop, parent -> row-list flavour:
 The listing holds BOTH locate paths of the flavour (a launch mixes listed and unlisted layers) and an item runs one of them, so the
 difference as listed, 10 .. 20 instructions, bounds what an item can pay from above; the ceiling below is 32 (1 % of the exact-f32
 loop, 0.3 % of the split-bf16 one).  Registers: 392 / 476 and 496 / 496 VGPRs + AGPRs, the parents' counts; no scratch."""
-import os
 import re
-import shutil
-import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
-import pytest
+import tools.asm_listing as asm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 MARGIN = 32          # vector instructions as listed in the work-item loop, over the parent flavour
 
 # the patterns of tests/test_kernel_resources.py
@@ -26,52 +22,36 @@ PARENT = {"mlp_wave": r"_ZN6stnerf21mlp_wave_stage_kernelILb[01]E\S*", "mlp_bf16
 ROWS = {"mlp_wave": r"_ZN6stnerf26mlp_wave_stage_rows_kernelILb[01]E\S*", "mlp_bf16x3": r"_ZN6stnerf28mlp_bf16x3_stage_rows_kernelILb[01]E\S*"}
 
 
-def _compile_all(tmp_path, names):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    procs = {}
-    for name in names:
-        asm = str(tmp_path / (name + ".s"))
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
-               "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, name + ".hip")]
-        procs[name] = (subprocess.Popen(cmd, stderr=subprocess.DEVNULL), asm)
-    texts = {}
-    for name, (p, asm) in procs.items():
-        assert p.wait(timeout=900) == 0, name
-        texts[name] = open(asm).read()
-    return texts
-
-
-def _kernels(text, pattern):
-    """{deep_rgb: (vector instructions as listed in the work-item loop, VGPRs + AGPRs, scratch bytes, occupancy)} of the inference
+def _flavours(kernels, pattern):
+    """{deep_rgb: (vector instructions as listed in the work-item loop, VGPRs + AGPRs, scratch bytes, occupancy, MFMAs)} of the inference
     instantiations (the training tap's is not a parent of a row-list flavour)."""
     out = {}
-    for name in re.findall(r"^(%s):" % pattern, text, re.M):
-        if "StoreTapArgs" in name:
+    for name, k in kernels.items():
+        if not re.fullmatch(pattern, name) or "StoreTapArgs" in name:
             continue
-        tail = text[text.index(name + ":"):]
-        body = tail[:tail.index("s_endpgm")]
-        lines = body.split("\n")
+        lines = k["body"].split("\n")
         loop = next(i for i, l in enumerate(lines) if "This Loop Header: Depth=1" in l)
         ops = [l.split()[0] for l in lines[loop:] if l.startswith("\t") and l.strip() and not l.strip().startswith((".", ";"))]
         vec = sum(1 for o in ops if o.startswith("v_") and "mfma" not in o)
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", tail).group(1))
-        assert "scratch_" not in body and "s_swappc" not in body, name
-        out["ILb1E" in name] = (vec, get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), body.count("v_mfma"))
+        asm.assert_no_scratch_no_call(k, name)
+        out["ILb1E" in name] = (vec, k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["body"].count("v_mfma"))
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_row_list_flavours_cost_no_register_and_no_scratch(tmp_path):
-    texts = _compile_all(tmp_path, ["mlp_wave", "mlp_wave_rows", "mlp_bf16x3", "mlp_bf16x3_rows"])
+@asm.needs_hipcc
+def test_row_list_flavours_cost_no_register_and_no_scratch():
+    sources = ["mlp_bf16x3.hip", "mlp_bf16x3_rows.hip", "mlp_wave.hip", "mlp_wave_rows.hip"]
+    with ThreadPoolExecutor(len(sources)) as pool:          # (side by side; what another gate of this run compiled is not compiled again)
+        texts = dict(zip(sources, pool.map(asm.listing, sources)))
     for stem in ("mlp_wave", "mlp_bf16x3"):
-        parent_text, rows_text = texts[stem], texts[stem + "_rows"]
+        parent_text, rows_text = texts[stem + ".hip"], texts[stem + "_rows.hip"]
+        parent_kernels, rows_kernels = asm.kernels(parent_text), asm.kernels(rows_text)
         # a name of their own, in a file of their own: the parents' patterns see three kernels where they saw three, and none here
-        assert len(re.findall(r"^(%s):" % PARENT[stem], parent_text, re.M)) == 3
+        assert sum(bool(re.fullmatch(PARENT[stem], n)) for n in parent_kernels) == 3
         assert not re.findall(PARENT[stem], rows_text) and not re.findall(ROWS[stem], parent_text)
-        assert len(re.findall(r"^(%s):" % ROWS[stem], rows_text, re.M)) == 2
-        assert [int(v) for v in re.findall(r"; ScratchSize: (\d+)", rows_text)] == [0, 0]          # nothing else in the file
-        parent, rows = _kernels(parent_text, PARENT[stem]), _kernels(rows_text, ROWS[stem])
+        assert sum(bool(re.fullmatch(ROWS[stem], n)) for n in rows_kernels) == 2
+        assert [k["ScratchSize"] for k in rows_kernels.values()] == [0, 0]          # nothing else in the file
+        parent, rows = _flavours(parent_kernels, PARENT[stem]), _flavours(rows_kernels, ROWS[stem])
         assert sorted(parent) == sorted(rows) == [False, True]
         for deep in (False, True):
             (pv, pr, _, _, pm), (rv, rr, rs, ro, rm) = parent[deep], rows[deep]

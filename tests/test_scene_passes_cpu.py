@@ -11,6 +11,7 @@ import types
 import pytest
 import torch
 
+import tools.asm_listing as asm
 from conftest import REPO
 from stnerf_amd import hip, ops, synthetic as syn
 
@@ -95,26 +96,17 @@ def test_ops_refuse_cpu_tensors():
         ops.render_rays(torch.zeros(4, 9), boxes, nets, params, torch.zeros(16, dtype=torch.uint8), scene=True)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") and shutil.which("hipcc") is None, reason="no hipcc")
-def test_compositor_instantiations_resources(tmp_path):
+@asm.needs_hipcc
+def test_compositor_instantiations_resources():
     """The instantiations a render without the pass launches come first in the object and keep their occupancy targets (what
     tests/test_kernel_resources.py reads); the ones that write merged_weights and layer_scene_kernel use no scratch, and the new
     kernel loads its colours as vectors."""
-    src = os.path.join(REPO, "st-nerf_amd", "csrc", "composite.hip")
-    asm = tmp_path / "composite.s"
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function", "-ffp-contract=off",
-                    "-I" + os.path.join(REPO, "include"), "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(asm), src],
-                   check=True, stderr=subprocess.DEVNULL, timeout=600)
-    text = asm.read_text()
-    names = re.findall(r"^(_ZN6stnerf\w+):", text, re.M)
+    kernels = asm.kernels(asm.listing("composite.hip"))
+    names = [n for n in kernels if re.fullmatch(r"_ZN6stnerf\w+", n)]
 
     def kernel(name):
-        body = text[text.index(name + ":"):]
-        end = body.index("s_endpgm")
-        meta = body[end:end + 8000]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", meta).group(1))
-        return body[:end], get("NumVgprs"), get("ScratchSize"), get("Occupancy")
+        k = kernels[name]
+        return k["body"], k["NumVgprs"], k["ScratchSize"], k["Occupancy"]
 
     merge = [n for n in names if "composite_merge_kernel" in n]
     assert len(merge) == 12 and all("ELb0EEE" in n for n in merge[:6]) and all("ELb1EEE" in n for n in merge[6:]), merge

@@ -8,42 +8,16 @@ merge's dependent loads), so it must leave room for at least FOUR workgroups per
 128 VGPRs -- and use no scratch: every per-layer array of the merge (cursors, head depths) is indexed by compile-time constants and
 lives in registers.
 Measured with hipcc --offload-arch=gfx950 (ROCm 7.2): ray_stop_kernel<4 | 8 | 16>: 34 / 58 / 106 VGPRs, occupancy 8 / 8 / 4."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import tools.asm_listing as asm
 
 
-def _kernels(text):
-    """{symbol: (VGPRs, scratch bytes, occupancy, LDS bytes)} of every kernel of an assembly listing."""
-    out = {}
-    for name in re.findall(r"^(_Z\w+):", text, re.M):
-        tail = text[text.index(name + ":"):]
-        if "s_endpgm" not in tail:
-            continue
-        body = tail[:tail.index("s_endpgm")]
-        get = lambda k: int(re.search(r"; " + k + r": (\d+)", tail).group(1))
-        assert "scratch_" not in body and "s_swappc" not in body, name
-        out[name] = (get("TotalNumVgprs"), get("ScratchSize"), get("Occupancy"), get("LDSByteSize"))
-    return out
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-def test_the_termination_kernels_use_no_scratch_and_fit_four_workgroups_per_cu(tmp_path):
-    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
-    csrc = os.path.join(ROOT, "st-nerf_amd", "csrc")
-    asm = str(tmp_path / "termination.s")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-I" + csrc, "-S", "--cuda-device-only", "-o", asm, os.path.join(csrc, "termination.hip")]
-    assert subprocess.run(cmd, stderr=subprocess.DEVNULL, timeout=900).returncode == 0
-    kernels = _kernels(open(asm).read())
+@asm.needs_hipcc
+def test_the_termination_kernels_use_no_scratch_and_fit_four_workgroups_per_cu():
+    kernels = asm.kernels(asm.listing("termination.hip"))
     assert len(kernels) == 3 and all("ray_stop_kernel" in k for k in kernels), sorted(kernels)       # LCAP 4 / 8 / 16
-    for name, (vgprs, scratch, occupancy, lds) in sorted(kernels.items()):
+    for name, k in sorted(kernels.items()):
+        asm.assert_no_scratch_no_call(k, name)
+        vgprs, scratch, occupancy, lds = k["TotalNumVgprs"], k["ScratchSize"], k["Occupancy"], k["LDSByteSize"]
         print(f"{name}: {vgprs} VGPRs, scratch {scratch}, occupancy {occupancy}, LDS {lds}")
         assert scratch == 0 and lds == 0, (name, scratch, lds)
         assert vgprs <= 128 and occupancy >= 4, (name, vgprs, occupancy)

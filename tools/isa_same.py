@@ -1,41 +1,32 @@
 #!/usr/bin/env python3
 """Did a change of source leave the kernels alone?  Compares every kernel present in both of two gfx950 assembly files
-(hipcc -O3 -S --cuda-device-only): the instruction stream from the kernel's label to s_endpgm -- comments and blank lines
-dropped, local labels (.LBB.., .Lpost_getpc.., any .L..) renamed by order of first appearance -- and the resource lines
-TotalNumSgprs, TotalNumVgprs, ScratchSize, Occupancy, LDSByteSize (a kernel without one of them is an error, not a match).  One
-line per kernel; exit status 1 on any difference.
+(python st-nerf_amd/build.py --asm SOURCE OUT): the instruction stream from the kernel's label to s_endpgm -- comments and blank
+lines dropped, local labels (.LBB.., .Lpost_getpc.., any .L..) renamed by order of first appearance -- and the resource lines
+TotalNumSgprs, TotalNumVgprs, ScratchSize, Occupancy, LDSByteSize (a kernel without one of them is an error, not a match), both as
+tools/asm_listing.py's kernels() reads them.  One line per kernel; exit status 1 on any difference.
 
     python tools/isa_same.py OLD.s NEW.s"""
 import re
 import sys
 
+import asm_listing
+
 RESOURCES = ("TotalNumSgprs", "TotalNumVgprs", "ScratchSize", "Occupancy", "LDSByteSize")
 
 
 def kernels(path):
-    t = open(path).read()
     out = {}
-    for name in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", t, re.M):
-        m = re.search(r"^" + re.escape(name) + r":", t, re.M)
-        if not m or "s_endpgm" not in t[m.end():]:
-            continue
-        end = t.index("s_endpgm", m.end())
+    for name, k in asm_listing.kernels(open(path).read()).items():
         labels = {}
         lines = []
-        for line in t[m.end():end].split("\n"):
+        for line in k["body"].split("\n")[1:]:          # (behind the kernel's own label)
             line = line.split(";", 1)[0].strip()
             if line:
                 lines.append(re.sub(r"\.L[A-Za-z_]+\d+(_\d+)?", lambda l: labels.setdefault(l.group(0), ".L%d" % len(labels)), line))
-        nxt = t.find("; -- Begin function", end)   # the kernel's resource lines lie in front of the next function
-        meta = t[end:nxt] if nxt >= 0 else t[end:]
-        res = []
-        for k in RESOURCES:
-            r = re.search(r"^; %s: (\d+)" % k, meta, re.M)
-            if not r:
-                sys.exit("%s: no '; %s:' line behind %s" % (path, k, name))
-            res.append(r.group(1))
-        res = tuple(res)
-        out[name] = (lines, res)
+        missing = [r for r in RESOURCES if r not in k]
+        if missing:
+            sys.exit("%s: no '; %s:' line behind %s" % (path, missing[0], name))
+        out[name] = (lines, tuple(str(k[r]) for r in RESOURCES))
     return out
 
 

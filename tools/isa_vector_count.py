@@ -13,14 +13,10 @@ loop body (x 6 per item, includes the skip segment's copy) | sigma, rgb_net.1, c
 v_accvgpr_read/write; also prints scratch size (must be 0) and register counts.
 """
 import collections
-import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "st-nerf_amd", "csrc", "mlp_wave.hip")
+import asm_listing
 
 
 def classify(line):
@@ -60,12 +56,7 @@ def main():
         asm = args[args.index("--asm") + 1]
         args = [a for a in args if a not in ("--asm", asm)]
     flags = [a for a in args if a != "--deep"]
-    if asm is None:
-        asm = os.path.join(tempfile.mkdtemp(prefix="stnerf_isa_"), "mlp_wave.s")
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function", *flags,
-               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(SRC), "-S", "--cuda-device-only", "-o", asm, SRC]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    lines = open(asm).read().split("\n")
+    lines = (open(asm).read() if asm else asm_listing.listing("mlp_wave.hip", tuple(flags))).split("\n")
     tag = "ILb1E" if deep else "ILb0E"
     start = next(i for i, l in enumerate(lines) if l.startswith("_ZN6stnerf21mlp_wave_stage_kernel" + tag) and ":" in l.split(";")[0])
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Time the REFERENCE itself (DarlingHang/st-nerf imported from /root/reference) on the CPU of the build container, on the
+"""Time the REFERENCE itself (DarlingHang/st-nerf imported from the reference checkout) on the CPU of the build container, on the
 same sample bench.py's `cpu_baseline` leg times with the oracle port on the GPU box: 8 reference chunks of 3584 rays spread
-evenly over the rows of the 1080p benchmark view.  /root/reference does not exist on the GPU
+evenly over the rows of the 1080p benchmark view.  The reference checkout does not exist on the GPU
 box, so this figure can only be produced here; it is committed beside the port's figure.
 
     PYTHONDONTWRITEBYTECODE=1 python tools/time_reference_cpu.py > profiles/r02_reference_cpu_build_container.json
@@ -17,7 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.dont_write_bytecode = True
 sys.argv = [sys.argv[0]]
 sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
-import make_golden as G          # noqa: E402  (imports /root/reference with the SURVEY 8c shims)
+import make_golden as G          # noqa: E402  (imports the reference checkout with the SURVEY 8c shims)
 from bench import WORKLOADS, _oracle_ray_window   # noqa: E402
 from oracle import stnerf_oracle as O   # noqa: E402
 
