@@ -13,6 +13,7 @@ import accumulate_common as A
 import occupancy_common as OCC
 import scene_edits_common as S
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import bits, detach_models, same_bits
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from stnerf_amd.accumulate import AccumulateSpec
 
@@ -28,21 +29,7 @@ IDS3 = [1.0, 2.5, 3.0]
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in SE._BASE.values():
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.set_layer_cache(None)
-        m.replay = None
-        m.fresh_draws_per_call = False
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+    detach_models()
 
 
 def dev_i32(a):

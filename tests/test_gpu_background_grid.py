@@ -20,6 +20,7 @@ import scene_edits_common as S
 import test_background_grid_cpu as CPU
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import assert_pairs_equal, bits, detach_models, with_chain
 from stnerf_amd import hip, ops, synthetic as syn
 from stnerf_amd.occupancy import OccupancyGrids
 from test_gpu_occupancy import assert_same_bits
@@ -33,14 +34,7 @@ TAU = 1e-3               # (tests/test_gpu_termination.py: at this tau the dense
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.replay = None
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
+    detach_models()
 
 
 # ---------------------------------------------------------------------------------------- 1. the rows kernel vs numpy
@@ -194,106 +188,6 @@ def test_row_list_stage_kernels_with_the_background_listed_in_the_coarse_shape(p
 
 
 # ---------------------------------------------------------------------------------------- 3. the pipeline equals its definition
-def chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, rotations, occupancy_ids, background_id, flags, tau):
-    """What ``stnerf_render_rays_background`` is DEFINED to compute, from op-level entries: sampler, [ray cull,] compaction, the
-    UNLISTED coarse stage, ``raw[:, 0]`` zeroed in torch on EVERY ray at the samples the numpy rule does not list on the chain's own
-    points [and the performers' sample cull], composite_scene, [ray_stop,] resample, the unlisted fine stage, the same zeros [and
-    the hidden samples of the flagged layers], composite_scene.  flags: early ray termination's, one per layer."""
-    l, n1, n2 = model.total_layers, model.coarse_ray_sample, model.fine_ray_sample
-    n = rays.shape[0]
-    prec = model.bkgd_spacenet.precision
-    grids = model._occupancy
-    table, held = grids.table(model, occupancy_ids, rays.device, retiming) if occupancy_ids is not None else (None, [None] * l)
-    sampled = grids.samples
-    bg = grids.background_grid(model, background_id, rays.device)
-    bg_np = (OC.np_unpack(bg.bits.cpu().numpy().view(np.uint32), bg.res), bg.lo, bg.inv_cell)
-    ec, ef = model._point_edits(l, False), model._point_edits(l, True)
-    first, stripe, period = (int(x) for x in window)
-    rng = dict(seed=int(model.seed) & 0xFFFFFFFFFFFFFFFF, ray_index_base=first, ray_index_stripe=stripe, ray_index_period=period)
-    t_c, xyz_c, mask = ops.sample_coarse(rays, boxes, n1, jitter=replay["jitter"] if replay else None, edits=ec, pivot=pivot, raw_mask=True,
-                                         rotations=rotations, **rng)
-    if table is not None:
-        ops.occupancy_cull(xyz_c, mask, table)
-    lst, cnt = ops.compact_rays(mask)
-    shown = [True] + [model.is_shown_layer(i) for i in range(1, l)]
-    hit = (mask & 1).bool()
-
-    def stage(xyz, ns, fine, t=None, stop=None):
-        raw = torch.full((n, l, ns, 4), 7.0, device=rays.device)
-        layers = []
-        for i in range(l):
-            if not shown[i]:
-                continue
-            deform = model.bkgd_use_deform_time if i == 0 else model.use_deform_time
-            timed = (True if i > 0 else model.bkgd_use_space_time) and model.use_space_time
-            if i == 0:
-                space, motion = (model.bkgd_spacenet_fine if fine else model.bkgd_spacenet), model.bkgd_time_deform_net if deform else None
-            else:
-                j = model._module_index(i)
-                space, motion = (model.spacenets_fine if fine else model.spacenets)[j], model.time_deform_nets[j] if deform else None
-            layers.append(dict(space=space._packed(prec), motion=None if motion is None else motion._packed(prec), xyz=xyz[:, i], raw=raw[:, i],
-                               times=rays[:, (6 + i) if retiming else 6] if (timed or deform) else None,
-                               ray_list=None if i == 0 else lst[i], ray_count=None if i == 0 else cnt[i:i + 1], plain_time=i == 0,
-                               rotation=None if rotations is None else rotations[i]))
-        ops.mlp_stage(layers, rays[:, 3:6], ns, deep_rgb=model.deep_rgb, sigmoid_rgb=True)
-        pts = xyz.cpu().numpy()
-        for i in range(l):
-            if not shown[i]:
-                continue
-            off = torch.zeros(n, ns, dtype=torch.bool, device=rays.device)
-            if i == 0:                                             # the background's rule: every ray, no mask bit
-                off |= torch.from_numpy(~OC.np_points_occupied(pts[:, 0], *bg_np)).to(rays.device)
-            elif sampled and held[i] is not None:                  # the performers' sample cull, on the hit rays
-                g = held[i]
-                grid = (OC.np_unpack(g.bits.cpu().numpy().view(np.uint32), g.res), g.lo, g.inv_cell)
-                off |= torch.from_numpy(~SC.np_listed(pts[:, i], grid)).to(rays.device)
-            if fine and flags[i]:                                  # the hidden samples
-                off |= t[:, i] > stop[:, None]
-            raw[:, i][off if i == 0 else off & hit[:, i, None]] = 0.0
-        return raw
-
-    evaluated = [2] + [int(s) for s in shown[1:]]
-    kw = dict(border=float(model.boarder_weight), near=float(model.near), evaluated=evaluated, rgb_activated=True)
-    raw_c = stage(xyz_c, n1, False)
-    lo_c, mix_c, w_c, merged_c, scene_c = ops.composite_scene(t_c, raw_c, mask, fine=False, cut_negative_t=True, want_weights=True,
-                                                              thresholds=[None] + [thr if retiming else None] * (l - 1), **kw)
-    if only_coarse:
-        return mix_c, mix_c, lo_c, lo_c, mask & 1, scene_c
-    stop = ops.ray_stop(t_c, merged_c, tau) if any(flags) else None
-    t_f, xyz_f = ops.resample(t_c, w_c, n2, rays, u=replay.get("u") if replay else None, edits=ef, pivot=pivot, mask=mask, rotations=rotations,
-                              **rng)
-    raw_f = stage(xyz_f, n1 + n2, True, t_f, stop)
-    lo_f, mix_f, _, _, scene_f = ops.composite_scene(t_f, raw_f, mask, fine=True, cut_negative_t=False,
-                                                     thresholds=([bthr] + [thr] * (l - 1)) if retiming else None, **kw)
-    return mix_f, mix_c, lo_f, lo_c, mask & 1, scene_f
-
-
-def with_chain(model, monkeypatch, pairs, flags=None, tau=TAU, chain=True):
-    """Every launch of the model also runs the chain on the same arguments; ``pairs`` gets (pipeline outputs, chain outputs)."""
-    real = model._render_launch
-    flags = [False] * model.total_layers if flags is None else flags
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False, occupancy_ids=None,
-                background_id=None):
-        assert background_id is not None
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=True,
-                   occupancy_ids=occupancy_ids, background_id=background_id)
-        want = chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, rotations, occupancy_ids, background_id,
-                            flags, tau)
-        pairs.append((got, want))
-        return got if scene else got[:5]
-    monkeypatch.setattr(model, "_render_launch", wrapped)
-
-
-def assert_pairs_equal(pairs, what):
-    assert pairs
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")
-    for piece, (got, want) in enumerate(pairs):
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else torch.equal(bits(g), bits(w))
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
-
-
 def _attach(model, case, performers=(), **kw):
     """The res-4 x-z checkerboard on the background; ``performers``: those layers get the half_x grid (ray cull; samples=True: both)."""
     grids = OccupancyGrids(auto=False, **kw)
@@ -323,9 +217,9 @@ def test_pipeline_equals_its_definition(monkeypatch, precision, variant):
     else:
         grids = _attach(model, case)
     pairs = []
-    with_chain(model, monkeypatch, pairs, flags)
+    with_chain(model, monkeypatch, pairs, flags, TAU)
     SE.gpu_render(model, case, rays)
-    assert len(pairs) == (S.N + S.CAP - 1) // S.CAP
+    assert len(pairs) == (S.N + S.CAP - 1) // S.CAP and all(chain.launch.get("background_id") is not None for _, chain in pairs)
     assert_pairs_equal(pairs, f"{variant} {precision}")
     st = grids.stats()
     tested, skipped = st["background"]

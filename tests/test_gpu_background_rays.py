@@ -24,6 +24,7 @@ import test_gpu_background_grid as BGT
 import test_gpu_render_entries as RE
 import test_gpu_reproject as GR
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import assert_pairs_equal, bits, detach_models, with_chain
 from stnerf_amd import BackgroundCache, ops, parallel, synthetic as syn
 from stnerf_amd import reproject as rp
 from stnerf_amd.bkgd_cache import view_key
@@ -33,16 +34,12 @@ pytestmark = pytest.mark.gpu
 
 POISON = BGT.POISON
 TAU = BGT.TAU
-bits = BGT.bits
 
 
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in SE._BASE.values():
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.replay = None
+    detach_models()
 
 
 # ---------------------------------------------------------------------------------------- 1. the rows kernel vs numpy
@@ -193,73 +190,6 @@ def test_a_mixed_mask_selects_per_ray_between_the_plain_call_and_the_call_withou
     assert counts.tolist() == [S.CAP * per_ray, int((flags == 0).sum()) * per_ray]
 
 
-def chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, rotations, background_id, term, tau, ray_flags):
-    """What the render call under a per-ray mask is DEFINED to compute, from op-level entries (the chain of
-    tests/test_gpu_background_grid.py with one more term): sampler, compaction, the UNLISTED coarse stage, ``raw[:, 0]`` zeroed in
-    torch on the rays whose flag is zero [and at the samples the background grid's numpy rule does not list], composite_scene,
-    [ray_stop,] resample, the unlisted fine stage, the same zeros [and the hidden samples of the terminated layers], composite_scene."""
-    l, n1, n2 = model.total_layers, model.coarse_ray_sample, model.fine_ray_sample
-    n, dev = rays.shape[0], rays.device
-    prec = model.bkgd_spacenet.precision
-    bg_np = None
-    if background_id is not None:
-        bg = model._occupancy.background_grid(model, background_id, dev)
-        bg_np = (OC.np_unpack(bg.bits.cpu().numpy().view(np.uint32), bg.res), bg.lo, bg.inv_cell)
-    ec, ef = model._point_edits(l, False), model._point_edits(l, True)
-    first, stripe, period = (int(x) for x in window)
-    rng = dict(seed=int(model.seed) & 0xFFFFFFFFFFFFFFFF, ray_index_base=first, ray_index_stripe=stripe, ray_index_period=period)
-    t_c, xyz_c, mask = ops.sample_coarse(rays, boxes, n1, jitter=replay["jitter"] if replay else None, edits=ec, pivot=pivot, raw_mask=True,
-                                         rotations=rotations, **rng)
-    lst, cnt = ops.compact_rays(mask)
-    shown = [True] + [model.is_shown_layer(i) for i in range(1, l)]
-    hit = (mask & 1).bool()
-    masked = (ray_flags == 0).to(dev)
-
-    def stage(xyz, ns, fine, t=None, stop=None):
-        raw = torch.full((n, l, ns, 4), 7.0, device=dev)
-        layers = []
-        for i in range(l):
-            if not shown[i]:
-                continue
-            deform = model.bkgd_use_deform_time if i == 0 else model.use_deform_time
-            timed = (True if i > 0 else model.bkgd_use_space_time) and model.use_space_time
-            if i == 0:
-                space, motion = (model.bkgd_spacenet_fine if fine else model.bkgd_spacenet), model.bkgd_time_deform_net if deform else None
-            else:
-                j = model._module_index(i)
-                space, motion = (model.spacenets_fine if fine else model.spacenets)[j], model.time_deform_nets[j] if deform else None
-            layers.append(dict(space=space._packed(prec), motion=None if motion is None else motion._packed(prec), xyz=xyz[:, i], raw=raw[:, i],
-                               times=rays[:, (6 + i) if retiming else 6] if (timed or deform) else None,
-                               ray_list=None if i == 0 else lst[i], ray_count=None if i == 0 else cnt[i:i + 1], plain_time=i == 0,
-                               rotation=None if rotations is None else rotations[i]))
-        ops.mlp_stage(layers, rays[:, 3:6], ns, deep_rgb=model.deep_rgb, sigmoid_rgb=True)
-        off = masked[:, None].expand(n, ns).clone()                                   # the mask: every sample of a masked ray
-        if bg_np is not None:                                                         # the background's grid: every ray, no mask bit
-            off |= torch.from_numpy(~OC.np_points_occupied(xyz[:, 0].cpu().numpy(), *bg_np)).to(dev)
-        if fine and term[0]:
-            off |= t[:, 0] > stop[:, None]
-        raw[:, 0][off] = 0.0
-        for i in range(1, l):
-            if shown[i] and fine and term[i]:                                         # the hidden samples of a terminated performer
-                raw[:, i][(t[:, i] > stop[:, None]) & hit[:, i, None]] = 0.0
-        return raw
-
-    evaluated = [2] + [int(s) for s in shown[1:]]
-    kw = dict(border=float(model.boarder_weight), near=float(model.near), evaluated=evaluated, rgb_activated=True)
-    raw_c = stage(xyz_c, n1, False)
-    lo_c, mix_c, w_c, merged_c, scene_c = ops.composite_scene(t_c, raw_c, mask, fine=False, cut_negative_t=True, want_weights=True,
-                                                              thresholds=[None] + [thr if retiming else None] * (l - 1), **kw)
-    if only_coarse:
-        return mix_c, mix_c, lo_c, lo_c, mask & 1, scene_c
-    stop = ops.ray_stop(t_c, merged_c, tau) if any(term) else None
-    t_f, xyz_f = ops.resample(t_c, w_c, n2, rays, u=replay.get("u") if replay else None, edits=ef, pivot=pivot, mask=mask, rotations=rotations,
-                              **rng)
-    raw_f = stage(xyz_f, n1 + n2, True, t_f, stop)
-    lo_f, mix_f, _, _, scene_f = ops.composite_scene(t_f, raw_f, mask, fine=True, cut_negative_t=False,
-                                                     thresholds=([bthr] + [thr] * (l - 1)) if retiming else None, **kw)
-    return mix_f, mix_c, lo_f, lo_c, mask & 1, scene_f
-
-
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("variant", ["mask alone", "with a grid and termination of layer 0", "only_coarse with a grid"])
 def test_pipeline_equals_its_definition(monkeypatch, precision, variant):
@@ -277,21 +207,15 @@ def test_pipeline_equals_its_definition(monkeypatch, precision, variant):
         term = [True, False, True, False]
         assert model.termination.flags(model) == term
     flags = torch.from_numpy(_mixed_flags(S.CAP)).cuda()
-    pairs, real = [], model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, **kw):
-        assert kw.get("scene") and kw["background_rays"].shape == (rays.shape[0],) and (kw.get("background_id") is not None) == (grids is not None)
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, **kw)
-        want = chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, kw.get("rotations"),
-                            kw.get("background_id"), term, TAU, kw["background_rays"])
-        pairs.append((got, want))
-        return got
-    monkeypatch.setattr(model, "_render_launch", wrapped)
+    pairs = []
+    with_chain(model, monkeypatch, pairs, term, TAU)
     with torch.no_grad():
         model.render_rays_scene(rays, only_coarse, case["thr"], case["bthr"], ref_chunk=case["chunk"], background_rays=flags)
     torch.cuda.synchronize()
-    assert len(pairs) == 1
-    BGT.assert_pairs_equal(pairs, f"{variant} {precision}")
+    launch = pairs[0][1].launch
+    assert len(pairs) == 1 and launch["scene"] and launch["background_rays"].shape == (S.CAP,)
+    assert (launch.get("background_id") is not None) == (grids is not None)
+    assert_pairs_equal(pairs, f"{variant} {precision}")
     per_ray = case["n1"] if only_coarse else 2 * case["n1"] + case["n2"]
     if grids is not None:        # the one rows launch per stage counted every sample, the masked rays' among the not listed
         tested, skipped = grids.stats()["background"]

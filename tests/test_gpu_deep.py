@@ -25,10 +25,10 @@ import occupancy_common as OCC
 import scene_edits_common as S
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
-import test_gpu_termination as TERM
+from pipeline_chain import assert_pairs_equal, bits, cu, detach_models, np_bits, same_bits, with_chain
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from stnerf_amd.deep import DeepFrame, DeepSpec
-from test_gpu_occluder import A_VALUES, POISON, PAD, Z_KINDS, kernel_inputs, np_bits, np_same, padded, same_bits, bits
+from test_gpu_occluder import A_VALUES, POISON, PAD, Z_KINDS, kernel_inputs, np_same, padded
 from test_gpu_occupancy import attach
 
 pytestmark = pytest.mark.gpu
@@ -41,15 +41,7 @@ CONFIGS = [(0.0, 0.0), (1e-3, 0.0), (0.0, 0.25), (1e-3, 0.25)]
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.replay = None
-
-
-def cu(x, dt=torch.float32):
-    return torch.as_tensor(x).to("cuda", dt).contiguous()
+    detach_models()
 
 
 def deep_inputs(n, l, S_, seed):
@@ -331,54 +323,13 @@ def test_deep_composite_ties_to_the_scene_pass_and_to_the_occluder(n, l, S_):
 
 
 # ---------------------------------------------------------------------------------------- 3. the pipeline is the chain
-def with_chain(model, monkeypatch, pairs, flags, tau):
-    """Every deep launch of the model also runs the chain of op-level entries on the same arguments
-    (tests/test_gpu_termination.py's ``chain_render``), then deep_count -> deep_offsets -> deep_fill on the buffers the chain's
-    final composite_scene took and returned.  ``pairs`` gets (pipeline outputs, the chain's plain outputs, the chain's deep list)."""
-    real = model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False,
-                occupancy_ids=None, background_id=None, deep=None, **more):
-        assert background_id is None
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=scene,
-                   occupancy_ids=occupancy_ids, **(dict(deep=deep) if deep is not None else {}), **more)
-        if deep is None:
-            return got
-        calls, composite_scene = [], ops.composite_scene
-
-        def recording(*a, **k):
-            out = composite_scene(*a, **k)
-            calls.append((a, k, out))
-            return out
-        ops.composite_scene = recording
-        try:
-            want, _, _ = TERM.chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, flags, tau)
-        finally:
-            ops.composite_scene = composite_scene
-        assert len(calls) == 2
-        (a, k, out) = calls[0 if only_coarse else 1]
-        _, _, _, merged, scene_pass = out
-        kw = dict(w_min=deep["w_min"], merge_dz=deep["merge_dz"], rgb_activated=k["rgb_activated"], evaluated=k["evaluated"])
-        counts = ops.deep_count(a[0], a[2], merged, **kw)
-        offsets = ops.deep_offsets(counts, a[0].shape[1] * a[0].shape[2])
-        samples = torch.empty(int(offsets[-1]), 8, device="cuda")
-        ops.deep_fill(a[0], a[1], a[2], merged, offsets, samples, **kw)
-        if only_coarse:
-            lo_c, mix_c = out[0], out[1]
-            want = (mix_c, mix_c, lo_c, lo_c, want[4], scene_pass)
-        pairs.append((got, want, (offsets, samples)))
-        return got
-    monkeypatch.setattr(model, "_render_launch", wrapped)
-
-
 def assert_pairs(pairs, what, pieces):
-    assert len(pairs) == pieces, (what, len(pairs))
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")
-    for piece, (got, want, (offsets, samples)) in enumerate(pairs):
-        assert len(got) == 9
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else same_bits(g, w)
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
+    """The six outputs against the chain (tests/pipeline_chain.py), then the deep list against deep_count -> deep_offsets ->
+    deep_fill on the buffers the chain's final composite_scene took and returned."""
+    assert_pairs_equal(pairs, what, pieces)
+    for piece, (got, chain) in enumerate(pairs):
+        assert len(got) == 9 and chain.launch.get("background_id") is None
+        offsets, samples = chain.deep
         total = int(got[8])
         assert torch.equal(got[6], offsets) and total == samples.shape[0] > 0, f"{what}: piece {piece}: the offsets differ from the chain's"
         assert same_bits(got[7][:total], samples), f"{what}: piece {piece}: the records differ from deep_fill on the chain's buffers"
@@ -414,8 +365,8 @@ def test_pipeline_is_the_chain_of_op_level_entries(monkeypatch, precision, varia
     _, scene, frame = deep_render(model, case, rays, spec)
     assert_pairs(pairs, f"{precision} {variant}", PIECES)
     # the frame is the pieces' lists joined: its flatten is the scene pass up to the dropped mass (exactly the records' sum)
-    assert frame.offsets.shape[0] == S.N + 1 and int(frame.offsets[-1]) == frame.samples.shape[0] == sum(p[2][1].shape[0] for p in pairs)
-    joined = torch.cat([p[2][1] for p in pairs])
+    assert frame.offsets.shape[0] == S.N + 1 and int(frame.offsets[-1]) == frame.samples.shape[0] == sum(p[1].deep[1].shape[0] for p in pairs)
+    joined = torch.cat([p[1].deep[1] for p in pairs])
     assert same_bits(frame.samples, joined)
     st = frame.stats()
     assert st["samples"] == frame.samples.shape[0] and st["max"] <= l * (case["n1"] + (0 if case["only_coarse"] else case["n2"]))
@@ -428,7 +379,7 @@ def test_pipeline_is_the_chain_with_a_background_cache(monkeypatch):
     assert model._bkgd_cache is not None
     K, T = syn.camera(BC.H, BC.W, 15.0)
     pairs = []
-    with_chain(model, monkeypatch, pairs, [False] * 3, 0.0)
+    with_chain(model, monkeypatch, pairs)
     frames = []
     for fids in (BC.fids(True, 2, (1.0, 1.0)), BC.fids(True, 2, (2.5, 3.0))):
         out = parallel.render_view(model, K, T, BC.H, BC.W, fids, chuncks=BC.CHUNK, deep=DeepSpec())

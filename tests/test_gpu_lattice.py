@@ -14,6 +14,7 @@ import lattice_common as L
 import occupancy_common as OCC
 import scene_edits_common as S
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import bits, detach_models, same_bits
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from stnerf_amd.lattice import LatticeSpec
 
@@ -27,21 +28,7 @@ POISON_BYTE = 0xEE              # a status no kernel writes
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in SE._BASE.values():
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.set_layer_cache(None)
-        m.replay = None
-        m.fresh_draws_per_call = False
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+    detach_models()
 
 
 def dev(a, dtype=None):

@@ -15,6 +15,7 @@ import occluder_common as OCL
 import occupancy_common as OCC
 import scene_edits_common as S
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import bits, detach_models, same_bits
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from stnerf_amd.accumulate import AccumulateSpec
 from stnerf_amd.lens import Lens
@@ -32,21 +33,7 @@ KEYS = (0, 0x9E3779B9)
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in SE._BASE.values():
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.set_layer_cache(None)
-        m.replay = None
-        m.fresh_draws_per_call = False
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+    detach_models()
 
 
 def eq(a, b):

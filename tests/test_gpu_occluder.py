@@ -23,7 +23,7 @@ import occupancy_common as OCC
 import scene_edits_common as S
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
-import test_gpu_termination as TERM
+from pipeline_chain import assert_pairs_equal, bits, chain_render, cu, detach_models, np_bits, same_bits, with_chain
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from test_gpu_occupancy import attach
 
@@ -38,23 +38,7 @@ U = 2.0 ** -24
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.replay = None
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def np_bits(x):
-    return np.ascontiguousarray(x, F).view(np.uint32)
+    detach_models()
 
 
 def np_same(a, b):
@@ -111,7 +95,6 @@ def padded(shape):
 
 def run_kernel(d, scene_in, mixed_in, occ, rgb_activated, t=None, wm=None, optional=True):
     """stnerf_scene_occluder through the library on canaried outputs -> dict of CPU numpy outputs (None for a NULL one)."""
-    cu = lambda x, dt=torch.float32: torch.as_tensor(x).to("cuda", dt).contiguous()
     t_, raw, mask, wm_ = cu(d["t"] if t is None else t), cu(d["raw"]), cu(d["mask"], torch.uint8), cu(d["wm"] if wm is None else wm)
     n, l, S_ = t_.shape
     p = ops.composite_params(evaluated=d["evaluated"], rgb_activated=rgb_activated)
@@ -145,7 +128,6 @@ def colours(raw, rgb_activated):
 def test_scene_occluder_kernel(n, l, S_):
     d = kernel_inputs(n, l, S_, seed=1000 * n + 10 * l + S_)
     g = np.random.default_rng(5)
-    cu = lambda x, dt=torch.float32: torch.as_tensor(x).to("cuda", dt).contiguous()
     for rgb_activated in (False, True):
         # ---- (a) a real composite: z beyond every depth reproduces scene_out in front, z below every depth behind, bit for bit
         _, mixed, _, merged, scene = ops.composite_scene(cu(d["clean"]), cu(d["raw"]), cu(d["mask"], torch.uint8), fine=True,
@@ -243,61 +225,26 @@ def test_occluder_stop_kernel_equals_numpy(n):
 
 
 # ---------------------------------------------------------------------------------------- 3. the pipeline is the chain
-def with_chain(model, monkeypatch, pairs, flags, tau):
-    """Every launch of the model also runs the chain of op-level entries on the same arguments (tests/test_gpu_termination.py's
-    ``chain_render``: sampler .. composite_scene), then ``ops.scene_occluder`` on the buffers the chain's final composite_scene
-    took and returned; with the occluder stop the chain runs again on ``ops.occluder_stop`` of its own stop depths.  ``pairs``
-    gets (pipeline outputs, the chain's plain outputs, the chain's occluded outputs)."""
-    real = model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False,
-                occupancy_ids=None, background_id=None, occluder=None, occluder_stops=False):
-        assert background_id is None
-        kw = dict(rotations=rotations, scene=scene, occupancy_ids=occupancy_ids)
-        if occluder is not None:
-            kw.update(occluder=occluder, occluder_stops=occluder_stops)
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, **kw)
-        if occluder is None:
-            return got
-        calls, composite_scene = [], ops.composite_scene
-
-        def recording(*a, **k):
-            out = composite_scene(*a, **k)
-            calls.append((a, k, out))
-            return out
-        ops.composite_scene = recording
-        try:
-            chain = lambda **ckw: TERM.chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids,
-                                                    flags, tau, **ckw)
-            want, stop, _ = chain()
-            if occluder_stops and any(flags) and not only_coarse:
-                calls.clear()
-                want, _, _ = chain(t_stop=ops.occluder_stop(occluder, stop.clone()))
-        finally:
-            ops.composite_scene = composite_scene
-        assert len(calls) == 2
-        (a, k, out) = calls[0 if only_coarse else 1]
-        assert bool(k["fine"]) == (not only_coarse)
-        _, mixed, _, merged, scene_pass = out
-        occluded = ops.scene_occluder(a[0], a[1], a[2], merged, scene_pass, mixed, occluder, rgb_activated=k["rgb_activated"],
-                                      evaluated=k["evaluated"])
-        if only_coarse:
-            lo_c, mix_c = out[0], out[1]
-            want = (mix_c, mix_c, lo_c, lo_c, want[4], scene_pass)
-        pairs.append((got, want, occluded[:3]))
-        return got
-    monkeypatch.setattr(model, "_render_launch", wrapped)
+def occluder_after(model, flags, tau):
+    """What follows the chain (tests/pipeline_chain.py) in an occluded launch: ``ops.scene_occluder`` on the buffers the chain's final
+    composite_scene took and returned, kept as ``chain.occluded``; with the occluder stop the chain runs again on
+    ``ops.occluder_stop`` of its own stop depths first."""
+    def after(chain, launch):
+        occluder = launch["occluder"]
+        assert launch.get("background_id") is None
+        if launch.get("occluder_stops") and any(flags) and not launch["only_coarse"]:
+            chain = chain_render(model, launch, flags, tau, t_stop=ops.occluder_stop(occluder, chain.stop.clone()))
+        chain.occluded = ops.scene_occluder(chain.t, chain.raw, chain.mask, chain.merged, chain.scene, chain.mixed, occluder, rgb_activated=True,
+                                            evaluated=chain.evaluated)[:3]
+        return chain
+    return after
 
 
 def assert_pairs(pairs, what, pieces):
-    assert len(pairs) == pieces, (what, len(pairs))
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")
-    for piece, (got, want, occluded) in enumerate(pairs):
+    assert_pairs_equal(pairs, what, pieces)
+    for piece, (got, chain) in enumerate(pairs):
         assert len(got) == 9
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else same_bits(g, w)
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
-        for name, g, w in zip(("occluded_mixed", "occluded_scene", "occluder_share"), got[6:], occluded):
+        for name, g, w in zip(("occluded_mixed", "occluded_scene", "occluder_share"), got[6:], chain.occluded):
             assert same_bits(g, w), f"{what}: piece {piece}: {name} differs from ops.scene_occluder on the chain's buffers"
 
 
@@ -334,7 +281,7 @@ def test_pipeline_is_the_chain_of_op_level_entries(monkeypatch, precision, varia
         model.set_termination(TAU, layers=[1, 2], background=True)
         flags, tau = [True, True, True, False], TAU
     pairs = []
-    with_chain(model, monkeypatch, pairs, flags, tau)
+    with_chain(model, monkeypatch, pairs, flags, tau, after=occluder_after(model, flags, tau))
     stops = variant.endswith("stops")
     first = flat_all(occluded_render(model, case, rays, occ, stops=stops))
     assert_pairs(pairs, f"{precision} {variant}", PIECES)
@@ -364,7 +311,7 @@ def test_pipeline_is_the_chain_with_a_background_cache(monkeypatch):
     n = BC.H * BC.W
     occ = torch.from_numpy(OCL.case_occluder(n)).cuda()
     pairs = []
-    with_chain(model, monkeypatch, pairs, [False] * 3, 0.0)
+    with_chain(model, monkeypatch, pairs, after=occluder_after(model, [False] * 3, 0.0))
     outs = []
     for fids in (BC.fids(True, 2, (1.0, 1.0)), BC.fids(True, 2, (2.5, 3.0))):
         outs.append(flat_all(parallel.render_view(model, K, T, BC.H, BC.W, fids, chuncks=BC.CHUNK, occluder=occ)))

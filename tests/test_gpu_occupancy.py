@@ -15,6 +15,7 @@ import scene_edits_common as S
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
 from oracle import stnerf_oracle as O
+from pipeline_chain import detach_models
 from stnerf_amd import ops
 from stnerf_amd.occupancy import OccupancyGrids
 from test_gpu_ops import _net_close
@@ -23,12 +24,9 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
-def detach_grids():
-    """The models of the imported test modules are shared by the whole session: leave none with grids attached."""
+def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_occupancy(None)
-        m.replay = None
+    detach_models()
 
 
 def words(bits):

@@ -19,15 +19,17 @@ import pytest
 import torch
 
 import occupancy_common as OCC
+import pipeline_chain as CHAIN
 import proposal_common as PC
 import scene_edits_common as S
 import test_gpu_scene_edits_oracle as SE
-import test_gpu_termination as TERM
 from oracle import stnerf_oracle as O
 from stnerf_amd import hip, ops, synthetic as syn
 from stnerf_amd.deep import DeepSpec
 from stnerf_amd.proposal import ProposalGrids
-from test_gpu_occluder import POISON, bits, same_bits
+from pipeline_chain import bits, cu, same_bits, with_chain
+from test_gpu_occluder import POISON
+from test_gpu_termination import TAU
 from test_gpu_occupancy import attach
 
 pytestmark = pytest.mark.gpu
@@ -37,19 +39,8 @@ F = np.float32
 
 @pytest.fixture(autouse=True)
 def detach():
-    """The models of the imported test modules are shared by the whole session: leave none with anything attached."""
     yield
-    for m in SE._BASE.values():
-        m.set_proposal(None)
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.set_background_cache(None)
-        m.set_layer_cache(None)
-        m.replay = None
-
-
-def cu(x, dt=torch.float32):
-    return torch.as_tensor(x).to("cuda", dt).contiguous()
+    CHAIN.detach_models()
 
 
 # ---------------------------------------------------------------------------------------- 1. the lookup, bit for bit
@@ -181,118 +172,16 @@ def test_lookup_against_fp64_on_points_rebuilt_from_rays_depths_and_edits():
 
 
 # ---------------------------------------------------------------------------------------- 3. the pipeline is the chain
-def chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, proposal_ids, flags, tau,
-                 deep=None):
-    """What a render with grid proposals is DEFINED to compute, from op-level entries (tests/test_gpu_termination.py's chain with the
-    proposal in it): sampler, [ray cull,] compaction, the coarse stage WITHOUT the flagged layers [with the sample cull's zeros of the
-    others], ``ops.proposal_density`` on the flagged layers' slices, composite_scene, ray_stop, resample, the fine stage of every layer,
-    ``raw`` zeroed in torch at the hidden samples of the terminated layers [and the sample cull's], composite_scene [, the deep list]."""
-    l, n1, n2 = model.total_layers, model.coarse_ray_sample, model.fine_ray_sample
-    n = rays.shape[0]
-    prec = model.bkgd_spacenet.precision
-    grids = model._occupancy
-    table, held = grids.table(model, occupancy_ids, rays.device, retiming) if grids is not None else (None, [None] * l)
-    sampled = grids is not None and grids.samples
-    prop_table, _ = model.proposal.table(model, proposal_ids, rays.device, retiming)
-    ec, ef = model._point_edits(l, False), model._point_edits(l, True)
-    first, stripe, period = (int(x) for x in window)
-    rng = dict(seed=int(model.seed) & 0xFFFFFFFFFFFFFFFF, ray_index_base=first, ray_index_stripe=stripe, ray_index_period=period)
-    t_c, xyz_c, mask = ops.sample_coarse(rays, boxes, n1, jitter=replay["jitter"] if replay else None, edits=ec, pivot=pivot, raw_mask=True,
-                                         rotations=rotations, **rng)
-    if table is not None:
-        ops.occupancy_cull(xyz_c, mask, table)
-    lst, cnt = ops.compact_rays(mask)
-    shown = [True] + [model.is_shown_layer(i) for i in range(1, l)]
-    hit = (mask & 1).bool()
-    hit[:, 0] = True
-
-    def stage(xyz, ns, fine, t=None, stop=None):
-        raw = torch.full((n, l, ns, 4), 7.0, device=rays.device)
-        layers, staged = [], []
-        for i in range(l):
-            if not shown[i] or (not fine and prop_table[i] is not None):
-                continue
-            deform = model.bkgd_use_deform_time if i == 0 else model.use_deform_time
-            timed = (True if i > 0 else model.bkgd_use_space_time) and model.use_space_time
-            if i == 0:
-                space, motion = (model.bkgd_spacenet_fine if fine else model.bkgd_spacenet), model.bkgd_time_deform_net if deform else None
-            else:
-                j = model._module_index(i)
-                space, motion = (model.spacenets_fine if fine else model.spacenets)[j], model.time_deform_nets[j] if deform else None
-            layers.append(dict(space=space._packed(prec), motion=None if motion is None else motion._packed(prec), xyz=xyz[:, i], raw=raw[:, i],
-                               times=rays[:, (6 + i) if retiming else 6] if (timed or deform) else None,
-                               ray_list=None if i == 0 else lst[i], ray_count=None if i == 0 else cnt[i:i + 1], plain_time=i == 0,
-                               rotation=None if rotations is None else rotations[i]))
-            staged.append(i)
-        pts = xyz.cpu().numpy()                              # (the points the stage is given)
-        if layers:
-            ops.mlp_stage(layers, rays[:, 3:6], ns, deep_rgb=model.deep_rgb, sigmoid_rgb=True)
-        for i in staged:
-            off = torch.zeros(n, ns, dtype=torch.bool, device=rays.device)
-            if sampled and held[i] is not None:
-                g = held[i]
-                grid = (OCC.np_unpack(g.bits.cpu().numpy().view(np.uint32), g.res), g.lo, g.inv_cell)
-                off |= torch.from_numpy(~TERM.SC.np_listed(pts[:, i], grid)).to(rays.device)
-            if fine and flags[i]:
-                off |= t[:, i] > stop[:, None]
-            raw[:, i][off & hit[:, i, None]] = 0.0
-        if not fine:
-            for i in range(l):
-                if prop_table[i] is not None:
-                    ops.proposal_density(xyz[:, i], raw[:, i], prop_table[i], layer=i, ray_list=None if i == 0 else lst[i],
-                                         ray_count=None if i == 0 else cnt[i:i + 1])
-        return raw
-
-    evaluated = [2] + [int(s) for s in shown[1:]]
-    kw = dict(border=float(model.boarder_weight), near=float(model.near), evaluated=evaluated, rgb_activated=True)
-    raw_c = stage(xyz_c, n1, False)
-    lo_c, mix_c, w_c, merged_c, _ = ops.composite_scene(t_c, raw_c, mask, fine=False, cut_negative_t=True, want_weights=True,
-                                                        thresholds=[None] + [thr if retiming else None] * (l - 1), **kw)
-    stop = ops.ray_stop(t_c, merged_c, tau) if any(flags) else None
-    t_f, xyz_f = ops.resample(t_c, w_c, n2, rays, u=replay.get("u") if replay else None, edits=ef, pivot=pivot, mask=mask, rotations=rotations,
-                              **rng)
-    raw_f = stage(xyz_f, n1 + n2, True, t_f, stop)
-    alpha = model._layer_alpha_table()
-    lo_f, mix_f, _, merged_f, scene_f = ops.composite_scene(t_f, raw_f, mask, fine=True, cut_negative_t=False, sigma_scale=alpha,
-                                                            thresholds=([bthr] + [thr] * (l - 1)) if retiming else None, **kw)
-    out = (mix_f, mix_c, lo_f, lo_c, mask & 1, scene_f)
-    if deep is None:
-        return out, None
-    dkw = dict(w_min=deep["w_min"], merge_dz=deep["merge_dz"], rgb_activated=True, evaluated=evaluated)
-    counts = ops.deep_count(t_f, mask, merged_f, **dkw)
-    offsets = ops.deep_offsets(counts, l * (n1 + n2))
-    samples = torch.empty(int(offsets[-1]), 8, device="cuda")
-    ops.deep_fill(t_f, raw_f, mask, merged_f, offsets, samples, **dkw)
-    return out, (offsets, samples)
-
-
-def with_chain(model, monkeypatch, pairs, flags, tau):
-    """Every launch of the model also runs the chain on the same arguments; ``pairs`` gets (pipeline outputs, chain outputs, deep)."""
-    real = model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False,
-                occupancy_ids=None, background_id=None, deep=None, proposal_ids=None, **more):
-        assert background_id is None and not only_coarse and proposal_ids is not None and not more
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=True,
-                   occupancy_ids=occupancy_ids, proposal_ids=proposal_ids, **(dict(deep=deep) if deep is not None else {}))
-        want, dlist = chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, proposal_ids, flags, tau,
-                                   deep)
-        pairs.append((got, want, dlist))
-        return got if (scene or deep is not None) else got[:5]
-    monkeypatch.setattr(model, "_render_launch", wrapped)
-
-
 def assert_pairs_equal(pairs, what, pieces):
-    assert len(pairs) == pieces, (what, len(pairs))
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")       # all five outputs and scene_out
-    for piece, (got, want, dlist) in enumerate(pairs):
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else same_bits(g, w)
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
-        if dlist is not None:
+    CHAIN.assert_pairs_equal(pairs, what, pieces)
+    for piece, (got, chain) in enumerate(pairs):
+        launch = chain.launch
+        assert not launch["only_coarse"] and launch.get("proposal_ids") is not None, what
+        assert all(launch.get(k) is None for k in ("background_id", "background_rays", "occluder")), what
+        if chain.deep is not None:
             total = int(got[8])
-            assert torch.equal(got[6], dlist[0]) and total == dlist[1].shape[0] > 0, f"{what}: piece {piece}: the deep offsets differ"
-            assert same_bits(got[7][:total], dlist[1]), f"{what}: piece {piece}: the deep records differ"
+            assert torch.equal(got[6], chain.deep[0]) and total == chain.deep[1].shape[0] > 0, f"{what}: piece {piece}: the deep offsets differ"
+            assert same_bits(got[7][:total], chain.deep[1]), f"{what}: piece {piece}: the deep records differ"
 
 
 PIECES = (S.N + S.CAP - 1) // S.CAP
@@ -312,8 +201,8 @@ def setup_variant(model, case, variant):
     if variant == "culls":
         attach(model, OCC.manual_grids(case, "half_x", 0, layers=(1, 2)), samples=True)
     if variant == "terminated":
-        model.set_termination(TERM.TAU, layers=[1, 2], background=True)
-        flags, tau = [True, True, True, False], TERM.TAU
+        model.set_termination(TAU, layers=[1, 2], background=True)
+        flags, tau = [True, True, True, False], TAU
     if variant == "deep":
         spec = DeepSpec(1e-4, 0.25)
     model.set_proposal(grids)

@@ -26,6 +26,7 @@ import torch
 import reproject_common as R
 import scene_edits_common as S
 from instances_common import base_model
+from pipeline_chain import same_bits
 from stnerf_amd import hip, ops, parallel, synthetic as syn
 from stnerf_amd import reproject as rp
 
@@ -39,14 +40,6 @@ IDS = [1.0, 2.5, 3.0]
 DENSE = 4.0                     # added to the background's density biases (above)
 REL, A_MIN = 1.0, 0.5           # the drivers' guard (above) and alpha floor, passed explicitly everywhere
 ORBIT = 15.0
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def poisoned(*shape, dtype=torch.float32):

@@ -17,6 +17,7 @@ import sample_cull_common as SC
 import scene_edits_common as S
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
+from pipeline_chain import assert_pairs_equal, bits, detach_models, with_chain
 from stnerf_amd import hip, ops, synthetic as syn
 from stnerf_amd.occupancy import OccupancyGrids
 from test_gpu_occupancy import assert_same_bits, attach
@@ -27,15 +28,9 @@ POISON = 0x7FC0BEEF      # a NaN pattern no kernel writes
 
 
 @pytest.fixture(autouse=True)
-def detach_grids():
+def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_occupancy(None)
-        m.replay = None
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
+    detach_models()
 
 
 # ---------------------------------------------------------------------------------------- 1. the rows kernel vs numpy
@@ -179,93 +174,6 @@ def test_row_list_stage_kernels_write_the_unlisted_launch_s_bytes(precision, dee
 
 
 # ---------------------------------------------------------------------------------------- 3. the pipeline equals its definition
-def chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, rotations, occupancy_ids):
-    """What a sample-culled ``stnerf_render_rays_samples`` is DEFINED to compute, from op-level entries: sampler, ray cull,
-    compaction, the UNLISTED stage, the not-listed ``raw`` zeroed in torch by the numpy rule on the chain's own points,
-    composite, resample, the unlisted fine stage, zero, composite_scene."""
-    l, n1, n2 = model.total_layers, model.coarse_ray_sample, model.fine_ray_sample
-    prec = model.bkgd_spacenet.precision
-    grids = model._occupancy
-    table, held = grids.table(model, occupancy_ids, rays.device, retiming)
-    ec, ef = model._point_edits(l, False), model._point_edits(l, True)
-    first, stripe, period = (int(x) for x in window)
-    rng = dict(seed=int(model.seed) & 0xFFFFFFFFFFFFFFFF, ray_index_base=first, ray_index_stripe=stripe, ray_index_period=period)
-    t_c, xyz_c, mask = ops.sample_coarse(rays, boxes, n1, jitter=replay["jitter"] if replay else None, edits=ec, pivot=pivot, raw_mask=True,
-                                         rotations=rotations, **rng)
-    ops.occupancy_cull(xyz_c, mask, table)
-    lst, cnt = ops.compact_rays(mask)
-    shown = [True] + [model.is_shown_layer(i) for i in range(1, l)]
-
-    def stage(xyz, ns, fine):
-        raw = torch.full((rays.shape[0], l, ns, 4), 7.0, device=rays.device)
-        layers = []
-        for i in range(l):
-            if not shown[i]:
-                continue
-            deform = model.bkgd_use_deform_time if i == 0 else model.use_deform_time
-            timed = (True if i > 0 else model.bkgd_use_space_time) and model.use_space_time
-            if i == 0:
-                space, motion = (model.bkgd_spacenet_fine if fine else model.bkgd_spacenet), model.bkgd_time_deform_net if deform else None
-            else:
-                j = model._module_index(i)
-                space, motion = (model.spacenets_fine if fine else model.spacenets)[j], model.time_deform_nets[j] if deform else None
-            layers.append(dict(space=space._packed(prec), motion=None if motion is None else motion._packed(prec), xyz=xyz[:, i], raw=raw[:, i],
-                               times=rays[:, (6 + i) if retiming else 6] if (timed or deform) else None,
-                               ray_list=None if i == 0 else lst[i], ray_count=None if i == 0 else cnt[i:i + 1], plain_time=i == 0,
-                               rotation=None if rotations is None else rotations[i]))
-        ops.mlp_stage(layers, rays[:, 3:6], ns, deep_rgb=model.deep_rgb, sigmoid_rgb=True)
-        hit = (mask & 1).bool().cpu().numpy()
-        pts = xyz.cpu().numpy()
-        for i, g in enumerate(held):                             # the rule, on the chain's own points
-            if g is None:
-                continue
-            grid = (OC.np_unpack(g.bits.cpu().numpy().view(np.uint32), g.res), g.lo, g.inv_cell)
-            off = hit[:, i, None] & ~SC.np_listed(pts[:, i], grid)
-            raw[:, i][torch.from_numpy(off).to(raw.device)] = 0.0
-        return raw
-
-    evaluated = [2] + [int(s) for s in shown[1:]]
-    kw = dict(border=float(model.boarder_weight), near=float(model.near), evaluated=evaluated, rgb_activated=True)
-    raw_c = stage(xyz_c, n1, False)
-    lo_c, mix_c, w_c, _, scene_c = ops.composite_scene(t_c, raw_c, mask, fine=False, cut_negative_t=True, want_weights=not only_coarse,
-                                                       thresholds=[None] + [thr if retiming else None] * (l - 1), **kw)
-    if only_coarse:
-        return mix_c, mix_c, lo_c, lo_c, mask & 1, scene_c
-    t_f, xyz_f = ops.resample(t_c, w_c, n2, rays, u=replay.get("u") if replay else None, edits=ef, pivot=pivot, mask=mask, rotations=rotations,
-                              **rng)
-    raw_f = stage(xyz_f, n1 + n2, True)
-    alpha = model._layer_alpha_table()
-    if alpha is None:
-        alpha = [1.0] * l
-        if l > 2:
-            alpha[2] = float(model.alpha)
-    lo_f, mix_f, _, _, scene_f = ops.composite_scene(t_f, raw_f, mask, fine=True, cut_negative_t=False, sigma_scale=alpha,
-                                                     thresholds=([bthr] + [thr] * (l - 1)) if retiming else None, **kw)
-    return mix_f, mix_c, lo_f, lo_c, mask & 1, scene_f
-
-
-def with_chain(model, monkeypatch, pairs):
-    """Every launch of the model also runs the chain on the same arguments; ``pairs`` gets (pipeline outputs, chain outputs)."""
-    real = model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False, occupancy_ids=None):
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=True,
-                   occupancy_ids=occupancy_ids)
-        want = chain_render(model, rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, rotations, occupancy_ids)
-        pairs.append((got, want))
-        return got if scene else got[:5]
-    monkeypatch.setattr(model, "_render_launch", wrapped)
-
-
-def assert_pairs_equal(pairs, what):
-    assert pairs
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")
-    for piece, (got, want) in enumerate(pairs):
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else torch.equal(bits(g), bits(w))
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
-
-
 @pytest.mark.parametrize("precision", ["bf16x3", "fp32"])
 @pytest.mark.parametrize("only_coarse", [False, True])
 @pytest.mark.parametrize("edits", ["plain", "full"])

@@ -13,12 +13,12 @@ import torch
 import background_rays_common as BR
 import test_gpu_background_grid as BGT
 import test_gpu_background_rays as BRT
+from pipeline_chain import bits
 from stnerf_amd import ops
 
 pytestmark = pytest.mark.gpu
 
 POISON = BGT.POISON
-bits = BGT.bits
 SHAPES = [(n, ns) for n in (1, 16, 17, 197) for ns in (1, 64, 65, 129, 256)]
 L = 2                                  # the layers of the case's arrays; every call below works on slice 0 of them
 

@@ -11,6 +11,8 @@ import types
 import pytest
 import torch
 
+from pipeline_chain import bits
+
 from oracle import stnerf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +23,6 @@ def ops():
     from stnerf_amd import ops as _ops
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return _ops
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
 
 
 def scene(n, l, S, seed, hit=0.5, ties=True):

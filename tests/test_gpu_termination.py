@@ -21,6 +21,7 @@ import termination_common as TC
 import test_gpu_bkgd_cache as BC
 import test_gpu_scene_edits_oracle as SE
 import test_termination_cpu as CPU
+from pipeline_chain import assert_pairs_equal, bits, detach_models, with_chain
 from stnerf_amd import hip, ops, synthetic as syn
 from test_gpu_occupancy import assert_same_bits, attach
 
@@ -33,14 +34,7 @@ INF = float("inf")
 @pytest.fixture(autouse=True)
 def detach():
     yield
-    for m in list(SE._BASE.values()) + list(BC._MODELS.values()):
-        m.set_termination(None)
-        m.set_occupancy(None)
-        m.replay = None
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
+    detach_models()
 
 
 # ---------------------------------------------------------------------------------------- 1. the stop depth vs numpy
@@ -261,106 +255,6 @@ def test_row_list_stage_kernels_with_the_background_listed(precision):
 
 
 # ---------------------------------------------------------------------------------------- 4. the pipeline equals its definition
-def chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, flags, tau, t_stop=None,
-                 via_rows=False):
-    """What a terminated ``stnerf_render_rays_terminated`` is DEFINED to compute, from op-level entries: sampler, [ray cull,]
-    compaction, the unlisted coarse stage [with the sample cull's zeros], composite_scene, ray_stop, resample, the unlisted fine
-    stage, ``raw`` zeroed in torch at the hidden samples of the flagged layers [and the sample cull's], composite_scene.
-    t_stop: a tensor in place of ray_stop's.  via_rows: the flagged layers' fine stage through ``ops.visibility_rows`` and the
-    row-list stage launch instead of the unlisted launch and torch's zeros."""
-    l, n1, n2 = model.total_layers, model.coarse_ray_sample, model.fine_ray_sample
-    n = rays.shape[0]
-    prec = model.bkgd_spacenet.precision
-    grids = model._occupancy
-    table, held = grids.table(model, occupancy_ids, rays.device, retiming) if grids is not None else (None, [None] * l)
-    sampled = grids is not None and grids.samples
-    ec, ef = model._point_edits(l, False), model._point_edits(l, True)
-    first, stripe, period = (int(x) for x in window)
-    rng = dict(seed=int(model.seed) & 0xFFFFFFFFFFFFFFFF, ray_index_base=first, ray_index_stripe=stripe, ray_index_period=period)
-    t_c, xyz_c, mask = ops.sample_coarse(rays, boxes, n1, jitter=replay["jitter"] if replay else None, edits=ec, pivot=pivot, raw_mask=True,
-                                         rotations=rotations, **rng)
-    if table is not None:
-        ops.occupancy_cull(xyz_c, mask, table)
-    lst, cnt = ops.compact_rays(mask)
-    shown = [True] + [model.is_shown_layer(i) for i in range(1, l)]
-    hit = (mask & 1).bool()
-    hit[:, 0] = True
-
-    def stage(xyz, ns, fine, t=None, stop=None):
-        raw = torch.full((n, l, ns, 4), 7.0, device=rays.device)
-        layers = []
-        for i in range(l):
-            if not shown[i]:
-                continue
-            deform = model.bkgd_use_deform_time if i == 0 else model.use_deform_time
-            timed = (True if i > 0 else model.bkgd_use_space_time) and model.use_space_time
-            if i == 0:
-                space, motion = (model.bkgd_spacenet_fine if fine else model.bkgd_spacenet), model.bkgd_time_deform_net if deform else None
-            else:
-                j = model._module_index(i)
-                space, motion = (model.spacenets_fine if fine else model.spacenets)[j], model.time_deform_nets[j] if deform else None
-            ly = dict(space=space._packed(prec), motion=None if motion is None else motion._packed(prec), xyz=xyz[:, i], raw=raw[:, i],
-                      times=rays[:, (6 + i) if retiming else 6] if (timed or deform) else None,
-                      ray_list=None if i == 0 else lst[i], ray_count=None if i == 0 else cnt[i:i + 1], plain_time=i == 0,
-                      rotation=None if rotations is None else rotations[i])
-            if fine and via_rows and flags[i]:
-                g = held[i] if sampled else None
-                ly["row_list"], ly["row_count"] = ops.visibility_rows(t[:, i], stop, raw[:, i], xyz=xyz[:, i] if g is not None else None,
-                                                                      grid=None if g is None else g.entry(), layer=i, ray_list=ly["ray_list"],
-                                                                      ray_count=ly["ray_count"])
-            layers.append(ly)
-        ops.mlp_stage(layers, rays[:, 3:6], ns, deep_rgb=model.deep_rgb, sigmoid_rgb=True)
-        pts = xyz.cpu().numpy()
-        for i in range(l):
-            if not shown[i] or (fine and via_rows and flags[i]):
-                continue
-            off = torch.zeros(n, ns, dtype=torch.bool, device=rays.device)
-            if sampled and held[i] is not None:                    # the sample cull's rule, on the chain's own points
-                g = held[i]
-                grid = (OC.np_unpack(g.bits.cpu().numpy().view(np.uint32), g.res), g.lo, g.inv_cell)
-                off |= torch.from_numpy(~SC.np_listed(pts[:, i], grid)).to(rays.device)
-            if fine and flags[i]:                                  # the hidden samples
-                off |= t[:, i] > stop[:, None]
-            raw[:, i][off & hit[:, i, None]] = 0.0
-        return raw
-
-    evaluated = [2] + [int(s) for s in shown[1:]]
-    kw = dict(border=float(model.boarder_weight), near=float(model.near), evaluated=evaluated, rgb_activated=True)
-    raw_c = stage(xyz_c, n1, False)
-    lo_c, mix_c, w_c, merged_c, _ = ops.composite_scene(t_c, raw_c, mask, fine=False, cut_negative_t=True, want_weights=True,
-                                                        thresholds=[None] + [thr if retiming else None] * (l - 1), **kw)
-    stop = ops.ray_stop(t_c, merged_c, tau) if t_stop is None else t_stop
-    t_f, xyz_f = ops.resample(t_c, w_c, n2, rays, u=replay.get("u") if replay else None, edits=ef, pivot=pivot, mask=mask, rotations=rotations,
-                              **rng)
-    raw_f = stage(xyz_f, n1 + n2, True, t_f, stop)
-    lo_f, mix_f, _, _, scene_f = ops.composite_scene(t_f, raw_f, mask, fine=True, cut_negative_t=False,
-                                                     thresholds=([bthr] + [thr] * (l - 1)) if retiming else None, **kw)
-    return (mix_f, mix_c, lo_f, lo_c, mask & 1, scene_f), stop, raw_f
-
-
-def with_chain(model, monkeypatch, pairs, flags, tau, **chain_kw):
-    """Every launch of the model also runs the chain on the same arguments; ``pairs`` gets (pipeline outputs, chain outputs, the
-    chain's t_stop)."""
-    real = model._render_launch
-
-    def wrapped(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False, occupancy_ids=None):
-        got = real(rays, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=True,
-                   occupancy_ids=occupancy_ids)
-        want, stop, _ = chain_render(model, rays, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, flags, tau, **chain_kw)
-        pairs.append((got, want, stop))
-        return got if scene else got[:5]
-    monkeypatch.setattr(model, "_render_launch", wrapped)
-
-
-def assert_pairs_equal(pairs, what):
-    assert pairs
-    names = ("fine_mixed", "coarse_mixed", "fine_layer", "coarse_layer", "mask", "scene")
-    for piece, (got, want, _) in enumerate(pairs):
-        for name, g, w in zip(names, got, want):
-            same = torch.equal(g, w) if g.dtype == torch.uint8 else torch.equal(bits(g), bits(w))
-            assert same, f"{what}: piece {piece}: {name} differs from the chain of op-level entries"
-
-
 TAU = 1e-3     # (a large tau, at which the dense synthetic background hides about a third of layer 1's fine samples and most of
                # layer 2's: tests/test_termination_cpu.py ``oracle_cases`` has the scene's story)
 
@@ -381,7 +275,7 @@ def test_pipeline_equals_its_definition(monkeypatch, precision, background):
     SE.gpu_render(model, case, rays)
     assert len(pairs) == (S.N + S.CAP - 1) // S.CAP
     assert_pairs_equal(pairs, f"{precision} background={background}")
-    stops = torch.cat([p[2] for p in pairs]).cpu()
+    stops = torch.cat([p[1].stop for p in pairs]).cpu()
     assert bool(torch.isfinite(stops).any())
     rows = model.termination.stats()["rows"]
     assert sorted(rows) == ([0] if background else []) + [1, 2] and all(0 < skipped < tested for tested, skipped in rows.values()), rows
@@ -484,16 +378,7 @@ def test_an_infinite_stop_depth_changes_no_bit(monkeypatch, precision):
     model = SE.make_model(case, precision)
     l = model.total_layers
     pairs = []
-    real = model._render_launch
-
-    def wrapped(rays_, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece=None, rotations=None, scene=False, occupancy_ids=None):
-        got = real(rays_, boxes, pivot, retiming, only_coarse, thr, bthr, window, replay, piece, rotations=rotations, scene=True, occupancy_ids=occupancy_ids)
-        stop = torch.full((rays_.shape[0],), INF, device=rays_.device)
-        want, _, _ = chain_render(model, rays_, boxes, pivot, retiming, thr, bthr, window, replay, rotations, occupancy_ids, [True] * l, TAU,
-                                  t_stop=stop, via_rows=True)
-        pairs.append((got, want, stop))
-        return got if scene else got[:5]
-    monkeypatch.setattr(model, "_render_launch", wrapped)
+    with_chain(model, monkeypatch, pairs, [True] * l, TAU, t_stop=INF, via_rows=True)
     SE.gpu_render(model, case, rays)                             # (no termination attached: the un-terminated pipeline)
     assert_pairs_equal(pairs, f"t_stop = +inf, {precision}")
 
